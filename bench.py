@@ -12,6 +12,8 @@ the columns cloudy (McICA, ih = 1), aerosols on -- so the driver's N = 8 weak-sc
 Chou-Suarez pair irrad + sorad (configs[0] / configs[2] schemes), `--scheme irrad` / `--scheme sorad` one of them.
 Columns shard embarrassingly: every rank owns its own batch (weak scaling), there is no data-path
 collective; the only collectives are the timing barrier and the max-over-ranks of the time.
+The inputs are a pure function of the arguments, so `--dump-outputs DIR` (the last timed step's outputs as .npy files, see
+dump_outputs) lets two builds be compared output for output.
 
 One JSON line is printed by rank 0 (contract in the task statement), with
   roofline     : the kernel with the largest share of the step, timed live with HIP events on the launch stream
@@ -122,6 +124,27 @@ def all_over_ranks(value, world):
     got = [torch.zeros(1, dtype=torch.float64) for _ in range(world)]
     dist.all_gather(got, t)
     return [float(g.item()) for g in got]
+
+
+DUMP_BYTES = 60_000_000            # --dump-outputs: array bytes at most (64 MB in all with the .npy headers)
+DUMP_SEED = 20251015
+
+
+def dump_outputs(outdir, outputs, ncol):
+    """--dump-outputs DIR: the arrays the timed path hands its caller, as the last timed step left them, one DIR/<name>.npy each
+    (fp32 outputs as float32, every other type as float64).  Outputs larger than DUMP_BYTES in all are represented by a fixed,
+    seeded sample of the batch's columns, the same in every run with the same arguments; DIR/sample_columns.npy lists them.
+    `outputs`: {name: (device tensor, axis that indexes the columns)}."""
+    import torch
+    host = {k: (np.float32 if t.dtype == torch.float32 else np.float64) for k, (t, _) in outputs.items()}
+    per_col = 8 + sum(t.numel() // ncol * np.dtype(host[k]).itemsize for k, (t, _) in outputs.items())
+    n = min(ncol, DUMP_BYTES // per_col)
+    cols = np.arange(ncol) if n == ncol else np.sort(np.random.default_rng(DUMP_SEED).choice(ncol, n, replace=False))
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "sample_columns.npy"), cols.astype(np.float64))
+    for k, (t, axis) in outputs.items():
+        sel = t.index_select(axis, torch.from_numpy(cols).to(t.device))
+        np.save(os.path.join(outdir, k + ".npy"), sel.cpu().numpy().astype(host[k]))
 
 
 def _cpu_worker(args):
@@ -377,6 +400,13 @@ def bench_gridcomp(a, rank, world, dev, local_rank, aerosol, cpu):
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, world, torch.device("cpu"))
     ctx.check(stream)
+    if a.dump_outputs and rank == 0:
+        if a.scheme == "gridcomp":
+            outs = {k: (tl[k], 0 if k in ("OLRB", "DOLRB") else -1) for k in G.LWD_OUT + G.LWD_RAT_OUT if k in tl}
+            outs.update({k: (ts[k], -1) for k in G.SWD_OUT if k in ts})
+        else:           # the exports only: rt also holds inputs named like LW exports (SFCEM, DSFDTS)
+            outs = {k: (v[k], -1) for v, ks in ((lw, HB_LW), (sw, HB_SW), (rt, HB_RT)) for k in ks}
+        dump_outputs(a.dump_outputs, outs, ncol)
     dev_ms = ev0.elapsed_time(ev1) / a.steps
     if a.scheme == "gridcomp" and not a.no_overlap:
         dev_ms = elapsed / a.steps * 1e3          # two streams: the events of one do not bracket the other
@@ -815,6 +845,8 @@ def bench_mcica(a, rank, world, dev, local_rank, cpu):
     prof = ctx.profile_read()
     if rank != 0:
         return
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {k: (d[k], 0) for k in ("cldy_stoch", "ciwp_stoch", "clwp_stoch")}, ncol)
     ms, n = prof["k_mcica"]
     abytes = (5 * nlay + 1) * a.real + nsub * nlay * (4 + 2 * a.real)      # zm, play, cldf, ciwp, clwp, alat in; mask + 2 water paths out
     per_launch_s = ms / max(n, 1) * 1e-3
@@ -1300,7 +1332,12 @@ def main():
     ap.add_argument("--inputs-cache", default="", help="internal: directory with the parent run's generated inputs (np.save files)")
     ap.add_argument("--control-path-only", action="store_true",
                     help="no GPU work: launcher, rank -> shard, barrier, MAX over ranks and rank 0's JSON line only (CPU rehearsal / tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the outputs of the last one (rank 0's batch) as DIR/<name>.npy, float32 or float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of the columns when the batch is larger (DIR/sample_columns.npy)")
     a = ap.parse_args()
+    if a.dump_outputs and (a.control_path_only or a.ranks_per_gpu or a.configs_only):
+        sys.exit("bench.py: --dump-outputs needs the timed path of a --scheme run")
     import warnings
     warnings.filterwarnings("ignore", message="The given NumPy array is not writable")      # inputs mapped read-only from the cache
     if "WORLD_SIZE" not in os.environ:
@@ -1555,6 +1592,17 @@ def main():
     elapsed = max_over_ranks(elapsed, world, torch.device("cpu"))
     ctx.check(stream)
     prof = ctx.profile_read()
+    if a.dump_outputs and rank == 0:
+        keys = []
+        if do_lw:
+            keys += ["uflx", "dflx", "uflxc", "dflxc", "duflx_dTs", "duflxc_dTs", "clearCounts"]
+        if do_sw:           # with --lit: the full-size fields the lit columns' results were unpacked into
+            keys += list(PARITY_SW) + ["fswband"] + SW_OUT1 + (["clearCounts_sw"] if lit is None else [])
+        if do_irrad:        # taua / ssaa / asya are in-out: the caller gets them back rescaled
+            keys += ["ch_" + k for k in IRRAD_OUT + ("sfcem", "taudiag", "taua", "ssaa", "asya")]
+        if do_sorad:
+            keys += ["so_" + k for k in ("flx", "flc", "flxu", "flcu", "fdiruv", "fdifuv", "fdirpar", "fdifpar", "fdirir", "fdifir", "flx_sfc_band")]
+        dump_outputs(a.dump_outputs, {k: (d[k], -1) for k in keys}, ncol)
     # the dominant kernel's OWN launch duration: with the two solvers on two streams the HIP events around a kernel also cover the time
     # it shares the GPU with the other solver's kernels, so the roofline figure comes from two further steps enqueued on one stream
     prof1 = prof

@@ -226,3 +226,34 @@ def test_bench_inputs_cache_and_config_bytes(tmp_path):
     assert bench.cfg_algorithmic_bytes("cfg2_mcica_200") == 174244
     assert bench.cfg_algorithmic_bytes("cfg4_c720_share_137l_rrtmg_standin") == bench.algorithmic_bytes_sw(137, 4, True)
     assert len(bench.CFG_NAMES) == 7 and bench.cfg_algorithmic_bytes("cfg0_irrad_1000_clear") == 19476
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one DIR/<name>.npy per output, float32 kept, every other type as float64; a batch above the byte
+    budget is represented by the same seeded sample of its columns in every run, taken along each array's own column axis."""
+    import torch
+    import bench
+    ncol = 1000
+    flux = torch.arange(3 * ncol, dtype=torch.float32).reshape(3, ncol)
+    cc = torch.arange(2 * ncol, dtype=torch.int32).reshape(2, ncol)
+    stoch = torch.arange(2 * ncol, dtype=torch.float64).reshape(ncol, 2)
+    outs = {"flux": (flux, -1), "clearCounts": (cc, -1), "stoch": (stoch, 0)}
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40_000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), outs, ncol)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["clearCounts.npy", "flux.npy", "sample_columns.npy", "stoch.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 40_000 + 128 * len(files)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f), got[f[:-4]])
+    cols = got["sample_columns"].astype(np.int64)
+    assert len(cols) == 40_000 // (8 + 3 * 4 + 2 * 8 + 2 * 8) and (np.diff(cols) > 0).all() and cols[-1] < ncol
+    assert got["flux"].dtype == np.float32 and got["clearCounts"].dtype == np.float64 and got["stoch"].dtype == np.float64
+    np.testing.assert_array_equal(got["flux"], flux.numpy()[:, cols])
+    np.testing.assert_array_equal(got["clearCounts"], cc.numpy()[:, cols])
+    np.testing.assert_array_equal(got["stoch"], stoch.numpy()[cols])
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 ** 6)          # within the budget: every column
+    bench.dump_outputs(str(tmp_path / "c"), outs, ncol)
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "sample_columns.npy"), np.arange(ncol))
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "flux.npy"), flux.numpy())
