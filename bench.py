@@ -15,11 +15,20 @@ collective; the only collectives are the timing barrier and the max-over-ranks o
 The inputs are a pure function of the arguments, so `--dump-outputs DIR` (the last timed step's outputs as .npy files, see
 dump_outputs) lets two builds be compared output for output.
 
-One JSON line is printed by rank 0 (contract in the task statement), with
-  roofline     : the kernel with the largest share of the step, timed live with HIP events on the launch stream
+One JSON line is printed by rank 0.  A plain run does only what its headline figure needs: it generates the inputs, warms
+up, times the steps, writes --dump-outputs and prints the line (metric, value, unit, ms_per_step, higher_is_better, dtype,
+the workload, and kernels_ms_per_step from the timed steps' own HIP-event profile).  `--full` adds every figure that
+takes work of its own before or after the timed steps, with
+  roofline     : the kernel with the largest share of the step, timed live with HIP events on the launch stream (with
+                 two streams: from two further one-stream steps); its HBM traffic and roofline_compute from rocprofv3
+                 --pmc child runs
   cpu_baseline : RRTMG_LW = the reference's own Fortran (oracle/_ref); RRTMG_SW = the plain-C oracle (the
                  reference's rrtmg_sw driver needs ESMF/MAPL and cannot be built here) -- timed on the host
-                 cores on a bounded sample of the same workload.
+                 cores on a bounded sample of the same workload
+  f64, parity  : the default workload at real_kind 8, and in-run parity of the timed batch against the oracle
+  configs      : BASELINE configs[0] / [1] / [2] and a configs[4] stand-in, each timed on its own (default line only).
+A plain run on one stream (--no-overlap, a single solver, --scheme mcica | heartbeat) still carries `roofline`: it comes from
+the timed steps themselves.
 """
 import argparse
 import contextlib
@@ -425,9 +434,10 @@ def bench_gridcomp(a, rank, world, dev, local_rank, aerosol, cpu):
         kms = {"heartbeat (3 launches)": dev_ms}
     else:
         prof = ctx.profile_read()
-        # the dominant kernel's own launch duration: from two further steps on ONE stream (as in the default bench)
-        prof1, nst = prof, a.steps
-        if side is not None and sw_stream != stream:
+        # the dominant kernel's own launch duration: from two further steps on ONE stream (as in the default bench; --full only)
+        two_streams = side is not None and sw_stream != stream
+        prof1, nst = (None if two_streams else prof), a.steps
+        if two_streams and a.full:
             torch.cuda.synchronize()
             sw_stream = stream
             ctx.profile(True)
@@ -435,15 +445,17 @@ def bench_gridcomp(a, rank, world, dev, local_rank, aerosol, cpu):
                 step()
             torch.cuda.synchronize()
             prof1, nst = ctx.profile_read(), 2
-        cand = {k: v for k, v in prof1.items() if k in LW_BAND_KERNELS + SW_BAND_KERNELS and v[1] > 0}
-        kname = max(cand, key=lambda k: cand[k][0])
-        ms, n = prof1[kname]
-        abytes = (algorithmic_bytes_lw if kname.startswith("k_lw") else algorithmic_bytes_sw)(lm, a.real, aerosol)
-        per_launch_s = (ms / max(n, 1)) * 1e-3
-        achieved = abytes * ncol / (n / nst) / per_launch_s / 1e9
-        roof = {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "traffic": None,
-                "algorithmic_bytes_per_column": abytes, "avg_launch_ms": ms / max(n, 1), "launches": n,
-                "note": "same dominant kernel as the default bench; the driver adds prep / flip / post streaming kernels around the solvers"}
+        roof = None
+        if prof1 is not None:
+            cand = {k: v for k, v in prof1.items() if k in LW_BAND_KERNELS + SW_BAND_KERNELS and v[1] > 0}
+            kname = max(cand, key=lambda k: cand[k][0])
+            ms, n = prof1[kname]
+            abytes = (algorithmic_bytes_lw if kname.startswith("k_lw") else algorithmic_bytes_sw)(lm, a.real, aerosol)
+            per_launch_s = (ms / max(n, 1)) * 1e-3
+            achieved = abytes * ncol / (n / nst) / per_launch_s / 1e9
+            roof = {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "traffic": None,
+                    "algorithmic_bytes_per_column": abytes, "avg_launch_ms": ms / max(n, 1), "launches": n,
+                    "note": "same dominant kernel as the default bench; the driver adds prep / flip / post streaming kernels around the solvers"}
         wl = (f"RRTMG branches of LW_Driver + SORADCORE on GEOS-native fields (model ordering, SI units): {ncol} columns/GPU, {lm} layers, "
               f"McICA clouds on {100 * a.cloudy:.0f} % of the columns, aerosols {'on' if aerosol else 'off'}"
               + (f", RATS diagnostics for {', '.join(G.RAT_GAS[:a.rats])}" if a.rats else ""))
@@ -1294,6 +1306,58 @@ def configs_assemble(res, parity, cpu, live, ncol_default, steps_default, warmup
     return out
 
 
+def headline_roofline(a, prof, prof1, live, ncol, ncol_sw, nlay, aerosol, two_streams):
+    """(roofline, roofline_compute) of the headline line from the timed steps' profile `prof` or, with two streams, the profile `prof1`
+    of two further one-stream steps; `live`: this run's PMC counters (live_counters) or None"""
+    # dominant kernel = largest total time; its algorithmic bytes are those of the solver it belongs to
+    # (SURVEY 8(d): compulsory bytes at the solver API, every input read once + every output written once)
+    cand = {k: v for k, v in prof1.items() if k in LW_BAND_KERNELS + ("k_chou_bands", "k_sorad_pass", "k_sorad_col") + SW_BAND_KERNELS and v[1] > 0}
+    kname = max(cand, key=lambda k: cand[k][0])
+    ms, n = prof1[kname]
+    launches_per_step = n / (2 if prof1 is not prof else a.steps)
+    if kname == "k_chou_bands":
+        abytes = 19476 * a.real // 4                # SURVEY 8(d): Chou irrad 3 491 in + 1 378 out reals @72 layers
+    elif kname in ("k_sorad_pass", "k_sorad_col"):
+        abytes = 11904 * a.real // 4                # SURVEY 8(d): Chou sorad 2 670 in + 306 out reals
+    else:
+        abytes = (algorithmic_bytes_lw if kname.startswith("k_lw") else algorithmic_bytes_sw)(nlay, a.real, aerosol)
+    per_launch_s = (ms / max(n, 1)) * 1e-3
+    ncol_k = ncol_sw if kname in SW_BAND_KERNELS else ncol          # columns the dominant kernel's launches cover
+    achieved = abytes * (ncol_k / launches_per_step) / per_launch_s / 1e9 if per_launch_s > 0 else 0.0
+    # HBM bytes per launch of the dominant kernel: measured by this run's own rocprofv3 --pmc child runs (live_counters), else from the
+    # passes committed under profiles/ (FETCH_SIZE x 2 + WRITE_SIZE, separate --pmc runs) - those only for the exact configuration they
+    # were collected on
+    traffic = traffic_source = compute = None
+    default_paths = not (os.environ.get("GEOSRAD_LW_PATH") or os.environ.get("GEOSRAD_SORAD_PATH") or os.environ.get("GEOSRAD_LIB"))
+    ckey = None
+    if a.scheme == "lwsw" and default_paths and (ncol, ncol_sw, nlay, a.cloudy, aerosol, a.real) == (97_200, 97_200, 72, 0.6, True, 4):
+        ckey = "lwsw_97200_72_0.6_aer_f32"
+    elif a.scheme in ("chou", "irrad", "sorad") and default_paths and (ncol, nlay, a.cloudy, aerosol, a.real) == (100_000, 72, 0.6, True, 4):
+        ckey = "chou_100000_72_0.6_aer_f32"
+    t = None
+    if live is not None and kname in live:
+        t, traffic_source = dict(live[kname]), "measured in this run: rocprofv3 --pmc child runs of 3 one-stream steps of the same workload"
+        t["lane_ops_per_column"] = round(t["valu_insts"] * 64.0 / ncol_k) if "valu_insts" in t else None
+    elif ckey is not None:
+        t, traffic_source = committed_counters(ckey, kname)
+    if t is not None:
+        traffic = t["traffic_bytes"] / launches_per_step
+        if "valu_util" in t:
+            # SURVEY 8(d): the fused path is ~170 FLOP per compulsory byte, so the vector-ALU side is the second roofline
+            compute = {"kernel": kname, "valu_util": t["valu_util"], "lane_ops_per_column": t.get("lane_ops_per_column"),
+                       "valu_insts_per_step": t.get("valu_insts"), "wait_frac": t.get("wait_frac"), "source": traffic_source,
+                       "resident_waves_per_simd": t.get("resident_waves_per_simd"),
+                       "note": "valu_util = SQ_ACTIVE_INST_VALU x 4 / (GRBM_GUI_ACTIVE / 8 x 1024 SIMDs): share of the kernel's SIMD-cycles "
+                               "with a vector instruction in the pipe; lane_ops_per_column = SQ_INSTS_VALU x 64 lanes / columns; wait_frac = "
+                               "SQ_WAIT_ANY / SQ_WAVE_CYCLES"}
+    roof = {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+            "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": traffic_source,
+            "algorithmic_bytes_per_column": abytes, "avg_launch_ms": ms / max(n, 1), "launches": n,
+            "columns_per_launch": ncol_k / launches_per_step,
+            "note": roofline_note(kname, two_streams)}
+    return roof, compute
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1312,12 +1376,16 @@ def main():
     ap.add_argument("--lit", type=float, default=1.0, help="lwsw / sw: fraction of the columns RRTMG_SW runs on (packed daytime columns; default: all)")
     ap.add_argument("--rats", type=int, default=0, help="gridcomp: RATS diagnostics for the first N gases of gridcomp.RAT_GAS (0-8)")
     ap.add_argument("--coherent", type=int, default=1, help="repeat every K-th profile K times (gather-divergence sensitivity)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-f64", action="store_true", help="lwsw / lw / sw at --real 4: skip the real_kind 8 leg (3 + 5 steps after the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure: roofline (PMC counters from child rocprofv3 runs; two further "
+                         "one-stream steps), cpu_baseline, the f64 leg, in-run parity, and the `configs` legs of the default line")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-f64", action="store_true", help="with --full, lwsw / lw / sw at --real 4: skip the real_kind 8 leg (3 + 5 steps after the timed region)")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not collect the dominant kernels' PMC counters in child rocprofv3 runs before the timed run (roofline.traffic, roofline_compute "
-                         "then quote the figures committed under profiles/)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the in-run parity figures (256 columns of the timed batch against the oracle) and the f64 leg")
+                    help="with --full: do not collect the dominant kernels' PMC counters in child rocprofv3 runs before the timed run (roofline.traffic, "
+                         "roofline_compute then quote the figures committed under profiles/)")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="with --full: skip the in-run parity figures (256 columns of the timed batch against the oracle) and the f64 leg")
     ap.add_argument("--host-api", action="store_true",
                     help="lwsw / lw / sw: also time the drop-in host-pointer entry points (geosrad_rrtmg_lw / _sw: pinned staging, chunk-pipelined "
                          "H2D / kernels / D2H) on the same columns and report the PCIe-inclusive rate next to the device-resident one")
@@ -1325,8 +1393,8 @@ def main():
                     help="K1,K2,...: for each K, K child processes (Fortran drop-in callers, host arrays) share the GPU on 1/K of the batch each; "
                          "aggregate columns/s per K (what the MPI ranks of a node get)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="default line (lwsw, N = 1): skip the `configs` object - BASELINE configs[1] / [2] (RRTMG_LW clear-sky; RRTMG_SW + sorad + "
-                         "irrad + the 200-sub-column generator; 100 000 columns each) timed after the headline's legs")
+                    help="default line with --full (lwsw, N = 1): skip the `configs` object - BASELINE configs[1] / [2] (RRTMG_LW clear-sky; RRTMG_SW + "
+                         "sorad + irrad + the 200-sub-column generator; 100 000 columns each) timed after the headline's legs")
     ap.add_argument("--configs-only", action="store_true", help="run only the configuration legs (the PMC child of the default line)")
     ap.add_argument("--configs-legs", default="", help="with --configs-only: comma list of legs (default: all)")
     ap.add_argument("--inputs-cache", default="", help="internal: directory with the parent run's generated inputs (np.save files)")
@@ -1362,10 +1430,10 @@ def main():
 
     if a.configs_only:
         return configs_only(a, local_rank)
-    # the `configs` object rides on the default line only (one GPU, fp32 headline, every column lit)
-    want_cfg = (rank == 0 and world == 1 and a.gpus == 1 and a.scheme == "lwsw" and a.real == 4 and a.lit == 1.0 and a.coherent == 1
+    # the `configs` object rides on the default line with --full only (one GPU, fp32 headline, every column lit)
+    want_cfg = (a.full and rank == 0 and world == 1 and a.gpus == 1 and a.scheme == "lwsw" and a.real == 4 and a.lit == 1.0 and a.coherent == 1
                 and not a.no_configs and not a.host_api and not os.environ.get("GEOSRAD_BENCH_SORTED_CLOUDS"))
-    want_pmc = (rank == 0 and a.gpus == 1 and world == 1 and not a.no_pmc and a.scheme in ("lwsw", "lw", "sw", "chou", "irrad", "sorad")
+    want_pmc = (a.full and rank == 0 and a.gpus == 1 and world == 1 and not a.no_pmc and a.scheme in ("lwsw", "lw", "sw", "chou", "irrad", "sorad")
                 and not under_profiler())
     live = live_cfg = live_cfg2 = cache = None
     inp_main = None
@@ -1413,7 +1481,7 @@ def main():
         a.no_cpu = True           # the CPU leg times LW and SW on the same columns: not the --lit workload
     if want_cfg and not a.no_cpu:
         cpu_cfg = configs_cpu_baseline()
-    if rank == 0 and a.gpus == 1 and not a.no_cpu:                 # before any GPU initialisation in this process (fork pool)
+    if a.full and rank == 0 and a.gpus == 1 and not a.no_cpu:      # before any GPU initialisation in this process (fork pool)
         if a.scheme == "heartbeat":
             cpu = heartbeat_cpu_baseline(a.nlay)
         elif a.scheme == "mcica":
@@ -1605,8 +1673,9 @@ def main():
         dump_outputs(a.dump_outputs, {k: (d[k], -1) for k in keys}, ncol)
     # the dominant kernel's OWN launch duration: with the two solvers on two streams the HIP events around a kernel also cover the time
     # it shares the GPU with the other solver's kernels, so the roofline figure comes from two further steps enqueued on one stream
-    prof1 = prof
-    if side is not None:
+    # (--full only: without them a two-stream line has no roofline)
+    prof1 = prof if side is None else None
+    if side is not None and a.full:
         sw_stream = lw_stream = stream
         ctx.profile(True)
         for _ in range(2):
@@ -1637,7 +1706,7 @@ def main():
 
     # ---- the tolerance-qualifying precision and the in-run parity figures (N = 1, RRTMG schemes, every column lit) ---------------------
     f64_leg = parity = None
-    want_parity = (rank == 0 and world == 1 and (do_lw or do_sw) and lit is None and a.coherent == 1 and not a.no_parity
+    want_parity = (a.full and rank == 0 and world == 1 and (do_lw or do_sw) and lit is None and a.coherent == 1 and not a.no_parity
                    and not os.environ.get("GEOSRAD_BENCH_SORTED_CLOUDS"))         # the parity sample is taken in the generator's column order
     if want_parity:
         ns = min(PARITY_COLS, ncol)
@@ -1679,47 +1748,7 @@ def main():
     if rank == 0:
         total_cols = world * ncol * a.steps
         value = total_cols / elapsed
-        # dominant kernel = largest total time; its algorithmic bytes are those of the solver it belongs to
-        # (compulsory bytes at the solver API, every input read once + every output written once)
-        cand = {k: v for k, v in prof1.items() if k in LW_BAND_KERNELS + ("k_chou_bands", "k_sorad_pass", "k_sorad_col") + SW_BAND_KERNELS and v[1] > 0}
-        kname = max(cand, key=lambda k: cand[k][0])
-        ms, n = prof1[kname]
-        launches_per_step = n / (2 if prof1 is not prof else a.steps)
-        if kname == "k_chou_bands":
-            abytes = 19476 * a.real // 4                # Chou irrad 3 491 in + 1 378 out reals @72 layers
-        elif kname in ("k_sorad_pass", "k_sorad_col"):
-            abytes = 11904 * a.real // 4                # Chou sorad 2 670 in + 306 out reals
-        else:
-            abytes = (algorithmic_bytes_lw if kname.startswith("k_lw") else algorithmic_bytes_sw)(nlay, a.real, aerosol)
-        per_launch_s = (ms / max(n, 1)) * 1e-3
-        ncol_k = ncol_sw if kname in SW_BAND_KERNELS else ncol          # columns the dominant kernel's launches cover
-        achieved = abytes * (ncol_k / launches_per_step) / per_launch_s / 1e9 if per_launch_s > 0 else 0.0
-        # HBM bytes per launch of the dominant kernel: measured by this run's own rocprofv3 --pmc child runs (live_counters), else from the
-        # passes committed under profiles/ (FETCH_SIZE x 2 + WRITE_SIZE, separate --pmc runs) - those only for the exact configuration they
-        # were collected on
-        traffic = traffic_source = compute = None
-        default_paths = not (os.environ.get("GEOSRAD_LW_PATH") or os.environ.get("GEOSRAD_SORAD_PATH") or os.environ.get("GEOSRAD_LIB"))
-        ckey = None
-        if a.scheme == "lwsw" and default_paths and (ncol, ncol_sw, nlay, a.cloudy, aerosol, a.real) == (97_200, 97_200, 72, 0.6, True, 4):
-            ckey = "lwsw_97200_72_0.6_aer_f32"
-        elif a.scheme in ("chou", "irrad", "sorad") and default_paths and (ncol, nlay, a.cloudy, aerosol, a.real) == (100_000, 72, 0.6, True, 4):
-            ckey = "chou_100000_72_0.6_aer_f32"
-        t = None
-        if live is not None and kname in live:
-            t, traffic_source = dict(live[kname]), "measured in this run: rocprofv3 --pmc child runs of 3 one-stream steps of the same workload"
-            t["lane_ops_per_column"] = round(t["valu_insts"] * 64.0 / ncol_k) if "valu_insts" in t else None
-        elif ckey is not None:
-            t, traffic_source = committed_counters(ckey, kname)
-        if t is not None:
-            traffic = t["traffic_bytes"] / launches_per_step
-            if "valu_util" in t:
-                # the fused path is ~170 FLOP per compulsory byte, so the vector-ALU side is the second roofline
-                compute = {"kernel": kname, "valu_util": t["valu_util"], "lane_ops_per_column": t.get("lane_ops_per_column"),
-                           "valu_insts_per_step": t.get("valu_insts"), "wait_frac": t.get("wait_frac"), "source": traffic_source,
-                           "resident_waves_per_simd": t.get("resident_waves_per_simd"),
-                           "note": "valu_util = SQ_ACTIVE_INST_VALU x 4 / (GRBM_GUI_ACTIVE / 8 x 1024 SIMDs): share of the kernel's SIMD-cycles "
-                                   "with a vector instruction in the pipe; lane_ops_per_column = SQ_INSTS_VALU x 64 lanes / columns; wait_frac = "
-                                   "SQ_WAIT_ANY / SQ_WAVE_CYCLES"}
+        roof, compute = (None, None) if prof1 is None else headline_roofline(a, prof, prof1, live, ncol, ncol_sw, nlay, aerosol, side is not None)
         schemes = {"lwsw": "RRTMG_LW (140 g-points) + RRTMG_SW (112 g-points)", "lw": "RRTMG_LW (140 g-points)",
                    "sw": "RRTMG_SW (112 g-points)", "chou": "Chou-Suarez irrad (10 bands) + sorad (8 bands, 35 spectral passes)",
                    "irrad": "Chou-Suarez irrad (10 bands, trace gases on)", "sorad": "Chou-Suarez sorad (8 bands, 35 spectral passes)"}[a.scheme]
@@ -1738,11 +1767,7 @@ def main():
             "config": {"workload": wl, "schemes": schemes, "columns_per_gpu": ncol, "layers": nlay,
                        "cloudy_fraction": a.cloudy, "aerosol": aerosol, "hip_streams": 2 if side is not None else 1,
                        "sharding": "independent column batches per GPU, no collective"},
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                         "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_column": abytes, "avg_launch_ms": ms / max(n, 1), "launches": n,
-                         "columns_per_launch": ncol_k / launches_per_step,
-                         "note": roofline_note(kname, side is not None)},
+            "roofline": roof,
             "kernels_ms_per_step": {k: v[0] / a.steps for k, v in prof.items() if v[1] > 0},
             "cpu_baseline": cpu,
         }

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp && cd $R
 O=gpurun_out/final; rm -rf $O; mkdir -p $O
-b() { n=$1; shift; python3 bench.py "$@" > $O/$n.json 2> $O/$n.err; echo "$n: $(python3 -c "import json;d=json.loads(open('$O/$n.json').read().strip().splitlines()[-1]);print('%.2f ms/step %.3g %s' % (d['ms_per_step'], d['value'], d['unit']))" 2>&1)"; }
+b() { n=$1; shift; python3 bench.py --full "$@" > $O/$n.json 2> $O/$n.err; echo "$n: $(python3 -c "import json;d=json.loads(open('$O/$n.json').read().strip().splitlines()[-1]);print('%.2f ms/step %.3g %s' % (d['ms_per_step'], d['value'], d['unit']))" 2>&1)"; }
 b bench_lwsw --steps 20
 b bench_lwsw_one_stream --no-pmc --no-overlap --no-cpu --no-parity --no-configs
 b bench_lwsw_host_api --no-pmc --no-cpu --no-parity --host-api --steps 5

@@ -74,7 +74,7 @@ def test_bench_launches_its_own_ranks():
 def test_bench_two_ranks_on_one_gpu():
     """The N > 1 path of bench.py on a GPU, as the driver's multi-GPU run takes it (launcher -> two ranks -> barrier, MAX over ranks, one
     JSON line), rehearsed with both ranks on the box's one device (GEOSRAD_BENCH_REHEARSAL=1: gloo carries the barrier and the MAX - the
-    path has no data exchange).  Started as a child process; 2 x 20 000 columns."""
+    path has no data exchange).  Started as a child process; 2 x 20 000 columns; --full for the two-stream line's roofline."""
     import json
     import subprocess
     import sys
@@ -82,7 +82,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["GEOSRAD_BENCH_REHEARSAL"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--ncol", "20000",
-                        "--no-cpu", "--no-parity"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu", "--no-parity"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -95,6 +95,29 @@ def test_bench_two_ranks_on_one_gpu():
     assert roof["kernel"] in ("k_sw_reform", "k_lw_bands") and roof["peak"] == 8000.0 and 0 < roof["frac"] < 1
     assert roof["achieved"] == pytest.approx(roof["algorithmic_bytes_per_column"] * roof["columns_per_launch"] / (roof["avg_launch_ms"] * 1e-3) / 1e9, rel=1e-6)
     assert "configs" not in out and "cpu_baseline" in out
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_is_the_headline_alone():
+    """A plain `bench.py` run (no --full) prints the headline line and measures nothing that takes work of its own: no cpu_baseline,
+    f64 leg, parity or configs, and - two streams - no roofline (it would take two further one-stream steps).  Small batch."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--ncol", "20000"],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["metric"] == "columns/sec (LW+SW, 72 layers)" and out["unit"] == "columns/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["steps"] == 3 and out["warmup"] == 1 and out["config"]["hip_streams"] == 2
+    assert out["value"] == pytest.approx(20000 / (out["ms_per_step"] * 1e-3), rel=1e-9)
+    assert out["cpu_baseline"] is None and out["roofline"] is None
+    assert not {"f64", "parity", "parity_ok", "configs", "roofline_compute", "host_api"} & set(out)
+    assert out["kernels_ms_per_step"] and all(v >= 0 for v in out["kernels_ms_per_step"].values())
 
 
 @pytest.mark.gpu
