@@ -126,6 +126,17 @@ class Context:
     def workspace_bytes(self):
         return int(self.L.geosrad_workspace_bytes(self.h))
 
+    def set_overcast(self, irrad=False, sorad=False):
+        """The Chou-Suarez schemes as the reference builds them with -DOVERCAST (geosrad_set_overcast): every layer clear or fully cloudy,
+        random overlap, ict / icb not read.  One switch per scheme; both off (the default) is maximum-random overlap."""
+        self._chk(self.L.geosrad_set_overcast(self.h, ctypes.c_int((1 if irrad else 0) | (2 if sorad else 0))))
+
+    @property
+    def overcast(self):
+        """dict(irrad=bool, sorad=bool): the current geosrad_set_overcast mode."""
+        f = int(self.L.geosrad_get_overcast(self.h))
+        return {"irrad": bool(f & 1), "sorad": bool(f & 2)}
+
     # ---- RRTMG_LW, host arrays -------------------------------------------------------------------------
     def rrtmg_lw(self, ncol, nlay, psize, dudTs, play, plev, tlay, tlev, tsfc, emis,
                  h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr,

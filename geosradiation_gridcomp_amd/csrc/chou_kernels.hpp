@@ -1,7 +1,9 @@
 // chou_kernels.hpp -- hand-written HIP kernels (gfx950 / CDNA4) for the Chou-Suarez longwave scheme `irrad`.
 //
 // Reference behaviour: GEOSirrad_GridComp/irrad.F90:27-1338 (driver + band loop), helpers :1341-2780 (planck, *exps, tablup,
-// *kdis, cldovlp, sfcflux, mkicx/SORTIT); cloud optics GEOS_RadiationShared/getirtau.code:1-102.  Non-OVERCAST build.
+// *kdis, cldovlp, sfcflux, mkicx/SORTIT); cloud optics GEOS_RadiationShared/getirtau.code:1-102.  Both builds of the reference: the default
+// one (maximum-random overlap: mkicx + cldovlp) and -DOVERCAST (k_chou_bands<R, true>: every cloudy layer fully covered, random overlap -
+// the clear line of sight is the running product of the layers' cloud transmittances, irrad.F90:1187-1195; no sort, ict / icb unused).
 //
 // Unlike RRTMG (independent g-points, first-order vertical recurrences -> lane = column), irrad couples every pair of levels
 // (k1, k2): O(np^2) transmittance products per band.  Mapping here: ONE WAVEFRONT PER (column, band).
@@ -291,9 +293,10 @@ template <typename R> struct ChState {
 // ---------------------------------------------------------------------------------------------------
 // k_chou_bands: one wavefront per (CH_CPW columns, band); blockIdx.x = column group, blockIdx.y = band - 1.  Dynamic LDS.
 // The band is a template parameter of the body: which absorbers a band has, where their exponentials sit and how many running
-// products a lane carries are then compile-time facts (dead branches and their registers disappear).
+// products a lane carries are then compile-time facts (dead branches and their registers disappear).  OC: the reference's -DOVERCAST
+// build (no P2, no cldovlp; the record field CH_F_ICX stays unused, so both instantiations share one LDS layout).
 // ---------------------------------------------------------------------------------------------------
-template <typename R, int IBN>
+template <typename R, int IBN, bool OC>
 GR_DEV void chou_band_body(const ChouArgs<R> &A, const ChouDev<R> &T, unsigned char *ch_smem)
 {
     // CH_CPW columns per wavefront, CH_LPC = 64 / CH_CPW lanes each: loop 2000 walks one row k1 per lane in lock-step, rows of 73 .. 1
@@ -534,8 +537,9 @@ GR_DEV void chou_band_body(const ChouArgs<R> &A, const ChouDev<R> &T, unsigned c
         blevel[k] = v;
     }
     // ---- P2: clouds sorted by increasing N within each super-layer (mkicx / SORTIT :2729-2781), as a rank sort ----------
+    // (OVERCAST: not compiled, :658-665)
     int ncld0 = 0, ncld1 = 0, ncld2 = 0;
-    {
+    if constexpr (!OC) {
         bool anyc = false;
         for (int k = lane; k <= np; k += CH_LPC) anyc |= enn[k] > 0;
         if ((__ballot(anyc) & hmask) != 0) {
@@ -679,7 +683,7 @@ GR_DEV void chou_band_body(const ChouArgs<R> &A, const ChouDev<R> &T, unsigned c
         const int k1 = k1b + lane;
         const bool act = k1 <= np;
         ChState<R> S; reset_state(S);
-        R cldlw = 0, cldmd = 0, cldhi = 0, tranal = 1, taant = 1, trant = 1, fclr = 1;
+        R cldlw = 0, cldmd = 0, cldhi = 0, tranal = 1, taant = 1, trant = 1, fclr = 1, fclr_oc = 1;     // fclr_oc: OVERCAST fclr_above
         R axu = 0, acu = 0, aau = 0, axau = 0;                 // this lane's flxu(k1), flcu(k1), flau(k1), flxau(k1)
         R bd0 = 0, bd1 = 0, cd0 = 0, cd1 = 0, ad0 = 0, ad1 = 0, dd0 = 0, dd1 = 0;
         if (act) {
@@ -702,14 +706,16 @@ GR_DEV void chou_band_body(const ChouArgs<R> &A, const ChouDev<R> &T, unsigned c
                 // every LDS operand of the step is requested here, in front of the arithmetic (the aerosol-free set too: without aerosols
                 // du == bu, au == cu, dd == bd, ad == cd and taant == trant, so the same expressions serve both cases and the step has no
                 // uniform branches that would cut the requests into round trips of their own)
-                const R ekm = enn[km], tae = taer[km];
+                const R ekm = OC ? tcld[km] : enn[km], tae = taer[km];
                 const R bu0 = bu[k2 - 1], bu1 = bu[k2], du0 = du[k2 - 1], du1 = du[k2], cu0 = cu[k2 - 1], cu1 = cu[k2], au0 = au[k2 - 1], au1 = au[k2];
                 const R fxd = flxd[k2], fxad = flxad[k2], fcd = flcd[k2], fad = flad[k2];
                 taant = 1; trant = 1; fclr = 1;
                 layer_tran(km, true, S, trant);
                 taant = trant;
                 tranal = tranal * tae; trant = trant * tranal;          // taer == 1 without aerosols
-                if (ekm >= (R)0.001) {                        // cldovlp :2513-2601
+                if constexpr (OC) {
+                    fclr_oc = fclr_oc * ekm;                  // OVERCAST: fclr = fclr_above * tcldlyr(k2-1) (:1193-1195, :1046, :1275)
+                } else if (ekm >= (R)0.001) {                 // cldovlp :2513-2601
                     // the group's value is picked and put back with selects: a pointer to one of the three locals would move them to scratch
                     // memory (a load / store round trip per step, which was 30 % of a cloudy column's time)
                     const int g = km < ict ? 0 : (km < icb ? 1 : 2);
@@ -722,7 +728,8 @@ GR_DEV void chou_band_body(const ChouArgs<R> &A, const ChouDev<R> &T, unsigned c
                     }
                     cldhi = g == 0 ? v : cldhi; cldmd = g == 1 ? v : cldmd; cldlw = g == 2 ? v : cldlw;
                 }
-                fclr = ((R)1.0 - cldhi) * ((R)1.0 - cldmd) * ((R)1.0 - cldlw);
+                if constexpr (OC) fclr = fclr_oc;
+                else fclr = ((R)1.0 - cldhi) * ((R)1.0 - cldmd) * ((R)1.0 - cldlw);
                 {
                     // products rounded before they are added, as the reference's `xx = ...; flux = flux + xx` does: a clear column's all-sky and
                     // clear-sky fluxes stay bit-identical (fclr == 1), which a product fused into one of the two sums would break
@@ -782,7 +789,7 @@ GR_DEV void chou_band_body(const ChouArgs<R> &A, const ChouDev<R> &T, unsigned c
 #undef EX
 }
 
-template <typename R>
+template <typename R, bool OC = false>
 __global__ void __launch_bounds__(64) k_chou_bands(ChouArgs<R> A, const ChouDev<R> *__restrict__ Tp)
 {
     extern __shared__ __align__(16) unsigned char ch_smem[];
@@ -792,16 +799,16 @@ __global__ void __launch_bounds__(64) k_chou_bands(ChouArgs<R> A, const ChouDev<
 #else
     switch (blockIdx.y) {
 #endif
-        case 0: chou_band_body<R, 1>(A, T, ch_smem); break;
-        case 1: chou_band_body<R, 2>(A, T, ch_smem); break;
-        case 2: chou_band_body<R, 3>(A, T, ch_smem); break;
-        case 3: chou_band_body<R, 4>(A, T, ch_smem); break;
-        case 4: chou_band_body<R, 5>(A, T, ch_smem); break;
-        case 5: chou_band_body<R, 6>(A, T, ch_smem); break;
-        case 6: chou_band_body<R, 7>(A, T, ch_smem); break;
-        case 7: chou_band_body<R, 8>(A, T, ch_smem); break;
-        case 8: chou_band_body<R, 9>(A, T, ch_smem); break;
-        default: chou_band_body<R, 10>(A, T, ch_smem); break;
+        case 0: chou_band_body<R, 1, OC>(A, T, ch_smem); break;
+        case 1: chou_band_body<R, 2, OC>(A, T, ch_smem); break;
+        case 2: chou_band_body<R, 3, OC>(A, T, ch_smem); break;
+        case 3: chou_band_body<R, 4, OC>(A, T, ch_smem); break;
+        case 4: chou_band_body<R, 5, OC>(A, T, ch_smem); break;
+        case 5: chou_band_body<R, 6, OC>(A, T, ch_smem); break;
+        case 6: chou_band_body<R, 7, OC>(A, T, ch_smem); break;
+        case 7: chou_band_body<R, 8, OC>(A, T, ch_smem); break;
+        case 8: chou_band_body<R, 9, OC>(A, T, ch_smem); break;
+        default: chou_band_body<R, 10, OC>(A, T, ch_smem); break;
     }
 }
 

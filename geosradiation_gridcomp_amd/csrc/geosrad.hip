@@ -327,6 +327,7 @@ struct geosrad_ctx {
     bool lw_cols_path = false;      // RRTMG_LW band sweeps: parked cells in HBM (default) | GEOSRAD_LW_PATH=cols: on-chip intermediates
     bool lw_split_path = false;     //                       | GEOSRAD_LW_PATH=split: k-distribution layer-parallel (k_lw_cells) + recurrences (k_lw_sweep)
     int sw_path = 2;                // RRTMG_SW band sweeps: k_sw_reform (2, default) | GEOSRAD_SW_PATH=bands: k_sw_bands, the first mapping (0)
+    int overcast = 0;               // GEOSRAD_OVERCAST_IRRAD | GEOSRAD_OVERCAST_SORAD: the Chou-Suarez schemes as built with -DOVERCAST
     std::string last_error;
     hipStream_t stream = nullptr;   // internal stream of the host-pointer entry points
     // optional per-kernel timing with HIP events recorded on the launch stream (geosrad_profile*)
@@ -2281,7 +2282,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (!have_chou) return fail(GEOSRAD_EINVAL, "Chou-Suarez LW tables not set: call geosrad_load_tables_chou_lw first");
         if (m <= 0 || np < 4 || np > 400) return fail(GEOSRAD_EINVAL, "bad m/np");
         if (ns < 1 || ns > 15) return fail(GEOSRAD_EINVAL, "ns must be in 1..15");
-        if (!(ict >= 1 && ict < icb && icb <= np)) return fail(GEOSRAD_EINPUT, "ict / icb must satisfy 1 <= ict < icb <= np");
+        const bool oc = (overcast & GEOSRAD_OVERCAST_IRRAD) != 0;      // -DOVERCAST reads neither ict nor icb
+        if (!oc && !(ict >= 1 && ict < icb && icb <= np)) return fail(GEOSRAD_EINPUT, "ict / icb must satisfy 1 <= ict < icb <= np");
         if (nb < 10) return fail(GEOSRAD_EINVAL, "nb (bands of the aerosol arrays) must be 10");
         for (int k = 0; k < C_NIN; k++) if (!in[k]) return fail(GEOSRAD_EINVAL, "null input array");
         for (int k = 0; k < CO_NOUT; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
@@ -2299,8 +2301,9 @@ template <typename R> struct Ctx : geosrad_ctx {
 #define GEOSRAD_EXP_LDS_PAD 0
 #endif
         const size_t lds = chou_bands_lds_bytes<R>(np) + GEOSRAD_EXP_LDS_PAD;
+        const void *kb = oc ? (const void *)k_chou_bands<R, true> : (const void *)k_chou_bands<R>;
         if (lds > 64 * 1024) {
-            if (hipFuncSetAttribute((const void *)k_chou_bands<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            if (hipFuncSetAttribute(kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
                 return fail(GEOSRAD_EINVAL, "np too large for the LDS-resident band state");
         }
         for (int c0 = 0; c0 < m; c0 += nc_max) {
@@ -2319,7 +2322,8 @@ template <typename R> struct Ctx : geosrad_ctx {
             hipLaunchKernelGGL(k_chou_prep<R>, dim3((unsigned)((nc + 63) / 64), (unsigned)chou_prep_tiles<R>(np)), dim3(256), 0, st, A);
             span_end(st);
             span_begin(11, st);
-            hipLaunchKernelGGL(k_chou_bands<R>, dim3((unsigned)((nc + CH_CPW - 1) / CH_CPW), nband), dim3(64), lds, st, A, (const ChouDev<R> *)d_C);
+            if (oc) hipLaunchKernelGGL((k_chou_bands<R, true>), dim3((unsigned)((nc + CH_CPW - 1) / CH_CPW), nband), dim3(64), lds, st, A, (const ChouDev<R> *)d_C);
+            else hipLaunchKernelGGL(k_chou_bands<R>, dim3((unsigned)((nc + CH_CPW - 1) / CH_CPW), nband), dim3(64), lds, st, A, (const ChouDev<R> *)d_C);
             span_end(st);
             ChouOut<R> O{};
             auto Q = [&](int k) { return (R *)out[k] + c0; };
@@ -2408,7 +2412,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (!have_sorad) return fail(GEOSRAD_EINVAL, "Chou-Suarez SW tables not set: call geosrad_load_tables_chou_sw first");
         if (m <= 0 || np < 4 || np > 400) return fail(GEOSRAD_EINVAL, "bad m/np");
         if (nb < 8) return fail(GEOSRAD_EINVAL, "nb (bands of the aerosol arrays) must be 8");
-        if (!(ict >= 1 && ict < icb && icb <= np)) return fail(GEOSRAD_EINPUT, "ict / icb must satisfy 1 <= ict < icb < np + 1");
+        const bool oc = (overcast & GEOSRAD_OVERCAST_SORAD) != 0;      // -DOVERCAST reads neither ict nor icb
+        if (!oc && !(ict >= 1 && ict < icb && icb <= np)) return fail(GEOSRAD_EINPUT, "ict / icb must satisfy 1 <= ict < icb < np + 1");
         if (!hk_uv || !hk_ir) return fail(GEOSRAD_EINVAL, "hk_uv / hk_ir null");
         for (int k = 0; k < SI_NIN; k++) if (!in[k]) return fail(GEOSRAD_EINVAL, "null input array");
         for (int k = 0; k < SOO_DRBAND; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
@@ -2418,11 +2423,12 @@ template <typename R> struct Ctx : geosrad_ctx {
         const size_t per = (size_t)nc_max * sizeof(R);
         // passes: k_sorad_pass (lane = column, the per-level arrays of every pass in HBM scratch planes, 30 x K2 reals per (column, pass))
         // or k_sorad_col (one block per column, everything on chip, no scratch; GEOSRAD_SORAD_PATH=col)
-        // (a layer count whose on-chip arrays exceed the LDS takes the scratch-plane path)
-        const bool col_path = sorad_col_path && K2 <= 256 && sorad_col_lds_reals<R>(np) * sizeof(R) <= (size_t)160 * 1024;
+        // (a layer count whose on-chip arrays exceed the LDS takes the scratch-plane path; so does OVERCAST: k_sorad_col has no OVERCAST
+        // variant, the OVERCAST passes are k_sorad_pass_oc whatever GEOSRAD_SORAD_PATH says)
+        const bool col_path = !oc && sorad_col_path && K2 <= 256 && sorad_col_lds_reals<R>(np) * sizeof(R) <= (size_t)160 * 1024;
         const size_t o_lay = 0, o_swh = o_lay + al(4 * K2 * per), o_colv = o_swh + al(K2 * per), o_cld = o_colv + al(8 * per),
                      o_psum = o_cld + al((size_t)SO_NGRP * 4 * K2 * per), o_aer = o_psum + al((size_t)SO_NPASS * 3 * per),
-                     o_perm = o_aer + (col_path ? 0 : al((size_t)3 * SO_NGATHER * np * per)), o_cls = o_perm + al((size_t)nc_max * sizeof(int32_t)),
+                     o_perm = o_aer + (col_path || oc ? 0 : al((size_t)3 * SO_NGATHER * np * per)), o_cls = o_perm + al((size_t)nc_max * sizeof(int32_t)),
                      o_off = o_cls + al((size_t)nc_max), o_scr = o_off + al(16 * sizeof(int32_t)),
                      need = o_scr + (col_path ? 0 : al((size_t)SO_NPASS * SO_NPLANE * K2 * per));
         const size_t so_lds = sorad_col_lds_reals<R>(np) * sizeof(R);
@@ -2450,18 +2456,24 @@ template <typename R> struct Ctx : geosrad_ctx {
             A.rsuvdf = P(SI_RSUVDF); A.rsirbm = P(SI_RSIRBM); A.rsirdf = P(SI_RSIRDF);
             A.lay = (R *)(d_ws_so + o_lay); A.swh = (R *)(d_ws_so + o_swh); A.colv = (R *)(d_ws_so + o_colv); A.cld = (R *)(d_ws_so + o_cld);
             A.psum = (R *)(d_ws_so + o_psum); A.scr = col_path ? nullptr : (R *)(d_ws_so + o_scr);
-            A.aer = col_path ? nullptr : (R *)(d_ws_so + o_aer); A.perm = (int32_t *)(d_ws_so + o_perm); A.cls = (uint8_t *)(d_ws_so + o_cls);
+            A.aer = col_path || oc ? nullptr : (R *)(d_ws_so + o_aer); A.perm = (int32_t *)(d_ws_so + o_perm); A.cls = (uint8_t *)(d_ws_so + o_cls);
             A.cls_off = (int32_t *)(d_ws_so + o_off);
             const dim3 blk(256);
             const unsigned gx = (unsigned)((nc + 255) / 256);
             span_begin(12, st);
-            // the columns sorted by which cloud groups hold cloud (8 classes): workspace by position from here on (the on-chip path keeps the
-            // caller's order: one class)
-            hipLaunchKernelGGL(k_sorad_class<R>, dim3(gx), blk, 0, st, A, col_path ? 1 : 0);
-            hipLaunchKernelGGL(k_partition8, dim3(1), dim3(1024), 0, st, nc, (const uint8_t *)A.cls, A.perm, A.cls_off);
-            if (!col_path) hipLaunchKernelGGL(k_sorad_gather<R>, dim3(gx, (unsigned)(3 * SO_NGATHER * np)), blk, 0, st, A);
-            hipLaunchKernelGGL(k_sorad_prep<R>, dim3(gx), blk, 0, st, A);
-            hipLaunchKernelGGL(k_sorad_cloud<R>, dim3(gx, (unsigned)np), blk, 0, st, A, (const SoradDev<R> *)d_O);
+            if (oc) {          // OVERCAST: one class, positions are columns
+                hipLaunchKernelGGL(k_sorad_ident<R>, dim3(gx), blk, 0, st, A);
+                hipLaunchKernelGGL(k_sorad_prep<R>, dim3(gx), blk, 0, st, A);
+                hipLaunchKernelGGL((k_sorad_cloud<R, true>), dim3(gx, (unsigned)np), blk, 0, st, A, (const SoradDev<R> *)d_O);
+            } else {
+                // the columns sorted by which cloud groups hold cloud (8 classes): workspace by position from here on (the on-chip path keeps the
+                // caller's order: one class)
+                hipLaunchKernelGGL(k_sorad_class<R>, dim3(gx), blk, 0, st, A, col_path ? 1 : 0);
+                hipLaunchKernelGGL(k_partition8, dim3(1), dim3(1024), 0, st, nc, (const uint8_t *)A.cls, A.perm, A.cls_off);
+                if (!col_path) hipLaunchKernelGGL(k_sorad_gather<R>, dim3(gx, (unsigned)(3 * SO_NGATHER * np)), blk, 0, st, A);
+                hipLaunchKernelGGL(k_sorad_prep<R>, dim3(gx), blk, 0, st, A);
+                hipLaunchKernelGGL(k_sorad_cloud<R>, dim3(gx, (unsigned)np), blk, 0, st, A, (const SoradDev<R> *)d_O);
+            }
             span_end(st);
             SoradOut<R> O{};
             auto Q = [&](int k) { return out[k] ? (R *)out[k] + c0 : (R *)nullptr; };
@@ -2469,7 +2481,9 @@ template <typename R> struct Ctx : geosrad_ctx {
             O.fdifpar = Q(SOO_FDIFPAR); O.fdirir = Q(SOO_FDIRIR); O.fdifir = Q(SOO_FDIFIR); O.flxu = Q(SOO_FLXU); O.flcu = Q(SOO_FLCU);
             O.flx_sfc_band = Q(SOO_SFCBAND); O.drband = Q(SOO_DRBAND); O.dfband = Q(SOO_DFBAND);
             span_begin(13, st);
-            if (col_path) {   // one block per column, lanes = (pass slot, level) (whole wavefronts), all 35 passes on chip
+            if (oc) {
+                hipLaunchKernelGGL(k_sorad_pass_oc<R>, dim3(band_grid(nc, SO_NPASS)), blk, 0, st, A, (const SoradDev<R> *)d_O);
+            } else if (col_path) {   // one block per column, lanes = (pass slot, level) (whole wavefronts), all 35 passes on chip
                 const unsigned nthr = (unsigned)sorad_col_threads(np);
                 const unsigned grid = 8u * (unsigned)((nc + 7) / 8);
                 hipLaunchKernelGGL(k_sorad_col<R>, dim3(grid), dim3(nthr), so_lds, st, A, (const SoradDev<R> *)d_O, O);
@@ -2857,6 +2871,15 @@ int geosrad_set_chunk(geosrad_ctx *c, int n)
     return GEOSRAD_OK;
 }
 size_t geosrad_workspace_bytes(const geosrad_ctx *c) { return c ? c->workspace_bytes() : 0; }
+int geosrad_set_overcast(geosrad_ctx *c, int flags)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    if (flags & ~(GEOSRAD_OVERCAST_IRRAD | GEOSRAD_OVERCAST_SORAD)) return c->fail(GEOSRAD_EINVAL, "unknown geosrad_set_overcast flag bits");
+    if (auto *m = dynamic_cast<MultiCtx *>(c)) for (auto *k : m->kid) k->overcast = flags;
+    c->overcast = flags;
+    return GEOSRAD_OK;
+}
+int geosrad_get_overcast(const geosrad_ctx *c) { return c ? c->overcast : 0; }
 
 int geosrad_set_tables_lw(geosrad_ctx *c, const void *blob, size_t n) { return c ? c->set_tables_lw(blob, n) : GEOSRAD_EINVAL; }
 
@@ -3279,7 +3302,7 @@ const char *geosrad_kernel_label(geosrad_ctx *c, int kernel_id)
     case 4: return c->lw_cols_path ? "k_lw_cols" : (c->lw_split_path ? "k_lw_cells+k_lw_sweep" : "k_lw_bands");
     case 8: return c->sw_path == 2 ? "k_sw_reform" : "k_sw_bands";
     case 9: return c->sw_path == 2 ? "k_swr_reduce" : "k_sw_reduce";
-    case 13: return c->sorad_col_path ? "k_sorad_col" : "k_sorad_pass";
+    case 13: return (c->overcast & GEOSRAD_OVERCAST_SORAD) ? "k_sorad_pass_oc" : (c->sorad_col_path ? "k_sorad_col" : "k_sorad_pass");
     default: return geosrad_kernel_name(kernel_id);
     }
 }

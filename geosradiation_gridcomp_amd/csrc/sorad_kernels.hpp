@@ -1,7 +1,8 @@
 // sorad_kernels.hpp -- hand-written HIP kernels (gfx950 / CDNA4) for the Chou-Suarez shortwave scheme `sorad`.
 //
 // Reference behaviour: GEOSsolar_GridComp/sorad.F90:43-1588 (SOLUV / SOLIR / CLDFLX inlined, O2 + CO2 flux reductions),
-// deledd :1592-1706; cloud optics GEOS_RadiationShared/getvistau.code, getnirtau.code.  Non-OVERCAST build.
+// deledd :1592-1706; cloud optics GEOS_RadiationShared/getvistau.code, getnirtau.code.  Both builds of the reference: the default one
+// (CLDFLX over up to 8 sky situations, below) and -DOVERCAST (k_sorad_ident, k_sorad_cloud<R, true>, k_sorad_pass_oc: see there).
 //
 // sorad is 35 independent spectral passes (5 UV/PAR bands + 3 NIR bands x 10 k-values), each a set of delta-Eddington layers (no
 // vertical dependence, fp64, the expensive part) + first-order vertical recurrences (adding over up to 8 sky situations):
@@ -218,15 +219,18 @@ __global__ void __launch_bounds__(256) k_sorad_prep(SoradArgs<R> A)
 // radii are read once (through the permutation) for the four optics groups; layers of cloud groups the column's class lacks are skipped
 // (no pass reads their planes)
 // ---------------------------------------------------------------------------------------------------
-template <typename R>
+// OC (-DOVERCAST: getvistau / getnirtau called with ict = icb = 0, sorad.F90:421, 955): every layer of every column, the optical
+// thickness NOT scaled (getvistau.code:7, 173-182) - a layer's condensate counts in full even where fcld <= 0.01; fcld only decides
+// whether the layer gets its own asymmetry factor / single-scattering albedo
+template <typename R, bool OC = false>
 __global__ void __launch_bounds__(256) k_sorad_cloud(SoradArgs<R> A, const SoradDev<R> *__restrict__ Tp)
 {
     const int pos = blockIdx.x * blockDim.x + threadIdx.x;
     const int k = (int)blockIdx.y + 1;
     if (pos >= A.m) return;
-    if (pos < A.cls_off[1]) return;          // class 0: no cloud group holds cloud, no pass reads the cloud planes
+    if (!OC && pos < A.cls_off[1]) return;   // class 0: no cloud group holds cloud, no pass reads the cloud planes
     const int i = A.perm[pos];
-    {
+    if (!OC) {
         const int c = A.cls[i];
         if (!(k < A.ict ? (c & 4) : (k < A.icb ? (c & 2) : (c & 1)))) return;
     }
@@ -265,7 +269,9 @@ __global__ void __launch_bounds__(256) k_sorad_cloud(SoradArgs<R> A, const Sorad
         const int kk = k < ict ? 1 : (k < icb ? 2 : 3);
         R tauc = tc1 + tc2 + tc3 + tc4;
         const bool cloudy = tauc > (R)0.02 && fc > (R)0.01;
-        if (cloudy) {
+        if (OC) {
+            tb = tc1 + tc2 + tc3 + tc4; tf = tb;
+        } else if (cloudy) {
             R fa = ib == 0 ? fc / cc[kk] : (cc[kk] != 0 ? fc / cc[kk] : (R)0);
             R tcap = tauc < (R)32. ? tauc : (R)32.;
             R fm = cosz / dm, ft = (gr_log10<R>(tcap) - t1) / dt;
@@ -605,6 +611,134 @@ __global__ void __launch_bounds__(256) k_sorad_pass(SoradArgs<R> A, const SoradD
     A.psum[((size_t)pass * 3 + 0) * m + i] = fsdir;
     A.psum[((size_t)pass * 3 + 1) * m + i] = fsdif;
     A.psum[((size_t)pass * 3 + 2) * m + i] = fall_sfc;      // all-sky net flux at the surface
+#undef RRAV
+#undef RXAV
+#undef P
+#undef LY
+}
+
+// ---------------------------------------------------------------------------------------------------
+// -DOVERCAST (sorad.F90:82-88): a layer is either clear or fully cloudy, so a column has ONE class and two sky situations - every layer's
+// clear portion (ih = 1) and every layer's cloudy portion (ih = 2).  k_sorad_ident replaces k_sorad_class + k_partition8 (identity
+// permutation, every position class 7 so that k_sorad_sum takes all four flux planes), k_sorad_cloud<R, true> the scaled cloud optics,
+// k_sorad_pass_oc the k_sorad_pass instantiations.  The aerosols are read from the caller's arrays (positions are columns: no gather).
+// ---------------------------------------------------------------------------------------------------
+template <typename R>
+__global__ void __launch_bounds__(256) k_sorad_ident(SoradArgs<R> A)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= 8) A.cls_off[i] = i < 8 ? 0 : A.m;
+    if (i >= A.m) return;
+    A.perm[i] = i; A.cls[i] = 7;
+}
+
+// k_sorad_pass_oc: one thread per (column, spectral pass), the "Inline CLDFLXY" blocks (UV/PAR :556-690, NIR :1086-1210): per sky situation
+// one adding chain up from the surface (rra, rxa, parked in planes 10 + 2 v, 11 + 2 v) and one down from the top (tda, tta, rsa in
+// registers); ih = 1 gives fclr / fupc, ih = 2 fall / fupa and the surface fsdir / fsdif - no weights.  The layers' properties (:480-551,
+// 1004-1068) as in k_sorad_pass, the cloudy portion formed at every layer (with the cloud's unscaled optical thickness, 0 where it has no
+// condensate).  Every step down is written tda * rsa * rr, as the reference's CLDFLXY writes it at every level (CLDFLX: tda * rr * rsa in
+// the low group), so the clear-sky fluxes agree with the default build's to rounding, not bit for bit.
+template <typename R>
+__global__ void __launch_bounds__(256) k_sorad_pass_oc(SoradArgs<R> A, const SoradDev<R> *__restrict__ Tp)
+{
+    int bstart, pass;
+    if (!band_block(A.m, SO_NPASS, bstart, pass)) return;
+    const int i = bstart + (int)threadIdx.x;                                            // position == column (k_sorad_ident)
+    if (i >= A.m) return;
+    const SoradDev<R> &T = *Tp;
+    const int np = A.np, m = A.m, K2 = np + 2;
+    const bool uv = pass < 5;
+    const int ib = uv ? pass + 1 : (pass - 5) / 10 + 1, ik = uv ? 0 : (pass - 5) % 10 + 1;   // band in its region, k-value
+    const int iv = uv ? ib : ib + 5;                                                         // aerosol band 1..8
+    const int grp = uv ? 0 : ib;
+    const R cz = A.cosz[i], dsm = (R)0.602;
+    const R wvtoa = A.colv[3 * (size_t)m + i], o3toa = A.colv[4 * (size_t)m + i];
+    R *S = A.scr + (size_t)pass * SO_NPLANE * K2 * m + i;
+    using L5 = SoL5<R>;
+#define P(q, k) S[((size_t)(q) * K2 + (k)) * m]
+#define LY(f, j, k) P(2 * (f) + (j) - 1, k)              // f: 0 rr 1 tt 2 td 3 rs 4 ts;  j: 1 clear, 2 cloudy
+#define RRAV(k, v) P(10 + 2 * (v), k)
+#define RXAV(k, v) P(11 + 2 * (v), k)
+    auto ld5 = [&](int j, int k) { L5 l; l.rr = LY(0, j, k); l.tt = LY(1, j, k); l.td = LY(2, j, k); l.rs = LY(3, j, k); l.ts = LY(4, j, k); return l; };
+    auto st5 = [&](int j, int k, const L5 &l) { LY(0, j, k) = l.rr; LY(1, j, k) = l.tt; LY(2, j, k) = l.td; LY(3, j, k) = l.rs; LY(4, j, k) = l.ts; };
+    const R rb = uv ? A.rsuvbm[i] : A.rsirbm[i], rd = uv ? A.rsuvdf[i] : A.rsirdf[i];
+    const R td0 = uv ? gr_exp<R>(-(wvtoa * T.wk_uv[ib - 1] + o3toa * T.zk_uv[ib - 1]) / cz) : gr_exp<R>(-wvtoa * T.xk_ir[ik - 1] / cz);
+    const R k_ry = uv ? T.ry_uv[ib - 1] : T.ry_ir[ib - 1], k_zk = uv ? T.zk_uv[ib - 1] : (R)0, k_wk = uv ? T.wk_uv[ib - 1] : T.xk_ir[ik - 1];
+    const R *a0 = A.taua + ((size_t)(iv - 1) * np) * A.ld + i, *a1 = A.ssaa + ((size_t)(iv - 1) * np) * A.ld + i,
+            *a2 = A.asya + ((size_t)(iv - 1) * np) * A.ld + i;
+    // ---- sweep U: the layers' clear (1) and cloudy (2) portions, parked for sweep D; composites from the surface --------------------
+    {
+        R rra[2] = {rb, rb}, rxa[2] = {rd, rd};
+        RRAV(np + 1, 0) = rb; RXAV(np + 1, 0) = rd; RRAV(np + 1, 1) = rb; RXAV(np + 1, 1) = rd;
+        for (int k = np; k >= 1; k--) {
+            const R dp = A.lay[((size_t)0 * K2 + k) * m + i], wh = A.lay[((size_t)1 * K2 + k) * m + i], oh = A.lay[((size_t)2 * K2 + k) * m + i];
+            const size_t ja = (size_t)(k - 1) * A.ld;
+            const R ta_ = a0[ja], sa_ = a1[ja], as_ = a2[ja];
+            const R tcb = A.cld[(((size_t)grp * 4 + 0) * K2 + k) * m + i], tcf = A.cld[(((size_t)grp * 4 + 1) * K2 + k) * m + i];
+            const R asyc = A.cld[(((size_t)grp * 4 + 2) * K2 + k) * m + i];
+            const R ssac = uv ? (R)1 : A.cld[(((size_t)grp * 4 + 3) * K2 + k) * m + i];
+            const R taurs = k_ry * dp;
+            const R tausto = uv ? taurs + k_zk * oh + k_wk * wh + ta_ + (R)1.0e-7 : taurs + k_wk * wh + ta_ + (R)1.0e-7;
+            const R ssatau = uv ? sa_ + taurs : sa_ + taurs + (R)1.0e-8;
+            const R asysto = as_;
+            L5 l1, l2;
+            R dum;
+            {
+                R ssatob = so_div(ssatau, tausto) + (R)1.0e-8;
+                ssatob = ssatob < (R)0.999999 ? ssatob : (R)0.999999;
+                const R asytob = so_div(asysto, ssatau);
+                so_deledd<R>(tausto, ssatob, asytob, cz, l1.rr, l1.tt, l1.td);
+                so_deledd<R>(tausto, ssatob, asytob, dsm, l1.rs, l1.ts, dum);
+            }
+            {
+                const R tautob = tausto + tcb;
+                R ssatob = so_div(uv ? (ssatau + tcb) : (ssatau + ssac * tcb), tautob) + (R)1.0e-8;
+                ssatob = ssatob < (R)0.999999 ? ssatob : (R)0.999999;
+                const R asytob = so_div(uv ? (asysto + asyc * tcb) : (asysto + asyc * ssac * tcb), ssatob * tautob);
+                const R tautof = tausto + tcf;
+                R ssatof = so_div(uv ? (ssatau + tcf) : (ssatau + ssac * tcf), tautof) + (R)1.0e-8;
+                ssatof = ssatof < (R)0.999999 ? ssatof : (R)0.999999;
+                const R asytof = so_div(uv ? (asysto + asyc * tcf) : (asysto + asyc * ssac * tcf), ssatof * tautof);
+                so_deledd<R>(tautob, ssatob, asytob, cz, l2.rr, l2.tt, l2.td);
+                so_deledd<R>(tautof, ssatof, asytof, dsm, l2.rs, l2.ts, dum);
+            }
+            st5(1, k, l1); st5(2, k, l2);
+            so_add_up<R>(l1, rra[0], rxa[0]);
+            so_add_up<R>(l2, rra[1], rxa[1]);
+            RRAV(k, 0) = rra[0]; RXAV(k, 0) = rxa[0]; RRAV(k, 1) = rra[1]; RXAV(k, 1) = rxa[1];
+        }
+    }
+    // ---- sweep D: composites from the top (the layer above the model top: td0, tt = 1, rs = 0), fluxes of both situations ------------
+    R fsdir = 0, fsdif = 0, fall_sfc = 0;
+    {
+        R tda[2] = {td0, td0}, tta[2] = {1, 1}, rsa[2] = {0, 0};
+        for (int k = 1; k <= np + 1; k++) {
+            L5 l[2] = {};
+            if (k <= np) { l[0] = ld5(1, k); l[1] = ld5(2, k); }
+            const R bra[2] = {RRAV(k, 0), RRAV(k, 1)}, bxa[2] = {RXAV(k, 0), RXAV(k, 1)};
+#pragma unroll
+            for (int v = 0; v < 2; v++) {
+                const R denm = so_div((R)1., (R)1. - rsa[v] * bxa[v]);
+                const R fdndir = tda[v];
+                const R xx4 = tda[v] * bra[v], yy = tta[v] - tda[v];
+                const R fdndif = (xx4 * rsa[v] + yy) * denm;
+                const R fupdif = (xx4 + yy * bxa[v]) * denm;
+                const R flxdn = fdndir + fdndif - fupdif;
+                if (v == 0) { P(27, k) = flxdn; P(29, k) = fupdif; }                       // fclr, fupc
+                else {
+                    P(26, k) = flxdn; P(28, k) = fupdif;                                   // fall, fupa
+                    if (k == np + 1) { fsdir = fdndir; fsdif = fdndif; fall_sfc = flxdn; }
+                }
+            }
+            if (k <= np) {
+#pragma unroll
+                for (int v = 0; v < 2; v++) so_add_down<R, false>(l[v], tda[v], tta[v], rsa[v]);
+            }
+        }
+    }
+    A.psum[((size_t)pass * 3 + 0) * m + i] = fsdir;
+    A.psum[((size_t)pass * 3 + 1) * m + i] = fsdif;
+    A.psum[((size_t)pass * 3 + 2) * m + i] = fall_sfc;
 #undef RRAV
 #undef RXAV
 #undef P

@@ -7,6 +7,8 @@
 !   soradmod : sorad      GEOSsolar_GridComp/sorad.F90:43-51
 ! The coefficient tables (the reference keeps them as module data in irrad_constants / sorad_constants / rad_constants) are
 ! uploaded to HBM on the first call.
+! Cloud mode: compiled with -DOVERCAST (as GEOS compiles irrad.F90 / sorad.F90 for it, irrad.F90:140-144, sorad.F90:82-88) each module
+! sets its own scheme's flag of geosrad_set_overcast before every call, otherwise it clears it; the other scheme's flag is left alone.
 module irradmod
    use iso_c_binding
    use geosrad_c
@@ -46,6 +48,12 @@ contains
          if (rc /= 0) call geosrad_fail('irrad (tables)')
          loaded = .true.
       end if
+      rc = geosrad_get_overcast(geosrad_ctx_handle())
+#ifdef OVERCAST
+      rc = geosrad_set_overcast(geosrad_ctx_handle(), ior(rc, GEOSRAD_OVERCAST_IRRAD))
+#else
+      rc = geosrad_set_overcast(geosrad_ctx_handle(), iand(rc, not(GEOSRAD_OVERCAST_IRRAD)))
+#endif
       rc = geosrad_irrad(geosrad_ctx_handle(), int(m,c_int), int(np,c_int), c_loc(ple), c_loc(ta), c_loc(wa), c_loc(oa), c_loc(tb), &
          real(co2,c_double), merge(1_c_int, 0_c_int, trace), c_loc(n2o), c_loc(ch4), c_loc(cfc11), c_loc(cfc12), c_loc(cfc22), &
          c_loc(cwc), c_loc(fcld), int(ict,c_int), int(icb,c_int), c_loc(reff), int(ns,c_int), c_loc(fs), c_loc(tg), c_loc(eg), &
@@ -103,6 +111,12 @@ contains
          allocate(dr(m,nband), df(m,nband))
          pdr = c_loc(dr); pdf = c_loc(df)
       end if
+      rc = geosrad_get_overcast(geosrad_ctx_handle())
+#ifdef OVERCAST
+      rc = geosrad_set_overcast(geosrad_ctx_handle(), ior(rc, GEOSRAD_OVERCAST_SORAD))
+#else
+      rc = geosrad_set_overcast(geosrad_ctx_handle(), iand(rc, not(GEOSRAD_OVERCAST_SORAD)))
+#endif
       rc = geosrad_sorad(geosrad_ctx_handle(), int(m,c_int), int(np,c_int), int(nb,c_int), c_loc(cosz), c_loc(pl), c_loc(ta), c_loc(wa), &
          c_loc(oa), real(co2,c_double), c_loc(cwc), c_loc(fcld), int(ict,c_int), int(icb,c_int), c_loc(reff), c_loc(hk_uv), c_loc(hk_ir), &
          c_loc(taua), c_loc(ssaa), c_loc(asya), c_loc(rsuvbm), c_loc(rsuvdf), c_loc(rsirbm), c_loc(rsirdf), c_loc(flx), c_loc(flc), &

@@ -8,6 +8,9 @@ module geosrad_c
    public :: geosrad_ctx_handle, geosrad_fail, geosrad_warn, geosrad_data_path, geosrad_load_tables_sw, geosrad_rrtmg_sw, geosrad_load_tables_chou_lw, geosrad_load_tables_chou_sw, geosrad_irrad, geosrad_sorad
    public :: geosrad_create, geosrad_destroy, geosrad_last_error, geosrad_load_tables_lw, geosrad_load_inhomogeneity
    public :: geosrad_set_corr_lengths, geosrad_rrtmg_lw, geosrad_mcica, geosrad_clearcounts, geosrad_read_table
+   public :: geosrad_set_overcast, geosrad_get_overcast, GEOSRAD_OVERCAST_IRRAD, GEOSRAD_OVERCAST_SORAD
+
+   integer(c_int), parameter :: GEOSRAD_OVERCAST_IRRAD = 1, GEOSRAD_OVERCAST_SORAD = 2     ! geosrad_set_overcast flags
 
    type(c_ptr), save :: ctx = c_null_ptr
 
@@ -108,6 +111,15 @@ module geosrad_c
          type(c_ptr), value :: ctx
          integer(c_int), value :: ncol, nsubcol, nlay, cloudLM, cloudMH
          type(c_ptr), value :: cldy, cnt
+      end function
+      integer(c_int) function geosrad_set_overcast(ctx, flags) bind(C, name='geosrad_set_overcast')
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: flags
+      end function
+      integer(c_int) function geosrad_get_overcast(ctx) bind(C, name='geosrad_get_overcast')
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
       end function
    end interface
 

@@ -78,6 +78,13 @@ int geosrad_real_kind(const geosrad_ctx *ctx);
 int geosrad_set_chunk(geosrad_ctx *ctx, int max_columns);
 /* bytes of HBM workspace currently held */
 size_t geosrad_workspace_bytes(const geosrad_ctx *ctx);
+/* Chou-Suarez cloud mode: the reference's -DOVERCAST build of irrad.F90 / sorad.F90 (a layer is clear or fully cloudy; random overlap of
+ * the cloudy layers; sorad's cloud optical thickness not scaled; ict / icb not read).  One flag per scheme (GEOS compiles them in separate
+ * components); 0 (the default) = maximum-random overlap.  Applies to geosrad_irrad[_dev], geosrad_sorad[_dev] and
+ * geosrad_sw_driver_chou_dev, on every device of a multi-device context.  Unknown bits: GEOSRAD_EINVAL, the mode unchanged. */
+enum { GEOSRAD_OVERCAST_IRRAD = 1, GEOSRAD_OVERCAST_SORAD = 2 };
+int geosrad_set_overcast(geosrad_ctx *ctx, int flags);
+int geosrad_get_overcast(const geosrad_ctx *ctx);
 
 /* ---- tables ("GRTB" blobs, geosradiation_gridcomp_amd/data/) ------------------------------------- */
 /* what rrtmg_lw_ini leaves in rrlw_kgNN/rrlw_tbl/rrlw_wvn/rrlw_ref/rrlw_cld (rrtmg_lw_init.F90:22-165) */
@@ -237,7 +244,8 @@ int geosrad_rrtmg_sw_cldprmc(geosrad_ctx *ctx, int ncol, int nlay, const void *p
  * (k = 1 top layer), ple in Pa; Fortran layouts: ple (m,np+1); ta, wa, oa, n2o, ch4, cfc11, cfc12, cfc22, fcld (m,np); tb (m);
  * cwc, reff (m,np,4); fs, tg, tv (m,ns); eg, ev, rv (m,ns,10); taua, ssaa, asya (m,np,nb) are IN-OUT and rescaled in place
  * exactly like the reference does (irrad.F90:655-678; may be NULL when na == 0); outputs flxu ... flxad, dfdts (m,np+1),
- * sfcem (m), taudiag (m,np,10).  Upward fluxes are negative.  Non-OVERCAST behaviour (maximum-random overlap).
+ * sfcem (m), taudiag (m,np,10).  Upward fluxes are negative.  Maximum-random overlap, or the -DOVERCAST behaviour under
+ * GEOSRAD_OVERCAST_IRRAD (geosrad_set_overcast; ict / icb are then not read).
  * trace == 0: band 10 is skipped for every column (the reference `return`s out of its column loop there, irrad.F90:478;
  * GEOS always passes trace = .true.). */
 int geosrad_irrad(geosrad_ctx *ctx, int m, int np, const void *ple, const void *ta, const void *wa, const void *oa, const void *tb,
@@ -260,7 +268,8 @@ int geosrad_irrad_dev(geosrad_ctx *ctx, void *stream, int m, int np, const void 
  * cosz, rsuvbm, rsuvdf, rsirbm, rsirdf (m); pl (m,np+1); ta, wa, oa, fcld (m,np); cwc, reff (m,np,4); taua, ssaa, asya
  * (m,np,nb = 8) in the (tau, tau*ssa, tau*ssa*g) form the reference expects; hk_uv (5), hk_ir (3,10): HOST pointers in both
  * variants; outputs flx, flc, flxu, flcu (m,np+1), fdir/fdif uv/par/ir (m), flx_sfc_band (m,8), drband, dfband (m,8; written
- * only when do_drfband != 0, else may be NULL).  Fluxes are fractions of the TOA insolation.  Non-OVERCAST behaviour. */
+ * only when do_drfband != 0, else may be NULL).  Fluxes are fractions of the TOA insolation.  Maximum-random overlap, or the -DOVERCAST
+ * behaviour under GEOSRAD_OVERCAST_SORAD (geosrad_set_overcast; ict / icb are then not read). */
 int geosrad_sorad(geosrad_ctx *ctx, int m, int np, int nb, const void *cosz, const void *pl, const void *ta, const void *wa,
                   const void *oa, double co2, const void *cwc, const void *fcld, int ict, int icb, const void *reff,
                   const void *hk_uv, const void *hk_ir, const void *taua, const void *ssaa, const void *asya,

@@ -1,0 +1,55 @@
+/* chou_overcast_ref.c -- TEST INFRASTRUCTURE: the -DOVERCAST Chou-Suarez drivers (chou_overcast_impl.h) on top of the oracle's helpers,
+ * both precisions: oc_irrad_f32 / _f64, oc_sorad_f32 / _f64, with the oracle's own entry points and table setters alongside.  Built by
+ * tests/test_chou_overcast.py into pytest's temporary directory with the compiler and flags of oracle/Makefile's liboracle.so. */
+#include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#define REAL float
+#define SFX(x) x##_f32
+#define EXP expf
+#define LOG logf
+#define POW powf
+#define FMOD fmodf
+#define FABS fabsf
+#define SQRT sqrtf
+#define LOG10 log10f
+#define FLOOR floorf
+#include "../oracle/lw_oracle_impl.h"
+#include "../oracle/sw_oracle_impl.h"
+#include "../oracle/chou_oracle_impl.h"
+#include "../oracle/chou_sw_oracle_impl.h"
+#include "../oracle/gridcomp_oracle_impl.h"
+#include "chou_overcast_impl.h"
+#undef LOG10
+#undef FLOOR
+#undef NSOLFRAC
+#undef REAL
+#undef SFX
+#undef EXP
+#undef LOG
+#undef POW
+#undef FMOD
+#undef FABS
+#undef SQRT
+#undef F2
+#undef F3
+
+#define REAL double
+#define SFX(x) x##_f64
+#define EXP exp
+#define LOG log
+#define POW pow
+#define FMOD fmod
+#define FABS fabs
+#define SQRT sqrt
+#define LOG10 log10
+#define FLOOR floor
+#include "../oracle/lw_oracle_impl.h"
+#include "../oracle/sw_oracle_impl.h"
+#include "../oracle/chou_oracle_impl.h"
+#include "../oracle/chou_sw_oracle_impl.h"
+#include "../oracle/gridcomp_oracle_impl.h"
+#include "chou_overcast_impl.h"
+#undef LOG10
