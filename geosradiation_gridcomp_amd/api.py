@@ -458,6 +458,17 @@ class Context:
         self._chk(self.L.geosrad_sw_update_surface_dev(self.h, ctypes.c_void_p(stream), ci(ncol), ci(lm), ctypes.c_double(undef),
                                                         self._ptr_array(G.SWS_IN, ptr), self._ptr_array(G.SWS_OUT, ptr)))
 
+    def sw_update_clouds_dev(self, stream, ncol, lm, lcldmh, lcldlm, taucrit, ptr, consts=None):
+        """cloud diagnostics of UPDATE_EXPORT (GEOS_SolarGridComp.F90:7006-7058, :7223-7392): `ptr` name -> device address for
+        gridcomp.SWK_IN / SWK_OUT (missing = not associated); lcldmh / lcldlm in model ordering; taucrit = the TAUCRIT: resource (0.10);
+        consts in gridcomp.SWK_CONST order (default gridcomp.swk_consts())."""
+        from . import gridcomp as G
+        ci = ctypes.c_int
+        cs = (ctypes.c_double * len(G.SWK_CONST))(*(G.swk_consts() if consts is None else consts))
+        self._chk(self.L.geosrad_sw_update_clouds_dev(self.h, ctypes.c_void_p(stream), ci(ncol), ci(lm), ci(int(lcldmh)), ci(int(lcldlm)),
+                                                       ctypes.c_double(taucrit), cs, self._ptr_array(G.SWK_IN, ptr),
+                                                       self._ptr_array(G.SWK_OUT, ptr)))
+
     def sw_driver_rrtmg_dev(self, stream, ncol, lm, nb_aer, ptr, consts, iceflg, liqflg, sc, dist, isolvar, dyofyr, include_aerosols,
                             lcldlm, lcldmh, normflx=1, bndsolvar=None, indsolvar=None):
         """RRTMG branch of SORADCORE on the packed daytime columns (GEOS_SolarGridComp.F90:6113-6450)."""

@@ -608,6 +608,8 @@ struct geosrad_ctx {
                                     void *tbrb_exp) = 0;
     virtual int sw_update_export_dev(hipStream_t st, int ncol, int lm, int nbands, const void *const *in, void *const *out) = 0;
     virtual int sw_update_surface_dev(hipStream_t st, int ncol, int lm, double undef, const void *const *in, void *const *out) = 0;
+    virtual int sw_update_clouds_dev(hipStream_t st, int ncol, int lm, int lcldmh, int lcldlm, double taucrit, const double *consts,
+                                     const void *const *in, void *const *out) = 0;
     virtual int rad_tendencies_dev(hipStream_t st, int ncol, int lm, double grav, double cp, const void *const *in,
                                    void *const *out) = 0;
     virtual int sw_host(int ncol, int nlay, double scon, double adjes, int isolvar, const void *const *in, int iceflg, int liqflg,
@@ -1550,6 +1552,35 @@ template <typename R> struct Ctx : geosrad_ctx {
         U.slrsf = O(GEOSRAD_SWS_SLRSF); U.slrsfc = O(GEOSRAD_SWS_SLRSFC); U.slrsfna = O(GEOSRAD_SWS_SLRSFNA); U.slrsfcna = O(GEOSRAD_SWS_SLRSFCNA);
         U.slrsuf = O(GEOSRAD_SWS_SLRSUF); U.slrsufc = O(GEOSRAD_SWS_SLRSUFC); U.slrsufna = O(GEOSRAD_SWS_SLRSUFNA); U.slrsufcna = O(GEOSRAD_SWS_SLRSUFCNA);
         hipLaunchKernelGGL((k_sw_update_surface<R>), dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, st, U);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+
+    int sw_update_clouds_dev(hipStream_t st, int ncol, int lm, int lcldmh, int lcldlm, double taucrit, const double *consts,
+                             const void *const *in, void *const *out) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (ncol <= 0 || lm <= 0) return fail(GEOSRAD_EINVAL, "bad ncol/lm");
+        if (!(1 < lcldmh && lcldmh < lcldlm && lcldlm <= lm)) return fail(GEOSRAD_EINVAL, "super-layer levels must satisfy 1 < lcldmh < lcldlm <= lm");
+        if (!consts) return fail(GEOSRAD_EINVAL, "consts null");
+        if (!have_sorad) return fail(GEOSRAD_EINVAL, "Chou-Suarez SW tables not set: call geosrad_load_tables_chou_sw first");
+        bool any = false, optics = false;          // optics: an export GETVISTAU's optical thickness feeds
+        for (int k = 0; k < GEOSRAD_SWK_NOUT; k++) {
+            any = any || out[k];
+            optics = optics || (out[k] && ((k >= GEOSRAD_SWK_TAUCLI && k <= GEOSRAD_SWK_TAUCLS) || k >= GEOSRAD_SWK_TAULO));
+        }
+        if (any && !in[GEOSRAD_SWK_FCLD]) return fail(GEOSRAD_EINVAL, "FCLD is required");
+        for (int k = GEOSRAD_SWK_QI; k <= GEOSRAD_SWK_RS; k++)
+            if (optics && !in[k]) return fail(GEOSRAD_EINVAL, "an optical-thickness export was requested without QI..QS / RI..RS");
+        if (optics && !in[GEOSRAD_SWK_PLE]) return fail(GEOSRAD_EINVAL, "an optical-thickness export was requested without PLE");
+        if (out[GEOSRAD_SWK_CLDTMP] && !in[GEOSRAD_SWK_T]) return fail(GEOSRAD_EINVAL, "CLDTMP requested without T");
+        if (!any) return GEOSRAD_OK;
+        SwCld<R> U{};
+        U.ncol = ncol; U.lm = lm; U.ict = lcldmh; U.icb = lcldlm; U.optics = optics;
+        U.grav = (R)consts[GEOSRAD_SWK_C_GRAV]; U.undef = (R)consts[GEOSRAD_SWK_C_UNDEF]; U.taucrit = (R)taucrit;
+        for (int k = 0; k < GEOSRAD_SWK_NIN; k++) U.in[k] = (const R *)in[k];
+        for (int k = 0; k < GEOSRAD_SWK_NOUT; k++) U.out[k] = (R *)out[k];
+        hipLaunchKernelGGL((k_sw_update_clouds<R>), dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, st, U, (const SoradDev<R> *)d_O);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -2779,6 +2810,7 @@ struct MultiCtx final : geosrad_ctx {
                             const void *, void *, void *) override { return nodev("geosrad_lw_update_bands_dev"); }
     int sw_update_export_dev(hipStream_t, int, int, int, const void *const *, void *const *) override { return nodev("geosrad_sw_update_export_dev"); }
     int sw_update_surface_dev(hipStream_t, int, int, double, const void *const *, void *const *) override { return nodev("geosrad_sw_update_surface_dev"); }
+    int sw_update_clouds_dev(hipStream_t, int, int, int, int, double, const double *, const void *const *, void *const *) override { return nodev("geosrad_sw_update_clouds_dev"); }
     int rad_tendencies_dev(hipStream_t, int, int, double, double, const void *const *, void *const *) override { return nodev("geosrad_rad_tendencies_dev"); }
     int lit_index_dev(hipStream_t, int, const void *, int32_t *, int32_t *, int32_t *, int *) override { return nodev("geosrad_lit_index_dev"); }
     int lit_pack_dev(hipStream_t, int, int, int, const int32_t *, const int32_t *, const void *, void *) override { return nodev("geosrad_lit_pack_dev"); }
@@ -3243,6 +3275,13 @@ int geosrad_sw_update_surface_dev(geosrad_ctx *c, void *stream, int ncol, int lm
 {
     if (!c || !in || !out) return GEOSRAD_EINVAL;
     return c->sw_update_surface_dev((hipStream_t)stream, ncol, lm, undef, in, out);
+}
+
+int geosrad_sw_update_clouds_dev(geosrad_ctx *c, void *stream, int ncol, int lm, int lcldmh, int lcldlm, double taucrit,
+                                 const double *consts, const void *const *in, void *const *out)
+{
+    if (!c || !in || !out) return GEOSRAD_EINVAL;
+    return c->sw_update_clouds_dev((hipStream_t)stream, ncol, lm, lcldmh, lcldlm, taucrit, consts, in, out);
 }
 
 int geosrad_rad_tendencies_dev(geosrad_ctx *c, void *stream, int ncol, int lm, double grav, double cp, const void *const *in,

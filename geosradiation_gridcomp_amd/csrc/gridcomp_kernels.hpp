@@ -14,7 +14,10 @@
 // blockIdx.y = level): all accesses are coalesced, nothing is transposed, the vertical flip is an index calculation.
 // A null output pointer = Fortran "not associated" (export not requested).
 #pragma once
+#include "../../include/geosrad.h"
 #include "lw_device.hpp"
+#include "chou_kernels.hpp"      // gr_log10
+#include "sorad_kernels.hpp"     // SoradDev: the Chou-Suarez SW tables (caif, aib_uv, awb_uv, arb_uv)
 
 namespace geosrad {
 
@@ -648,6 +651,133 @@ template <typename R> __global__ void __launch_bounds__(256) k_sw_update_surface
     if (U.slrsufc) U.slrsufc[ij] = def ? alb * (U.fscn[sfc] / ((R)1. - alb)) * slr : (R)0.0;
     if (U.slrsufna) U.slrsufna[ij] = def ? alb * (U.fswnan[sfc] / ((R)1. - alb)) * slr : (R)0.0;
     if (U.slrsufcna) U.slrsufcna[ij] = def ? alb * (U.fscnan[sfc] / ((R)1. - alb)) * slr : (R)0.0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// UPDATE_EXPORT, cloud diagnostics (SOL:7006-7058, :7223-7392): super-layer cloud fractions, GETVISTAU's diffuse optical thickness
+// per species (getvistau.code with ict = LCLDMH, icb = LCLDLM; its beam output and asymmetry factor are dummies here, :7270, so caib is
+// not read), super-layer sums, TAUTX, COT / COTNUM, cloud top.  One thread per column, two walks down the column: the maxima (which
+// GETVISTAU's cover normalisation needs for every layer), then the optics.  Each walk issues the loads of NB layers before it uses the
+// first of them.  NB = 2 (94 VGPRs in fp32, 136 in fp64) measured fastest; NB = 8 needs 256 VGPRs plus AGPRs, drops to one wavefront per
+// SIMD and is the slowest; a second wavefront per SIMD forced by WPS = 2 only spills it (profiles/r05_sw_clouds.md).
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int SWK_NB = 2, SWK_WPS = 1;
+template <typename R> struct SwCld {
+    int ncol, lm, ict, icb;          // ict = LCLDMH, icb = LCLDLM (model ordering, 1 = top)
+    int optics;                      // some requested export needs GETVISTAU
+    R grav, undef, taucrit;
+    const R *in[GEOSRAD_SWK_NIN];    // GEOSRAD_SWK_* order
+    R *out[GEOSRAD_SWK_NOUT];
+};
+template <typename R, int NB = SWK_NB, int WPS = SWK_WPS>
+__global__ void __launch_bounds__(256, WPS) k_sw_update_clouds(SwCld<R> U, const SoradDev<R> *__restrict__ Tp)
+{
+#pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
+    const int ij = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ij >= U.ncol) return;
+    const int n = U.ncol, lm = U.lm, ict = U.ict, icb = U.icb;
+    const R *__restrict__ fcld = U.in[GEOSRAD_SWK_FCLD];
+    R *const *O = U.out;
+    // aCLDH / aCLDM / aCLDL (SOL:7008-7050); also getvistau.code's cc(1:3), the same maxima
+    R ch = 0, cm = 0, cl = 0;
+    for (int k0 = 0; k0 < lm; k0 += NB) {
+        R f[NB];
+#pragma unroll
+        for (int j = 0; j < NB; j++) f[j] = k0 + j < lm ? fcld[(size_t)(k0 + j) * n + ij] : (R)0;
+#pragma unroll
+        for (int j = 0; j < NB; j++) {
+            const int k = k0 + j + 1;
+            if (k > lm) break;
+            if (O[GEOSRAD_SWK_FCLD_X]) O[GEOSRAD_SWK_FCLD_X][(size_t)(k - 1) * n + ij] = f[j];      // FCLD = CLIN (:7006)
+            if (k < ict) ch = ch > f[j] ? ch : f[j];
+            else if (k < icb) cm = cm > f[j] ? cm : f[j];
+            else cl = cl > f[j] ? cl : f[j];
+        }
+    }
+    const R ct = (R)1. - ((R)1 - ch) * ((R)1 - cm) * ((R)1 - cl);      // aCLDT (:7054)
+    const R c4[4] = {cl, cm, ch, ct};                                   // LO MD HI TT, the order of the exports
+    for (int s = 0; s < 4; s++) {
+        if (O[GEOSRAD_SWK_CLDLO + s]) O[GEOSRAD_SWK_CLDLO + s][ij] = c4[s];
+        if (O[GEOSRAD_SWK_COTDENLO + s]) O[GEOSRAD_SWK_COTDENLO + s][ij] = c4[s];
+    }
+    if (!U.optics) return;
+
+    const SoradDev<R> &T = *Tp;
+    const R dt = (R)0.30103, da = (R)0.1, t1 = (R)-0.9031;
+    const R grav = U.grav, taucrit = U.taucrit;
+    const R *__restrict__ ple = U.in[GEOSRAD_SWK_PLE];
+    const R *__restrict__ q[4] = {U.in[GEOSRAD_SWK_QI], U.in[GEOSRAD_SWK_QL], U.in[GEOSRAD_SWK_QR], U.in[GEOSRAD_SWK_QS]};
+    const R *__restrict__ r[4] = {U.in[GEOSRAD_SWK_RI], U.in[GEOSRAD_SWK_RL], U.in[GEOSRAD_SWK_RR], U.in[GEOSRAD_SWK_RS]};
+    // GETVISTAU's cosz (ZTH = max(ZTH,0.0), :6874) enters only its beam scaling (fm, caib), which no export reads: ZTH is not read.
+#define CAIF(a, b) T.caif[((b) - 1) * 9 + ((a) - 1)]
+    R th = 0, tm = 0, tl = 0;                 // aTAUH / aTAUM / aTAUL (:7293-7345), summed top down
+    int ktop = 0;                             // topmost layer with TAUCLD(:,:,L,1) > TAUCRIT (:7380-7388), 0 = none
+    R pup = ple[ij];                          // PLE(k-1)
+    for (int k0 = 0; k0 < lm; k0 += NB) {
+        R pl[NB], f[NB], h[4][NB], re[4][NB];
+#pragma unroll
+        for (int j = 0; j < NB; j++) {
+            const bool live = k0 + j < lm;
+            const size_t o = (size_t)(k0 + j) * n + ij;
+            pl[j] = live ? ple[o + n] : (R)0;
+            f[j] = live ? fcld[o] : (R)0;
+#pragma unroll
+            for (int s = 0; s < 4; s++) { h[s][j] = live ? q[s][o] : (R)0; re[s][j] = live ? r[s][o] : (R)0; }
+        }
+#pragma unroll
+        for (int j = 0; j < NB; j++) {
+            const int k = k0 + j + 1;
+            if (k > lm) break;
+            const size_t o = (size_t)(k - 1) * n + ij;
+            const R dp = pl[j] - pup;                                       // DP = PLL(:,:,1:LM)-PLL(:,:,0:LM-1) (:7238)
+            const R wp = (dp * (R)1.0e3) / grav;
+            const R r1 = re[0][j] * (R)1.e6, r2 = re[1][j] * (R)1.e6, r4 = re[3][j] * (R)1.e6;      // REFF = R? * 1.e6 (:7246-7249)
+            const R tc1 = r1 <= 0 ? (R)0 : (wp * h[0][j]) * T.aib_uv / r1;
+            const R tc2 = r2 <= 0 ? (R)0 : (wp * h[1][j]) * (T.awb_uv[0] + T.awb_uv[1] / r2);
+            const R tc3 = (wp * h[2][j]) * T.arb_uv[0];
+            const R rs = r4 < (R)112.0 ? r4 : (R)112.0;                      // reff_snow = min(reff(k,4),112.0)
+            const R tc4 = rs <= 0 ? (R)0 : (wp * h[3][j]) * T.aib_uv / rs;
+            R d1 = 0, d2 = 0, d3 = 0, d4 = 0;                                // taudiff(k,1:4)
+            const R tauc = tc1 + tc2 + tc3 + tc4;
+            if (tauc > (R)0.02 && f[j] > (R)0.01) {
+                const R cc = k < ict ? ch : (k < icb ? cm : cl);
+                R fa = f[j] / cc;
+                const R tcap = tauc < (R)32. ? tauc : (R)32.;
+                R ft = (gr_log10<R>(tcap) - t1) / dt;
+                fa = fa / da;
+                int it = (int)(ft + (R)1.5), ia = (int)(fa + (R)1.5);
+                it = it > 2 ? it : 2; ia = ia > 2 ? ia : 2;
+                it = it < 8 ? it : 8; ia = ia < 10 ? ia : 10;
+                ft = ft - (R)(it - 1); fa = fa - (R)(ia - 1);
+                const R f0 = CAIF(it, ia);
+                R xai = (-CAIF(it - 1, ia) * ((R)1. - ft) + CAIF(it + 1, ia) * ((R)1. + ft)) * ft * (R).5 + f0 * ((R)1. - ft * ft);
+                xai = xai + (-CAIF(it, ia - 1) * ((R)1. - fa) + CAIF(it, ia + 1) * ((R)1. + fa)) * fa * (R).5 + f0 * ((R)1. - fa * fa);
+                xai = xai - f0;
+                xai = xai > 0 ? xai : (R)0; xai = xai < 1 ? xai : (R)1;
+                d1 = tc1 * xai; d2 = tc2 * xai; d3 = tc3 * xai; d4 = tc4 * xai;
+            }
+            if (O[GEOSRAD_SWK_TAUCLI]) O[GEOSRAD_SWK_TAUCLI][o] = d1;
+            if (O[GEOSRAD_SWK_TAUCLW]) O[GEOSRAD_SWK_TAUCLW][o] = d2;
+            if (O[GEOSRAD_SWK_TAUCLR]) O[GEOSRAD_SWK_TAUCLR][o] = d3;
+            if (O[GEOSRAD_SWK_TAUCLS]) O[GEOSRAD_SWK_TAUCLS][o] = d4;
+            const R tot = d1 + d2 + d3 + d4;                                  // TAUCLD(:,:,:,1) = 1 + 2 + 3 + 4 (:7280)
+            if (k < ict) th = th + tot; else if (k < icb) tm = tm + tot; else tl = tl + tot;
+            if (ktop == 0 && tot > taucrit) ktop = k;
+            pup = pl[j];
+        }
+    }
+#undef CAIF
+    const R undef = U.undef;
+    const R tx = ct > (R)0. ? (tl * cl + tm * cm + th * ch) / ct : (R)0;       // aTAUT (:7361)
+    const R t4[4] = {tl, tm, th, th + tm + tl}, x4[4] = {tl, tm, th, tx};      // TAUT = aTAUH + aTAUM + aTAUL (:7352)
+    for (int s = 0; s < 4; s++) {
+        if (O[GEOSRAD_SWK_TAULO + s]) O[GEOSRAD_SWK_TAULO + s][ij] = t4[s];
+        if (O[GEOSRAD_SWK_COTLO + s]) O[GEOSRAD_SWK_COTLO + s][ij] = c4[s] > (R)0. ? x4[s] : undef;
+        if (O[GEOSRAD_SWK_COTNUMLO + s]) O[GEOSRAD_SWK_COTNUMLO + s][ij] = c4[s] * x4[s];
+    }
+    if (O[GEOSRAD_SWK_TAUTX]) O[GEOSRAD_SWK_TAUTX][ij] = tx;
+    if (O[GEOSRAD_SWK_CLDTMP]) O[GEOSRAD_SWK_CLDTMP][ij] = ktop ? U.in[GEOSRAD_SWK_T][(size_t)(ktop - 1) * n + ij] : undef;
+    if (O[GEOSRAD_SWK_CLDPRS]) O[GEOSRAD_SWK_CLDPRS][ij] = ktop ? ple[(size_t)(ktop - 1) * n + ij] : undef;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@ module geosrad_gridcomp
    use geosrad_c, only : geosrad_ctx_handle, geosrad_fail, geosrad_data_path, geosrad_load_tables_chou_sw
    implicit none
    private
-   public :: lw_driver_rrtmg, lw_driver_rrtmg_rats, lw_update_rats, lw_update_bands, sw_update_surface, sw_driver_rrtmg, sw_driver_chou, lw_chou_post, lw_update_flx, sw_update_export, rad_tendencies
+   public :: lw_driver_rrtmg, lw_driver_rrtmg_rats, lw_update_rats, lw_update_bands, sw_update_surface, sw_update_clouds, sw_driver_rrtmg, sw_driver_chou, lw_chou_post, lw_update_flx, sw_update_export, rad_tendencies
    public :: lit_index, lit_pack, lit_unpack
    public :: dev_alloc, dev_free, dev_put, dev_get, dev_sync
 
@@ -27,6 +27,14 @@ module geosrad_gridcomp
    integer, parameter, public :: SWS_ALBVF_X = 1, SWS_ALBVR_X = 2, SWS_ALBNF_X = 3, SWS_ALBNR_X = 4, SWS_ALBEDO = 5, SWS_SLRTP = 6, SWS_DRUVR = 7, &
       SWS_DFUVR = 8, SWS_DRPAR = 9, SWS_DFPAR = 10, SWS_DRNIR = 11, SWS_DFNIR = 12, SWS_DRNUVR = 13, SWS_DRNPAR = 14, SWS_DRNNIR = 15, SWS_SLRSF = 16, &
       SWS_SLRSFC = 17, SWS_SLRSFNA = 18, SWS_SLRSFCNA = 19, SWS_SLRSUF = 20, SWS_SLRSUFC = 21, SWS_SLRSUFNA = 22, SWS_SLRSUFCNA = 23, SWS_NOUT = 23
+   ! ---- GEOSRAD_SWK_* (cloud diagnostics of UPDATE_EXPORT) ----
+   integer, parameter, public :: SWK_FCLD = 1, SWK_PLE = 2, SWK_T = 3, SWK_QI = 4, SWK_QL = 5, SWK_QR = 6, SWK_QS = 7, SWK_RI = 8, SWK_RL = 9, &
+      SWK_RR = 10, SWK_RS = 11, SWK_ZTH = 12, SWK_NIN = 12
+   integer, parameter, public :: SWK_C_GRAV = 1, SWK_C_UNDEF = 2, SWK_NCONST = 2
+   integer, parameter, public :: SWK_FCLD_X = 1, SWK_TAUCLI = 2, SWK_TAUCLW = 3, SWK_TAUCLR = 4, SWK_TAUCLS = 5, SWK_CLDLO = 6, SWK_CLDMD = 7, &
+      SWK_CLDHI = 8, SWK_CLDTT = 9, SWK_COTDENLO = 10, SWK_COTDENMD = 11, SWK_COTDENHI = 12, SWK_COTDENTT = 13, SWK_TAULO = 14, SWK_TAUMD = 15, &
+      SWK_TAUHI = 16, SWK_TAUTT = 17, SWK_TAUTX = 18, SWK_COTLO = 19, SWK_COTMD = 20, SWK_COTHI = 21, SWK_COTTT = 22, SWK_COTNUMLO = 23, &
+      SWK_COTNUMMD = 24, SWK_COTNUMHI = 25, SWK_COTNUMTT = 26, SWK_CLDTMP = 27, SWK_CLDPRS = 28, SWK_NOUT = 28
    ! ---- GEOSRAD_LWR_* (RATS exports of Update_Flx) ----
    integer, parameter, public :: LWR_FLX_INT = 1, LWR_SFCEM_INT = 2, LWR_DFDTS = 3, LWR_FLX_RAT = 4, LWR_SFCEM_RAT = 5, LWR_DFDTS_RAT = 6, LWR_NIN = 6
    integer, parameter, public :: LWR_DOLR = 1, LWR_DLWS = 2, LWR_DFLNS = 3, LWR_DSFCEM = 4, LWR_NETTRAP = 5, LWR_COLTRAP = 6, LWR_FLX = 7, &
@@ -116,6 +124,15 @@ module geosrad_gridcomp
          type(c_ptr), value :: ctx, stream
          integer(c_int), value :: ncol, lm
          real(c_double), value :: undef
+         type(c_ptr), intent(in) :: fin(*), fout(*)
+      end function
+      integer(c_int) function geosrad_sw_update_clouds_dev(ctx, stream, ncol, lm, lcldmh, lcldlm, taucrit, consts, fin, fout) &
+            bind(C, name='geosrad_sw_update_clouds_dev')
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: ctx, stream
+         integer(c_int), value :: ncol, lm, lcldmh, lcldlm
+         real(c_double), value :: taucrit
+         real(c_double), intent(in) :: consts(*)
          type(c_ptr), intent(in) :: fin(*), fout(*)
       end function
       integer(c_int) function geosrad_sw_driver_rrtmg_dev(ctx, stream, ncol, lm, nb_aer, fin, consts, iceflgsw, liqflgsw, sc, dist, isolvar, &
@@ -315,6 +332,23 @@ contains
          call geosrad_fail('UPDATE_EXPORT (surface)')
    end subroutine
 
+   ! cloud diagnostics of UPDATE_EXPORT (GEOS_SolarGridComp.F90:7006-7058, :7223-7392): CLD??, COTDEN??, GETVISTAU's TAUCL?, TAU??,
+   ! TAUTX, COT??, COTNUM??, CLDTMP / CLDPRS on all columns.  taucrit = the TAUCRIT: resource; MAPL_GRAV = 9.80665, MAPL_UNDEF = 1.0e15
+   ! (MAPL_Constants).  GETVISTAU reads the Chou-Suarez SW tables (rad_constants): loaded here on the first call if sw_driver_chou has not.
+   subroutine sw_update_clouds(ncol, lm, lcldmh, lcldlm, taucrit, fin, fout)
+      integer, intent(in) :: ncol, lm, lcldmh, lcldlm
+      real, intent(in) :: taucrit
+      type(c_ptr), intent(in) :: fin(SWK_NIN), fout(SWK_NOUT)
+      real, parameter :: grav = 9.80665, undef = 1.0e15
+      real(c_double) :: consts(SWK_NCONST)
+      integer :: rc
+      rc = load_chou_sw_tables()
+      if (rc /= 0) call geosrad_fail('UPDATE_EXPORT (clouds): Chou-Suarez SW tables')
+      consts(SWK_C_GRAV) = real(grav, c_double); consts(SWK_C_UNDEF) = real(undef, c_double)
+      if (geosrad_sw_update_clouds_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(lm,c_int), int(lcldmh,c_int), &
+            int(lcldlm,c_int), real(taucrit,c_double), consts, fin, fout) /= 0) call geosrad_fail('UPDATE_EXPORT (clouds)')
+   end subroutine
+
    ! RRTMG branch of SORADCORE (GEOS_SolarGridComp.F90:6113-6450) on the packed daytime columns
    subroutine sw_driver_rrtmg(ncol, lm, nb_aer, fin, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr, include_aerosols, lcldlm, &
          lcldmh, fout, rc)
@@ -338,20 +372,25 @@ contains
       real, intent(in) :: hk_uv_temp(5), hk_ir_temp(3,10)
       logical, intent(in) :: do_drfband
       integer, intent(out) :: rc
-      real :: x
-      logical, save :: loaded = .false.
-      if (.not. loaded) then       ! sorad's coefficient tables (the reference keeps them as module data in sorad_constants)
-         if (kind(x) == 4) then
-            rc = geosrad_load_tables_chou_sw(geosrad_ctx_handle(), geosrad_data_path('chou_sw_r4.grtb'))
-         else
-            rc = geosrad_load_tables_chou_sw(geosrad_ctx_handle(), geosrad_data_path('chou_sw_r8.grtb'))
-         end if
-         if (rc /= 0) return
-         loaded = .true.
-      end if
+      rc = load_chou_sw_tables()
+      if (rc /= 0) return
       rc = geosrad_sw_driver_chou_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(lm,c_int), fin, consts, int(lcldmh,c_int), &
             int(lcldlm,c_int), hk_uv_temp, hk_ir_temp, merge(1_c_int, 0_c_int, do_drfband), fout)
    end subroutine
+
+   ! sorad's coefficient tables (the reference keeps them as module data in sorad_constants / rad_constants), once per process
+   integer function load_chou_sw_tables() result(rc)
+      real :: x
+      logical, save :: loaded = .false.
+      rc = 0
+      if (loaded) return
+      if (kind(x) == 4) then
+         rc = geosrad_load_tables_chou_sw(geosrad_ctx_handle(), geosrad_data_path('chou_sw_r4.grtb'))
+      else
+         rc = geosrad_load_tables_chou_sw(geosrad_ctx_handle(), geosrad_data_path('chou_sw_r8.grtb'))
+      end if
+      loaded = rc == 0
+   end function
 
    ! after `call IRRAD` in the Chou-Suarez branch of LW_Driver (GEOS_IrradGridComp.F90:2101-2108, :3601-3616)
    subroutine lw_chou_post(ncol, lm, fin, fout)

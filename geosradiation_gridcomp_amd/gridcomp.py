@@ -3,7 +3,7 @@ enums) and the constants MAPL supplies to the reference (MAPL is not part of the
 MAPL_Constants and are only defaults for callers that do not pass their own).
 
 Reference: GEOSirrad_GridComp/GEOS_IrradGridComp.F90 (LW_Driver :3188-3615, Update_Flx :3796-3999),
-GEOSsolar_GridComp/GEOS_SolarGridComp.F90 (SORADCORE :6113-6450, UPDATE_EXPORT :7540-7579), GEOS_RadiationGridComp.F90:798-819.
+GEOSsolar_GridComp/GEOS_SolarGridComp.F90 (SORADCORE :6113-6450, UPDATE_EXPORT :7006-7058, :7223-7579), GEOS_RadiationGridComp.F90:798-819.
 """
 
 LWD_IN = ["PLE", "PL", "T", "Q", "O3", "CH4", "N2O", "CO2_3D", "CFC11", "CFC12", "HCFC22", "FCLD", "CWC_LIQ", "CWC_ICE", "REFF_LIQ",
@@ -55,6 +55,14 @@ RT_OUT_3D = ["DTDT", "RADLW", "RADSW", "RADLWC", "RADSWC", "RADSWNA", "RADLWCNA"
 RT_OUT_2D = ["BLW", "ALW", "RADSRF"]
 RT_OUT = RT_OUT_3D + RT_OUT_2D
 
+# cloud diagnostics of UPDATE_EXPORT (SOL:7006-7058, :7223-7392), GEOSRAD_SWK_*
+SWK_IN = ["FCLD", "PLE", "T", "QI", "QL", "QR", "QS", "RI", "RL", "RR", "RS", "ZTH"]
+SWK_CONST = ["GRAV", "UNDEF"]
+SWK_OUT_3D = ["FCLD_X", "TAUCLI", "TAUCLW", "TAUCLR", "TAUCLS"]
+SWK_OUT_2D = ["CLDLO", "CLDMD", "CLDHI", "CLDTT", "COTDENLO", "COTDENMD", "COTDENHI", "COTDENTT", "TAULO", "TAUMD", "TAUHI", "TAUTT", "TAUTX",
+              "COTLO", "COTMD", "COTHI", "COTTT", "COTNUMLO", "COTNUMMD", "COTNUMHI", "COTNUMTT", "CLDTMP", "CLDPRS"]
+SWK_OUT = SWK_OUT_3D + SWK_OUT_2D
+
 # MAPL_Constants (not in the reference repository): defaults only
 MAPL = {"AIRMW": 28.965, "H2OMW": 18.015, "O3MW": 47.9982, "RUNIV": 8314.47, "GRAV": 9.80665, "CP": 1004.6830, "UNDEF": 1.0e15}
 MAPL["RGAS"] = MAPL["RUNIV"] / MAPL["AIRMW"]
@@ -66,6 +74,12 @@ def swc_consts(co2=None, **over):
     d = dict(CO2=GAS["CO2"] if co2 is None else co2, O3MW=MAPL["O3MW"], AIRMW=MAPL["AIRMW"], UNDEF=MAPL["UNDEF"])
     d.update(over)
     return [d[k] for k in SWC_CONST]
+
+
+def swk_consts(**over):
+    d = dict(GRAV=MAPL["GRAV"], UNDEF=MAPL["UNDEF"])
+    d.update(over)
+    return [float(d[k]) for k in SWK_CONST]
 
 
 def lwd_consts(**over):

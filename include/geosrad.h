@@ -462,6 +462,27 @@ enum { GEOSRAD_SWS_ALBVF_X, GEOSRAD_SWS_ALBVR_X, GEOSRAD_SWS_ALBNF_X, GEOSRAD_SW
        GEOSRAD_SWS_SLRSUF, GEOSRAD_SWS_SLRSUFC, GEOSRAD_SWS_SLRSUFNA, GEOSRAD_SWS_SLRSUFCNA, GEOSRAD_SWS_NOUT };
 int geosrad_sw_update_surface_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm, double undef, const void *const *in, void *const *out);
 
+/* geosrad_sw_update_clouds_dev: the cloud diagnostics of UPDATE_EXPORT (GEOS_SolarGridComp.F90:7006-7058, :7223-7392), every model step
+ * over all columns: super-layer cloud fractions CLD?? / COTDEN?? (max of FCLD over layers 1..lcldmh-1, lcldmh..lcldlm-1, lcldlm..LM;
+ * CLDTT = 1 - (1-HI)(1-MD)(1-LO)), GETVISTAU's diffuse optical thickness per species (called with ict = lcldmh, icb = lcldlm, :7264-7272;
+ * dp in Pa, radii x 1e6 with no MAPL_UNDEF substitution), its super-layer sums TAU??, TAUTX, COT?? (MAPL_UNDEF where the fraction is 0),
+ * COTNUM??, and the cloud top CLDTMP / CLDPRS: T and the upper interface pressure of the topmost layer whose total optical thickness
+ * exceeds taucrit (the TAUCRIT: resource, default 0.10), MAPL_UNDEF where none does.  ZTH as MAPL_SunGetInsolation returns it (after
+ * max(ZTH,0), :6874, it enters only GETVISTAU's beam scaling, which no export reads: it may be NULL).  Fields (ncol,LM), PLE (ncol,0:LM)
+ * in Pa, the 2-D exports and ZTH (ncol); radii in m.  A NULL output is "not associated" and left untouched.  GEOSRAD_EINVAL, nothing
+ * launched: an input a requested output needs is NULL (FCLD for all; PLE, QI..QS, RI..RS for all but FCLD_X / CLD?? / COTDEN??; T for
+ * CLDTMP), ncol or lm < 1, not 1 < lcldmh < lcldlm <= lm (SOL:3036-3062), or the Chou-Suarez SW tables are not set. */
+enum { GEOSRAD_SWK_FCLD /*(ncol,LM)*/, GEOSRAD_SWK_PLE /*(ncol,0:LM) Pa*/, GEOSRAD_SWK_T, GEOSRAD_SWK_QI, GEOSRAD_SWK_QL, GEOSRAD_SWK_QR,
+       GEOSRAD_SWK_QS, GEOSRAD_SWK_RI /*m*/, GEOSRAD_SWK_RL, GEOSRAD_SWK_RR, GEOSRAD_SWK_RS, GEOSRAD_SWK_ZTH /*(ncol)*/, GEOSRAD_SWK_NIN };
+enum { GEOSRAD_SWK_C_GRAV, GEOSRAD_SWK_C_UNDEF, GEOSRAD_SWK_NCONST };
+enum { GEOSRAD_SWK_FCLD_X /*(ncol,LM)*/, GEOSRAD_SWK_TAUCLI, GEOSRAD_SWK_TAUCLW, GEOSRAD_SWK_TAUCLR, GEOSRAD_SWK_TAUCLS,
+       GEOSRAD_SWK_CLDLO /*(ncol)*/, GEOSRAD_SWK_CLDMD, GEOSRAD_SWK_CLDHI, GEOSRAD_SWK_CLDTT, GEOSRAD_SWK_COTDENLO, GEOSRAD_SWK_COTDENMD,
+       GEOSRAD_SWK_COTDENHI, GEOSRAD_SWK_COTDENTT, GEOSRAD_SWK_TAULO, GEOSRAD_SWK_TAUMD, GEOSRAD_SWK_TAUHI, GEOSRAD_SWK_TAUTT,
+       GEOSRAD_SWK_TAUTX, GEOSRAD_SWK_COTLO, GEOSRAD_SWK_COTMD, GEOSRAD_SWK_COTHI, GEOSRAD_SWK_COTTT, GEOSRAD_SWK_COTNUMLO,
+       GEOSRAD_SWK_COTNUMMD, GEOSRAD_SWK_COTNUMHI, GEOSRAD_SWK_COTNUMTT, GEOSRAD_SWK_CLDTMP, GEOSRAD_SWK_CLDPRS, GEOSRAD_SWK_NOUT };
+int geosrad_sw_update_clouds_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm, int lcldmh, int lcldlm, double taucrit,
+                                 const double *consts /*GRAV, UNDEF*/, const void *const *in, void *const *out);
+
 /* geosrad_rad_tendencies_dev: the parent's heating rates (GEOS_RadiationGridComp.F90:798-819). */
 enum { GEOSRAD_RT_PLE, GEOSRAD_RT_FLW, GEOSRAD_RT_FSW, GEOSRAD_RT_FLWCLR, GEOSRAD_RT_FSWCLR, GEOSRAD_RT_FSWNA, GEOSRAD_RT_FLA,
        GEOSRAD_RT_FSCNA, GEOSRAD_RT_DSFDTS, GEOSRAD_RT_SFCEM, GEOSRAD_RT_TRD, GEOSRAD_RT_NIN };
