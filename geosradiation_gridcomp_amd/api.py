@@ -497,6 +497,18 @@ class Context:
                                                     ci(int(lcldmh)), ci(int(lcldlm)), _p(hu), _p(hi), ci(1 if do_drfband else 0),
                                                     self._ptr_array(G.SWC_OUT, ptr)))
 
+    def lw_driver_chou_dev(self, stream, ncol, lm, ptr, consts, trace, lcldmh, lcldlm, binary_clouds=False):
+        """Chou-Suarez branch of LW_Driver in one call (GEOS_IrradGridComp.F90:1781-1785, :1876-1912, :2093-2108, :3604-3663): `ptr` holds
+        device pointers of gridcomp.LWK_IN (TAUA / SSAA / ASYA may be missing: no aerosols; when given they are rescaled in place like
+        irrad does) and gridcomp.LWK_OUT (LWK_OUT_REQUIRED must be there, the rest missing = not associated); consts in the order of
+        gridcomp.LWK_CONST (gridcomp.lwk_consts()); lcldmh / lcldlm: irrad's ict / icb; binary_clouds: RADLW_BINARY_CLOUDS."""
+        from . import gridcomp as G
+        ci = ctypes.c_int
+        cs = (ctypes.c_double * len(G.LWK_CONST))(*consts)
+        self._chk(self.L.geosrad_lw_driver_chou_dev(self.h, ctypes.c_void_p(stream), ci(ncol), ci(lm), self._ptr_array(G.LWK_IN, ptr), cs,
+                                                    ci(1 if trace else 0), ci(int(lcldmh)), ci(int(lcldlm)), ci(1 if binary_clouds else 0),
+                                                    self._ptr_array(G.LWK_OUT, ptr)))
+
     def lw_chou_post_dev(self, stream, ncol, lm, ptr):
         """after irrad in the Chou-Suarez branch of LW_Driver (GEOS_IrradGridComp.F90:2101-2108, :3601-3616): gridcomp.LWC_IN / LWC_OUT"""
         from . import gridcomp as G

@@ -48,6 +48,14 @@ template <typename R> struct ChouArgs {
     uint32_t *err;
 };
 template <typename R> struct ChouOut { R *flxu, *flcu, *flau, *flxau, *flxd, *flcd, *flad, *flxad, *dfdts, *sfcem; };
+// The cloud imports of the Chou-Suarez branch of LW_Driver as GEOS holds them (GEOS_IrradGridComp.F90:1781-1785, :1898-1912), read by
+// k_chou_prep<R, true> in place of A.cwc / A.reff: q / r = QI QL QR QS / RI RL RR RS (m, np), radii in metres with MAPL_UNDEF allowed;
+// A.fcld is then the FCLD import.  Same leading dimension and column offset as the arrays of ChouArgs.
+template <typename R> struct ChouGeos {
+    const R *q[4], *r[4];
+    R undef;
+    int binary;                            // RADLW_BINARY_CLOUDS: FCLD = 1 where FCLD > 0
+};
 
 template <typename R> GR_DEV R gr_log10(R x);
 template <> GR_DEV float gr_log10<float>(float x) { return log10f(x); }
@@ -60,8 +68,12 @@ template <> GR_DEV double gr_log10<double>(double x) { return log10(x); }
 // The records are column-major ([column][field][level]: k_chou_bands reads a column's fields with lanes = levels), the inputs
 // are level-major with the column index fastest: the transposition goes through an LDS tile of 64 columns x 8 (fp64: 4) levels, so that
 // the inputs are read coalesced (lanes = columns) and the records are written in 32-byte runs (lanes = levels x fields).
-template <typename R>
-__global__ void __launch_bounds__(256) k_chou_prep(ChouArgs<R> A)
+// GEOS = true (geosrad_lw_driver_chou_dev): what LW_Driver does to the cloud imports before `call IRRAD` happens on the way into the
+// tile - the FCLD copy with the binary-cloud option, CWC packed from the four species, REFF = the radius (36 / 14 / 50 / 50 microns
+// where it is MAPL_UNDEF) * 1.0e6 - so no (m, np, 4) copy of them is ever written; the imports are only read.  Every one of these is
+// an exact selection or a single rounded product: the record is bit for bit the one the staged arrays give.
+template <typename R, bool GEOS = false>
+__global__ void __launch_bounds__(256) k_chou_prep(ChouArgs<R> A, ChouGeos<R> G)
 {
     constexpr int CHP_KC = 32 / (int)sizeof(R);      // levels per tile: one 32-byte run per (column, field)
     __shared__ R tile[CF_NFIELD * CHP_KC * 65];
@@ -98,10 +110,24 @@ __global__ void __launch_bounds__(256) k_chou_prep(ChouArgs<R> A)
                 TL(CF_DF22, kk) = (R)789. * AP(A.cfc22, ks) * dp;
                 TL(CF_TA, kk) = ta;
                 TL(CF_DPPA, kk) = k == 0 ? (R)0 : AP(A.ple, k + 1) - AP(A.ple, k);
-                TL(CF_FCLD, kk) = k == 0 ? (R)0 : AP(A.fcld, k);
-                for (int l = 0; l < 4; l++) {
-                    TL(CF_REFF1 + l, kk) = k == 0 ? (R)0 : A.reff[((size_t)l * np + (k - 1)) * ld + i];
-                    TL(CF_CWC1 + l, kk) = k == 0 ? (R)0 : A.cwc[((size_t)l * np + (k - 1)) * ld + i];
+                if constexpr (GEOS) {
+                    const R dflt[4] = {(R)36.e-6, (R)14.e-6, (R)50.e-6, (R)50.e-6};      // IRR:1905-1908
+                    R fc = k == 0 ? (R)0 : AP(A.fcld, k);
+                    if (G.binary && fc > (R)0) fc = (R)1;                                // IRR:1785
+                    TL(CF_FCLD, kk) = fc;
+#pragma unroll
+                    for (int l = 0; l < 4; l++) {
+                        R r = k == 0 ? (R)0 : AP(G.r[l], k);
+                        if (r == G.undef) r = dflt[l];
+                        TL(CF_REFF1 + l, kk) = r * (R)1.0e6;                             // IRR:1909-1912
+                        TL(CF_CWC1 + l, kk) = k == 0 ? (R)0 : AP(G.q[l], k);             // IRR:1898-1901
+                    }
+                } else {
+                    TL(CF_FCLD, kk) = k == 0 ? (R)0 : AP(A.fcld, k);
+                    for (int l = 0; l < 4; l++) {
+                        TL(CF_REFF1 + l, kk) = k == 0 ? (R)0 : A.reff[((size_t)l * np + (k - 1)) * ld + i];
+                        TL(CF_CWC1 + l, kk) = k == 0 ? (R)0 : A.cwc[((size_t)l * np + (k - 1)) * ld + i];
+                    }
                 }
             }
         }

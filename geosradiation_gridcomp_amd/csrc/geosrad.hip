@@ -598,6 +598,8 @@ struct geosrad_ctx {
                               int liqflg, double sc, double dist, int isolvar, int dyofyr, int include_aerosols, int lcldlm,
                               int lcldmh, int normflx, const void *bndsolvar, const void *indsolvar, void *const *out) = 0;
     virtual int lw_chou_post_dev(hipStream_t st, int ncol, int lm, const void *const *in, void *const *out) = 0;
+    virtual int lw_driver_chou_dev(hipStream_t st, int ncol, int lm, const void *const *in, const double *consts, int trace, int lcldmh,
+                                   int lcldlm, int binary_clouds, void *const *out) = 0;
     virtual int sw_driver_chou_dev(hipStream_t st, int ncol, int lm, const void *const *in, const double *consts, int lcldmh, int lcldlm,
                                    const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out) = 0;
     virtual int lw_update_flx_dev(hipStream_t st, int ncol, int lm, int rrtmg, int lev_mid_high, int lev_low_mid, double undef,
@@ -683,6 +685,7 @@ template <typename R> struct Ctx : geosrad_ctx {
     ChouDev<R> *d_C = nullptr;
     bool have_chou = false;
     char *d_ws_ch = nullptr; size_t ws_ch_bytes = 0;
+    char *d_ws_lwk = nullptr; size_t ws_lwk_bytes = 0;      // lw_driver_chou_dev: irrad's per-column surface arguments (+ TAUDIAG when not exported)
     char *d_ws_drvs[2] = {nullptr, nullptr}; size_t ws_drvs_bytes[2] = {0, 0};      // RRTMG-side arrays of the LW / SW GridComp drivers (separate: the two may run on two streams)
     // McICA segment plans (jump-ahead constants), cached per (mode, nsubcol, nlay, inhomogeneous?)
     struct PlanEntry { McSegDev *d_seg; int nseg; KissJump jsub, jhalf; };
@@ -713,6 +716,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (d_ws_swc) (void)hipFree(d_ws_swc);
         if (d_C) (void)hipFree(d_C);
         if (d_ws_ch) (void)hipFree(d_ws_ch);
+        if (d_ws_lwk) (void)hipFree(d_ws_lwk);
         for (char *q : d_ws_drvs) if (q) (void)hipFree(q);
         if (d_S) (void)hipFree(d_S);
         if (d_ws_sw) (void)hipFree(d_ws_sw);
@@ -896,7 +900,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         return sync_T();
     }
 
-    size_t workspace_bytes() const override { return ws_bytes + ws_sw_bytes + ws_ch_bytes + ws_so_bytes + ws_drvs_bytes[0] + ws_drvs_bytes[1] + io_bytes + tab_bytes + tab_sw_bytes + tab_ch_bytes; }
+    size_t workspace_bytes() const override { return ws_bytes + ws_sw_bytes + ws_ch_bytes + ws_lwk_bytes + ws_so_bytes + ws_drvs_bytes[0] + ws_drvs_bytes[1] + io_bytes + tab_bytes + tab_sw_bytes + tab_ch_bytes; }
 
     // ---- workspace -------------------------------------------------------------------------------------
     struct Ws { R *sc; uint32_t *scidx; R *pwvcm; uint8_t *colcloudy, *laycloudy; int32_t *perm, *nclear; R *taucmc, *alpha, *rcorr; uint16_t *s1, *s2; R *part;
@@ -1362,6 +1366,87 @@ template <typename R> struct Ctx : geosrad_ctx {
               need(P.fla_int, P.flad, P.flau) && need(P.dfdtsna, P.dfdts) && need(P.ts_int, P.ts)))
             return fail(GEOSRAD_EINVAL, "an output was requested without the field it is computed from");
         hipLaunchKernelGGL((k_lwd_chou_post<R>), dim3((unsigned)((ncol + 255) / 256), lm + 1), dim3(256), 0, st, P);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+
+    // Chou-Suarez branch of LW_Driver: k_lwk_surface (T2M and the surface arguments) + irrad with the cloud records prepared from the GEOS
+    // fields (k_chou_prep<R, true>) + k_lwd_chou_post + k_lwk_diag.  Beyond irrad's own workspace: 34 values a column, and TAUDIAG when it
+    // is not exported.
+    int lw_driver_chou_dev(hipStream_t st, int ncol, int lm, const void *const *in, const double *consts, int trace, int lcldmh, int lcldlm,
+                           int binary_clouds, void *const *out) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (!have_chou) return fail(GEOSRAD_EINVAL, "Chou-Suarez LW tables not set: call geosrad_load_tables_chou_lw first");
+        if (ncol <= 0 || lm < 4 || lm > 400) return fail(GEOSRAD_EINVAL, "bad ncol/lm");
+        if (!consts) return fail(GEOSRAD_EINVAL, "consts null");
+        if (!(1 < lcldmh && lcldmh < lcldlm && lcldlm <= lm)) return fail(GEOSRAD_EINVAL, "super-layer levels must satisfy 1 < lcldmh < lcldlm <= lm");
+        const bool aer = in[GEOSRAD_LWK_TAUA] != nullptr;
+        if (aer != (in[GEOSRAD_LWK_SSAA] != nullptr) || aer != (in[GEOSRAD_LWK_ASYA] != nullptr))
+            return fail(GEOSRAD_EINVAL, "TAUA / SSAA / ASYA: all three or none");
+        for (int k = 0; k < GEOSRAD_LWK_TAUA; k++) if (!in[k]) return fail(GEOSRAD_EINVAL, "null input field");
+        for (int k = 0; k <= GEOSRAD_LWK_SFCEM_INT; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null INTERNAL flux array");
+        if (out[GEOSRAD_LWK_LWS0] && !out[GEOSRAD_LWK_FLX_INT]) return fail(GEOSRAD_EINVAL, "LWS0 was requested without FLX_INT, which it is computed from");
+        const size_t cell = (size_t)ncol * sizeof(R);
+        const size_t o_td = al(34 * cell), need = o_td + (out[GEOSRAD_LWK_TAUDIAG] ? 0 : al((size_t)10 * lm * cell));
+        if (need > ws_lwk_bytes) {
+            if (d_ws_lwk) { HIPCHK(hipFree(d_ws_lwk)); d_ws_lwk = nullptr; ws_lwk_bytes = 0; }
+            if (hipMalloc((void **)&d_ws_lwk, need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "LW_Driver (Chou-Suarez) workspace");
+            ws_lwk_bytes = need;
+        }
+        auto I = [&](int k) { return (const R *)in[k]; };
+        auto O = [&](int k) { return (R *)out[k]; };
+        // 16-byte accesses (4 floats / 2 doubles per thread) when the column count and every address the two kernels touch allow
+        constexpr int VW = 16 / (int)sizeof(R);
+        bool wide = ncol % VW == 0;
+        for (int k : {GEOSRAD_LWK_PLE, GEOSRAD_LWK_T, GEOSRAD_LWK_TS, GEOSRAD_LWK_EMIS}) wide = wide && ((uintptr_t)in[k] & 15) == 0;
+        for (int k = GEOSRAD_LWK_DFDTS; k < GEOSRAD_LWK_NOUT; k++) wide = wide && ((uintptr_t)out[k] & 15) == 0;
+        R *ws = (R *)d_ws_lwk;                 // T2M, FS, TG, TV (ncol); EG, EV, RV (ncol,10); 256-byte aligned base, ncol % VW == 0 keeps 16
+        LwkSurf<R> S{};
+        S.ncol = ncol; S.lm = lm; S.mkappa = -(R)consts[GEOSRAD_LWK_C_KAPPA];
+        S.ple = I(GEOSRAD_LWK_PLE); S.t = I(GEOSRAD_LWK_T); S.ts = I(GEOSRAD_LWK_TS); S.emis = I(GEOSRAD_LWK_EMIS);
+        S.t2m = O(GEOSRAD_LWK_T2M) ? O(GEOSRAD_LWK_T2M) : ws;
+        S.fs = ws + (size_t)ncol; S.tg = ws + (size_t)2 * ncol; S.tv = ws + (size_t)3 * ncol;
+        S.eg = ws + (size_t)4 * ncol; S.ev = ws + (size_t)14 * ncol; S.rv = ws + (size_t)24 * ncol;
+        const dim3 blk(256), gw((unsigned)((ncol / VW + 255) / 256)), g1((unsigned)((ncol + 255) / 256));
+        if (wide) hipLaunchKernelGGL((k_lwk_surface<R, VW>), dim3(gw.x, 11), blk, 0, st, S);
+        else hipLaunchKernelGGL((k_lwk_surface<R, 1>), dim3(g1.x, 11), blk, 0, st, S);
+        HIPCHK(hipGetLastError());
+        R *taudiag = O(GEOSRAD_LWK_TAUDIAG) ? O(GEOSRAD_LWK_TAUDIAG) : (R *)(d_ws_lwk + o_td);
+        const void *ci[C_NIN] = {};
+        ci[C_PLE] = in[GEOSRAD_LWK_PLE]; ci[C_TA] = in[GEOSRAD_LWK_T]; ci[C_WA] = in[GEOSRAD_LWK_Q]; ci[C_OA] = in[GEOSRAD_LWK_O3]; ci[C_TB] = S.t2m;
+        ci[C_N2O] = in[GEOSRAD_LWK_N2O]; ci[C_CH4] = in[GEOSRAD_LWK_CH4]; ci[C_CFC11] = in[GEOSRAD_LWK_CFC11]; ci[C_CFC12] = in[GEOSRAD_LWK_CFC12];
+        ci[C_CFC22] = in[GEOSRAD_LWK_HCFC22]; ci[C_FCLD] = in[GEOSRAD_LWK_FCLD];
+        ci[C_FS] = S.fs; ci[C_TG] = S.tg; ci[C_EG] = S.eg; ci[C_TV] = S.tv; ci[C_EV] = S.ev; ci[C_RV] = S.rv;
+        ChouGeos<R> G{};
+        for (int s = 0; s < 4; s++) { G.q[s] = I(GEOSRAD_LWK_QI + s); G.r[s] = I(GEOSRAD_LWK_RI + s); }
+        G.undef = (R)consts[GEOSRAD_LWK_C_UNDEF]; G.binary = binary_clouds != 0;
+        void *ca[3] = {(void *)in[GEOSRAD_LWK_TAUA], (void *)in[GEOSRAD_LWK_SSAA], (void *)in[GEOSRAD_LWK_ASYA]};      // in-out, like irrad's
+        void *co[CO_NOUT];
+        static_assert(GEOSRAD_LWK_FLXU_INT == CO_FLXU && GEOSRAD_LWK_SFCEM_INT == CO_SFCEM, "the INTERNAL fluxes lead GEOSRAD_LWK_* in irrad's order");
+        for (int k = 0; k <= CO_SFCEM; k++) co[k] = out[k];
+        co[CO_TAUDIAG] = taudiag;
+        // NA = 0 without an aerosol provider (IRR:1966-1970): irrad then never reads the three arrays
+        const int rc = irrad_run(st, ncol, lm, ci, consts[GEOSRAD_LWK_C_CO2_FIXED], trace, lcldmh, lcldlm, 1, aer ? 1 : 0, 10, ca, co, &G);
+        if (rc) return rc;
+        const void *pi[GEOSRAD_LWC_NIN];
+        for (int k = 0; k <= GEOSRAD_LWC_DFDTS; k++) pi[k] = out[k];
+        pi[GEOSRAD_LWC_TS] = in[GEOSRAD_LWK_TS];
+        void *po[GEOSRAD_LWC_NOUT];
+        static_assert(GEOSRAD_LWK_TS_INT - GEOSRAD_LWK_SFCEM_INT == GEOSRAD_LWC_TS_INT - GEOSRAD_LWC_SFCEM_INT, "GEOSRAD_LWK_SFCEM_INT .. TS_INT follow GEOSRAD_LWC_*");
+        for (int k = 0; k < GEOSRAD_LWC_NOUT; k++) po[k] = out[GEOSRAD_LWK_SFCEM_INT + k];
+        const int rc2 = lw_chou_post_dev(st, ncol, lm, pi, po);
+        if (rc2) return rc2;
+        LwkDiag<R> D{};
+        D.ncol = ncol; D.lm = lm; D.taucrit = (R)consts[GEOSRAD_LWK_C_TAUCRIT] / (R)2.13; D.undef = G.undef;
+        D.taudiag = taudiag; D.t = S.t; D.ple = S.ple; D.ts = S.ts; D.dfdts = O(GEOSRAD_LWK_DFDTS); D.sfcem_int = O(GEOSRAD_LWK_SFCEM_INT);
+        D.flx_int = O(GEOSRAD_LWK_FLX_INT);
+        D.tauir = O(GEOSRAD_LWK_TAUIR); D.cldtmp = O(GEOSRAD_LWK_CLDTMP); D.cldprs = O(GEOSRAD_LWK_CLDPRS); D.tsreff = O(GEOSRAD_LWK_TSREFF);
+        D.dsfdts0 = O(GEOSRAD_LWK_DSFDTS0); D.sfcem0 = O(GEOSRAD_LWK_SFCEM0); D.lws0 = O(GEOSRAD_LWK_LWS0);
+        if (D.tauir || D.cldtmp || D.cldprs || D.tsreff || D.dsfdts0 || D.sfcem0 || D.lws0) {
+            if (wide) hipLaunchKernelGGL((k_lwk_diag<R, VW>), gw, blk, 0, st, D);
+            else hipLaunchKernelGGL((k_lwk_diag<R, 1>), g1, blk, 0, st, D);
+        }
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -2309,6 +2394,14 @@ template <typename R> struct Ctx : geosrad_ctx {
     int irrad_dev(hipStream_t st, int m, int np, const void *const *in, double co2, int trace, int ict, int icb, int ns, int na, int nb,
                   void *const *aer, void *const *out) override
     {
+        return irrad_run(st, m, np, in, co2, trace, ict, icb, ns, na, nb, aer, out, nullptr);
+    }
+
+    // geos != nullptr (lw_driver_chou_dev): in[C_FCLD] is the FCLD import and the cloud records come from the GEOS fields of *geos
+    // (k_chou_prep<R, true>); in[C_CWC] / in[C_REFF] are not read
+    int irrad_run(hipStream_t st, int m, int np, const void *const *in, double co2, int trace, int ict, int icb, int ns, int na, int nb,
+                  void *const *aer, void *const *out, const ChouGeos<R> *geos)
+    {
         HIPCHK(hipSetDevice(device));
         if (!have_chou) return fail(GEOSRAD_EINVAL, "Chou-Suarez LW tables not set: call geosrad_load_tables_chou_lw first");
         if (m <= 0 || np < 4 || np > 400) return fail(GEOSRAD_EINVAL, "bad m/np");
@@ -2316,7 +2409,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         const bool oc = (overcast & GEOSRAD_OVERCAST_IRRAD) != 0;      // -DOVERCAST reads neither ict nor icb
         if (!oc && !(ict >= 1 && ict < icb && icb <= np)) return fail(GEOSRAD_EINPUT, "ict / icb must satisfy 1 <= ict < icb <= np");
         if (nb < 10) return fail(GEOSRAD_EINVAL, "nb (bands of the aerosol arrays) must be 10");
-        for (int k = 0; k < C_NIN; k++) if (!in[k]) return fail(GEOSRAD_EINVAL, "null input array");
+        for (int k = 0; k < C_NIN; k++) if (!in[k] && !(geos && (k == C_CWC || k == C_REFF))) return fail(GEOSRAD_EINVAL, "null input array");
         for (int k = 0; k < CO_NOUT; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
         if (na > 0 && (!aer[0] || !aer[1] || !aer[2])) return fail(GEOSRAD_EINVAL, "na > 0 but taua/ssaa/asya null");
         const int K1 = np + 1, K2 = np + 2;
@@ -2343,14 +2436,19 @@ template <typename R> struct Ctx : geosrad_ctx {
             A.m = nc; A.ld = m; A.np = np; A.trace = trace; A.ict = ict; A.icb = icb; A.ns = ns; A.na = na; A.nb = nb; A.co2 = (R)co2;
             auto P = [&](int k) { return (const R *)in[k] + c0; };
             A.ple = P(C_PLE); A.ta = P(C_TA); A.wa = P(C_WA); A.oa = P(C_OA); A.tb = P(C_TB); A.n2o = P(C_N2O); A.ch4 = P(C_CH4);
-            A.cfc11 = P(C_CFC11); A.cfc12 = P(C_CFC12); A.cfc22 = P(C_CFC22); A.cwc = P(C_CWC); A.fcld = P(C_FCLD); A.reff = P(C_REFF);
+            A.cfc11 = P(C_CFC11); A.cfc12 = P(C_CFC12); A.cfc22 = P(C_CFC22); A.fcld = P(C_FCLD);
+            ChouGeos<R> G{};
+            if (geos) { G = *geos; for (int l = 0; l < 4; l++) { G.q[l] += c0; G.r[l] += c0; } }
+            else { A.cwc = P(C_CWC); A.reff = P(C_REFF); }
             A.fs = P(C_FS); A.tg = P(C_TG); A.eg = P(C_EG); A.tv = P(C_TV); A.ev = P(C_EV); A.rv = P(C_RV);
             A.taua = aer[0] ? (R *)aer[0] + c0 : nullptr; A.ssaa = aer[1] ? (R *)aer[1] + c0 : nullptr; A.asya = aer[2] ? (R *)aer[2] + c0 : nullptr;
             A.taudiag = (R *)out[CO_TAUDIAG] + c0;
             A.rec = (R *)d_ws_ch; A.part = (R *)(d_ws_ch + al((size_t)nc_max * CF_NFIELD * K1 * sizeof(R)));
             A.err = d_err + 2;
             span_begin(10, st);
-            hipLaunchKernelGGL(k_chou_prep<R>, dim3((unsigned)((nc + 63) / 64), (unsigned)chou_prep_tiles<R>(np)), dim3(256), 0, st, A);
+            const dim3 gp((unsigned)((nc + 63) / 64), (unsigned)chou_prep_tiles<R>(np));
+            if (geos) hipLaunchKernelGGL((k_chou_prep<R, true>), gp, dim3(256), 0, st, A, G);
+            else hipLaunchKernelGGL((k_chou_prep<R, false>), gp, dim3(256), 0, st, A, G);
             span_end(st);
             span_begin(11, st);
             if (oc) hipLaunchKernelGGL((k_chou_bands<R, true>), dim3((unsigned)((nc + CH_CPW - 1) / CH_CPW), nband), dim3(64), lds, st, A, (const ChouDev<R> *)d_C);
@@ -2802,6 +2900,7 @@ struct MultiCtx final : geosrad_ctx {
     int sw_driver_dev(hipStream_t, int, int, int, const void *const *, const double *, int, int, double, double, int, int, int, int, int, int,
                       const void *, const void *, void *const *) override { return nodev("geosrad_sw_driver_rrtmg_dev"); }
     int lw_chou_post_dev(hipStream_t, int, int, const void *const *, void *const *) override { return nodev("geosrad_lw_chou_post_dev"); }
+    int lw_driver_chou_dev(hipStream_t, int, int, const void *const *, const double *, int, int, int, int, void *const *) override { return nodev("geosrad_lw_driver_chou_dev"); }
     int sw_driver_chou_dev(hipStream_t, int, int, const void *const *, const double *, int, int, const void *, const void *, int,
                            void *const *) override { return nodev("geosrad_sw_driver_chou_dev"); }
     int lw_update_flx_dev(hipStream_t, int, int, int, int, int, double, const void *const *, void *const *) override { return nodev("geosrad_lw_update_flx_dev"); }
@@ -3235,6 +3334,13 @@ int geosrad_sw_driver_chou_dev(geosrad_ctx *c, void *stream, int ncol, int lm, c
 {
     if (!c || !in || !out) return GEOSRAD_EINVAL;
     return c->sw_driver_chou_dev((hipStream_t)stream, ncol, lm, in, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, out);
+}
+
+int geosrad_lw_driver_chou_dev(geosrad_ctx *c, void *stream, int ncol, int lm, const void *const *in, const double *consts, int trace,
+                               int lcldmh, int lcldlm, int binary_clouds, void *const *out)
+{
+    if (!c || !in || !out) return GEOSRAD_EINVAL;
+    return c->lw_driver_chou_dev((hipStream_t)stream, ncol, lm, in, consts, trace, lcldmh, lcldlm, binary_clouds, out);
 }
 
 int geosrad_lw_chou_post_dev(geosrad_ctx *c, void *stream, int ncol, int lm, const void *const *in, void *const *out)

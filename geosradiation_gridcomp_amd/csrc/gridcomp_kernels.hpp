@@ -470,6 +470,84 @@ template <typename R, int V> __global__ void __launch_bounds__(256) k_lw_update_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// LW_Driver, Chou-Suarez branch (geosrad_lw_driver_chou_dev): the arguments of `irrad` that are per-column (IRR:1876-1892) and the
+// exports formed after it (IRR:3626-3663).  The per-layer arguments are prepared inside k_chou_prep<R, true> (chou_kernels.hpp).
+// ---------------------------------------------------------------------------------------------------------------------------
+template <typename R> struct LwkSurf {
+    int ncol, lm;
+    R mkappa;                                  // -MAPL_KAPPA
+    const R *ple, *t, *ts, *emis;
+    R *t2m, *fs, *tg, *tv, *eg, *ev, *rv;      // NS = 1: (ncol) x 4, (ncol,10) x 3
+};
+// one thread per (V columns, row): row 0 = T2M, FS, TG, TV; rows 1..10 = band row - 1 of EG, EV, RV
+template <typename R, int V> __global__ void __launch_bounds__(256) k_lwk_surface(LwkSurf<R> P)
+{
+#pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
+    const int ij = (blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (ij >= P.ncol) return;
+    const int n = P.ncol, lm = P.lm;
+    R a[V], b[V], c[V];
+    if (blockIdx.y == 0) {
+        ldv<R, V>(P.t, (size_t)(lm - 1) * n + ij, a); ldv<R, V>(P.ple, (size_t)(lm - 1) * n + ij, b); ldv<R, V>(P.ple, (size_t)lm * n + ij, c);
+        VSET(P.t2m, ij, a[v] * gr_pow<R>((R)0.5 * ((R)1.0 + b[v] / c[v]), P.mkappa));      // IRR:1876
+        ldv<R, V>(P.ts, ij, a);
+        VSET(P.fs, ij, (R)1.0); VSET(P.tg, ij, a[v]); VSET(P.tv, ij, a[v]);                    // IRR:1888-1890
+    } else {
+        const size_t o = (size_t)(blockIdx.y - 1) * n + ij;
+        ldv<R, V>(P.emis, ij, a);
+        VSET(P.eg, o, a[v]); VSET(P.ev, o, (R)0.0); VSET(P.rv, o, (R)0.0);                     // IRR:1881-1883, :1891-1892
+    }
+}
+
+template <typename R> struct LwkDiag {
+    int ncol, lm;
+    R taucrit, undef;                          // TAUCRIT / 2.13 (IRR:3628), MAPL_UNDEF
+    const R *taudiag, *t, *ple, *ts, *dfdts, *sfcem_int, *flx_int;      // sfcem_int already positive (IRR:3611)
+    R *tauir, *cldtmp, *cldprs, *tsreff, *dsfdts0, *sfcem0, *lws0;
+};
+// one thread per V columns, walking the layers from the top: TAUIR and the first layer whose infrared cloud optical thickness passes
+// the threshold (IRR:3634-3650); the refresh-time exports ride along (IRR:3659-3663)
+template <typename R, int V> __global__ void __launch_bounds__(256) k_lwk_diag(LwkDiag<R> D)
+{
+#pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
+    const int ij = (blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (ij >= D.ncol) return;
+    const int n = D.ncol, lm = D.lm;
+    const size_t sp = (size_t)lm * n;
+    R a[V], b[V];
+    if (D.tauir || D.cldtmp || D.cldprs) {
+        int top[V], nfound = 0;
+        VFOR top[v] = -1;
+#pragma unroll 4
+        for (int l = 0; l < lm; l++) {
+            const size_t o = (size_t)l * n + ij;
+            R tau[V];
+            ldv<R, V>(D.taudiag, 2 * sp + o, a); ldv<R, V>(D.taudiag, 3 * sp + o, b);
+            VFOR tau[v] = (R)0.5 * (a[v] + b[v]);
+            if (D.tauir) stv<R, V>(D.tauir, o, tau);
+            VFOR if (top[v] < 0 && tau[v] > D.taucrit) { top[v] = l; nfound++; }
+            if (!D.tauir && nfound == V) break;
+        }
+        // layer L = top + 1: T(L) and PLE(L-1), the layer's upper edge, are both row `top` of their arrays
+        VFOR {
+            a[v] = D.undef; b[v] = D.undef;
+            if (top[v] >= 0) {
+                if (D.cldtmp) a[v] = D.t[(size_t)top[v] * n + ij + v];
+                if (D.cldprs) b[v] = D.ple[(size_t)top[v] * n + ij + v];
+            }
+        }
+        VSET(D.cldtmp, ij, a[v]); VSET(D.cldprs, ij, b[v]);
+    }
+    if (D.tsreff) { ldv<R, V>(D.ts, ij, a); VSET(D.tsreff, ij, a[v]); }
+    if (D.dsfdts0) { ldv<R, V>(D.dfdts, sp + ij, a); VSET(D.dsfdts0, ij, -a[v]); }
+    if (D.sfcem0 || D.lws0) {
+        ldv<R, V>(D.sfcem_int, ij, b);
+        VSET(D.sfcem0, ij, b[v]);
+        if (D.lws0) { ldv<R, V>(D.flx_int, sp + ij, a); VSET(D.lws0, ij, a[v] + b[v]); }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // SORADCORE, RRTMG branch (works on the packed daytime columns; ple has LM+1 levels 1..LM+1)
 // ---------------------------------------------------------------------------------------------------------------------------
 template <typename R> struct SwdArgs {

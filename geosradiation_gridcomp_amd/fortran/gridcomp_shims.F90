@@ -5,10 +5,10 @@
 ! GridComp needs to keep its INTERNAL state on the device between the full calculation and the heartbeat updates.
 module geosrad_gridcomp
    use iso_c_binding
-   use geosrad_c, only : geosrad_ctx_handle, geosrad_fail, geosrad_data_path, geosrad_load_tables_chou_sw
+   use geosrad_c, only : geosrad_ctx_handle, geosrad_fail, geosrad_data_path, geosrad_load_tables_chou_sw, geosrad_load_tables_chou_lw
    implicit none
    private
-   public :: lw_driver_rrtmg, lw_driver_rrtmg_rats, lw_update_rats, lw_update_bands, sw_update_surface, sw_update_clouds, sw_driver_rrtmg, sw_driver_chou, lw_chou_post, lw_update_flx, sw_update_export, rad_tendencies
+   public :: lw_driver_rrtmg, lw_driver_rrtmg_rats, lw_update_rats, lw_update_bands, sw_update_surface, sw_update_clouds, sw_driver_rrtmg, sw_driver_chou, lw_driver_chou, lw_chou_post, lw_update_flx, sw_update_export, rad_tendencies
    public :: lit_index, lit_pack, lit_unpack
    public :: dev_alloc, dev_free, dev_put, dev_get, dev_sync
 
@@ -45,6 +45,15 @@ module geosrad_gridcomp
       LWC_FLAD_INT = 7, LWC_FLXAD_INT = 8, LWC_DFDTS = 9, LWC_TS = 10, LWC_NIN = 10
    integer, parameter, public :: LWC_SFCEM_INT = 1, LWC_FLX_INT = 2, LWC_FLXA_INT = 3, LWC_FLC_INT = 4, LWC_FLA_INT = 5, LWC_DFDTSC = 6, &
       LWC_DFDTSNA = 7, LWC_DFDTSCNA = 8, LWC_TS_INT = 9, LWC_NOUT = 9
+   ! ---- GEOSRAD_LWK_* (Chou-Suarez branch of LW_Driver in one call) ----
+   integer, parameter, public :: LWK_PLE = 1, LWK_T = 2, LWK_Q = 3, LWK_O3 = 4, LWK_CH4 = 5, LWK_N2O = 6, LWK_CFC11 = 7, LWK_CFC12 = 8, &
+      LWK_HCFC22 = 9, LWK_FCLD = 10, LWK_QI = 11, LWK_QL = 12, LWK_QR = 13, LWK_QS = 14, LWK_RI = 15, LWK_RL = 16, LWK_RR = 17, LWK_RS = 18, &
+      LWK_TS = 19, LWK_EMIS = 20, LWK_TAUA = 21, LWK_SSAA = 22, LWK_ASYA = 23, LWK_NIN = 23
+   integer, parameter, public :: LWK_C_CO2_FIXED = 1, LWK_C_KAPPA = 2, LWK_C_UNDEF = 3, LWK_C_TAUCRIT = 4, LWK_NCONST = 4
+   integer, parameter, public :: LWK_FLXU_INT = 1, LWK_FLCU_INT = 2, LWK_FLAU_INT = 3, LWK_FLXAU_INT = 4, LWK_FLXD_INT = 5, LWK_FLCD_INT = 6, &
+      LWK_FLAD_INT = 7, LWK_FLXAD_INT = 8, LWK_DFDTS = 9, LWK_SFCEM_INT = 10, LWK_FLX_INT = 11, LWK_FLXA_INT = 12, LWK_FLC_INT = 13, &
+      LWK_FLA_INT = 14, LWK_DFDTSC = 15, LWK_DFDTSNA = 16, LWK_DFDTSCNA = 17, LWK_TS_INT = 18, LWK_TAUIR = 19, LWK_CLDTMP = 20, &
+      LWK_CLDPRS = 21, LWK_TSREFF = 22, LWK_DSFDTS0 = 23, LWK_SFCEM0 = 24, LWK_LWS0 = 25, LWK_T2M = 26, LWK_TAUDIAG = 27, LWK_NOUT = 27
    ! ---- GEOSRAD_SWC_* ----
    integer, parameter, public :: SWC_PLE = 1, SWC_T = 2, SWC_Q = 3, SWC_OX = 4, SWC_CL = 5, SWC_QI = 6, SWC_QL = 7, SWC_QR = 8, SWC_QS = 9, &
       SWC_RI = 10, SWC_RL = 11, SWC_RR = 12, SWC_RS = 13, SWC_TAUA = 14, SWC_SSAA = 15, SWC_ASYA = 16, SWC_ZT = 17, SWC_ALBVR = 18, &
@@ -152,6 +161,14 @@ module geosrad_gridcomp
          type(c_ptr), intent(in) :: fin(*), fout(*)
          real(c_double), intent(in) :: consts(*)
          real, intent(in) :: hk_uv(*), hk_ir(*)
+      end function
+      integer(c_int) function geosrad_lw_driver_chou_dev(ctx, stream, ncol, lm, fin, consts, trace, lcldmh, lcldlm, binary_clouds, fout) &
+            bind(C, name='geosrad_lw_driver_chou_dev')
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: ctx, stream
+         integer(c_int), value :: ncol, lm, trace, lcldmh, lcldlm, binary_clouds
+         type(c_ptr), intent(in) :: fin(*), fout(*)
+         real(c_double), intent(in) :: consts(*)
       end function
       integer(c_int) function geosrad_lw_chou_post_dev(ctx, stream, ncol, lm, fin, fout) bind(C, name='geosrad_lw_chou_post_dev')
          import :: c_int, c_ptr
@@ -391,6 +408,31 @@ contains
       end if
       loaded = rc == 0
    end function
+
+   ! Chou-Suarez branch of LW_Driver in one call (GEOS_IrradGridComp.F90:1781-1785, :1876-1912, :2093-2108, :3604-3663): the imports as
+   ! GEOS holds them in, the INTERNAL fluxes and the refresh-time exports out; fin(LWK_TAUA:LWK_ASYA) all c_null_ptr = no aerosol provider.
+   ! binary_clouds: the RADLW_BINARY_CLOUDS resource.  irrad's coefficient tables are loaded on the first call.
+   subroutine lw_driver_chou(ncol, lm, fin, consts, trace, lcldmh, lcldlm, binary_clouds, fout, rc)
+      integer, intent(in) :: ncol, lm, lcldmh, lcldlm
+      type(c_ptr), intent(in) :: fin(LWK_NIN), fout(LWK_NOUT)
+      real(c_double), intent(in) :: consts(LWK_NCONST)
+      logical, intent(in) :: trace, binary_clouds
+      integer, intent(out) :: rc
+      real :: x
+      logical, save :: loaded = .false.
+      rc = 0
+      if (.not. loaded) then
+         if (kind(x) == 4) then
+            rc = geosrad_load_tables_chou_lw(geosrad_ctx_handle(), geosrad_data_path('chou_lw_r4.grtb'))
+         else
+            rc = geosrad_load_tables_chou_lw(geosrad_ctx_handle(), geosrad_data_path('chou_lw_r8.grtb'))
+         end if
+         if (rc /= 0) return
+         loaded = .true.
+      end if
+      rc = geosrad_lw_driver_chou_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(lm,c_int), fin, consts, &
+            merge(1_c_int, 0_c_int, trace), int(lcldmh,c_int), int(lcldlm,c_int), merge(1_c_int, 0_c_int, binary_clouds), fout)
+   end subroutine
 
    ! after `call IRRAD` in the Chou-Suarez branch of LW_Driver (GEOS_IrradGridComp.F90:2101-2108, :3601-3616)
    subroutine lw_chou_post(ncol, lm, fin, fout)

@@ -1,4 +1,4 @@
-"""Argument orders of the GridComp data-path entry points (include/geosrad.h, the GEOSRAD_LWD_* / SWD_* / LWU_* / SWU_* / RT_*
+"""Argument orders of the GridComp data-path entry points (include/geosrad.h, the GEOSRAD_LWD_* / LWK_* / SWD_* / LWU_* / SWU_* / RT_*
 enums) and the constants MAPL supplies to the reference (MAPL is not part of the reference repository; these are the values of
 MAPL_Constants and are only defaults for callers that do not pass their own).
 
@@ -23,6 +23,14 @@ LWR_OUT = ["dOLR", "dLWS", "dFLNS", "dSFCEM", "NETTRAP", "COLTRAP", "FLX", "DFDT
 
 LWC_IN = ["FLXU_INT", "FLCU_INT", "FLAU_INT", "FLXAU_INT", "FLXD_INT", "FLCD_INT", "FLAD_INT", "FLXAD_INT", "DFDTS", "TS"]
 LWC_OUT = ["SFCEM_INT", "FLX_INT", "FLXA_INT", "FLC_INT", "FLA_INT", "DFDTSC", "DFDTSNA", "DFDTSCNA", "TS_INT"]
+
+# Chou-Suarez branch of LW_Driver in one call (IRR:1781-1785, :1876-1912, :2093-2108, :3604-3663): GEOSRAD_LWK_*
+LWK_IN = ["PLE", "T", "Q", "O3", "CH4", "N2O", "CFC11", "CFC12", "HCFC22", "FCLD", "QI", "QL", "QR", "QS", "RI", "RL", "RR", "RS", "TS", "EMIS",
+          "TAUA", "SSAA", "ASYA"]
+LWK_CONST = ["CO2_FIXED", "KAPPA", "UNDEF", "TAUCRIT"]
+LWK_OUT_REQUIRED = ["FLXU_INT", "FLCU_INT", "FLAU_INT", "FLXAU_INT", "FLXD_INT", "FLCD_INT", "FLAD_INT", "FLXAD_INT", "DFDTS", "SFCEM_INT"]
+LWK_OUT = LWK_OUT_REQUIRED + ["FLX_INT", "FLXA_INT", "FLC_INT", "FLA_INT", "DFDTSC", "DFDTSNA", "DFDTSCNA", "TS_INT", "TAUIR", "CLDTMP", "CLDPRS",
+                              "TSREFF", "DSFDTS0", "SFCEM0", "LWS0", "T2M", "TAUDIAG"]
 
 SWD_IN = ["PLE", "PL", "T", "Q", "O3", "CH4", "CL", "TS", "QQ_ICE", "QQ_LIQ", "RR_ICE", "RR_LIQ", "TAUA", "SSAA", "ASYA", "ZT", "ALAT",
           "ALBVR", "ALBVF", "ALBNR", "ALBNF"]
@@ -74,6 +82,14 @@ def swc_consts(co2=None, **over):
     d = dict(CO2=GAS["CO2"] if co2 is None else co2, O3MW=MAPL["O3MW"], AIRMW=MAPL["AIRMW"], UNDEF=MAPL["UNDEF"])
     d.update(over)
     return [d[k] for k in SWC_CONST]
+
+
+def lwk_consts(co2=None, taucrit=0.30, **over):
+    """consts of Context.lw_driver_chou_dev: MAPL_KAPPA = MAPL_RGAS / MAPL_CP; taucrit = the TAUCRIT: resource of the Irrad GridComp"""
+    d = dict(CO2_FIXED=GAS["CO2_FIXED"] if co2 is None else co2, KAPPA=(MAPL["RUNIV"] / MAPL["AIRMW"]) / MAPL["CP"], UNDEF=MAPL["UNDEF"],
+             TAUCRIT=taucrit)
+    d.update(over)
+    return [float(d[k]) for k in LWK_CONST]
 
 
 def swk_consts(**over):

@@ -264,6 +264,31 @@ def geos_chou_sw_fields(inp, aerosol=True, undef_every=7):
     return f
 
 
+def geos_chou_lw_fields(inp, aerosol=True, undef_every=7):
+    """GEOS-side fields (gridcomp.LWK_IN; model ordering, SI units, [k][ij]) that lead the Chou-Suarez branch of LW_Driver
+    (GEOS_IrradGridComp.F90:1876-1912) back to `chou_lw_inputs(inp)`: the four hydrometeor species, effective radii in metres with every
+    `undef_every`-th cell MAPL_UNDEF (the GridComp then substitutes 36 / 14 / 50 / 50 microns), one EMIS for all bands, TS; the aerosol
+    triplet in irrad's (tau, tau*ssa, tau*ssa*g) form only with `aerosol` (else no provider: NA = 0).  float64 numpy; plus the scalars
+    irrad needs.  (T2M is the GridComp's own: it is not a field.)"""
+    from . import gridcomp as G
+    ch = chou_lw_inputs(inp, aerosol=aerosol)
+    f64 = lambda a: np.asarray(a, dtype=np.float64)
+    f = {"PLE": f64(ch["ple"]), "T": f64(ch["ta"]), "Q": f64(ch["wa"]), "O3": f64(ch["oa"]), "CH4": f64(ch["ch4"]), "N2O": f64(ch["n2o"]),
+         "CFC11": f64(ch["cfc11"]), "CFC12": f64(ch["cfc12"]), "HCFC22": f64(ch["cfc22"]), "FCLD": f64(ch["fcld"]), "TS": f64(inp["tsfc"]),
+         "EMIS": f64(inp["emis"])[0].copy()}
+    for s, (q, r) in enumerate((("QI", "RI"), ("QL", "RL"), ("QR", "RR"), ("QS", "RS"))):
+        f[q] = f64(ch["cwc"][s])
+        rr = f64(ch["reff"][s]) * 1.0e-6
+        if undef_every:
+            flat = rr.reshape(-1)
+            flat[s::undef_every] = G.MAPL["UNDEF"]
+        f[r] = rr
+    if aerosol and ch["na"] > 0:
+        f["TAUA"] = f64(ch["taua"]); f["SSAA"] = f64(ch["ssaa"]); f["ASYA"] = f64(ch["asya"])
+    f["LCLDMH"] = int(ch["ict"]); f["LCLDLM"] = int(ch["icb"]); f["CO2"] = float(ch["co2"])
+    return f
+
+
 def geos_lw_fields(inp):
     """GEOS-side (model ordering, 1 = top, SI units) fields of gridcomp.LWD_IN that lead LW_Driver's prep
     (GEOS_IrradGridComp.F90:3243-3371) back to (nearly) the RRTMG-side columns `inp` of make_columns; plus the model-ordering

@@ -80,8 +80,8 @@ int geosrad_set_chunk(geosrad_ctx *ctx, int max_columns);
 size_t geosrad_workspace_bytes(const geosrad_ctx *ctx);
 /* Chou-Suarez cloud mode: the reference's -DOVERCAST build of irrad.F90 / sorad.F90 (a layer is clear or fully cloudy; random overlap of
  * the cloudy layers; sorad's cloud optical thickness not scaled; ict / icb not read).  One flag per scheme (GEOS compiles them in separate
- * components); 0 (the default) = maximum-random overlap.  Applies to geosrad_irrad[_dev], geosrad_sorad[_dev] and
- * geosrad_sw_driver_chou_dev, on every device of a multi-device context.  Unknown bits: GEOSRAD_EINVAL, the mode unchanged. */
+ * components); 0 (the default) = maximum-random overlap.  Applies to geosrad_irrad[_dev], geosrad_sorad[_dev],
+ * geosrad_lw_driver_chou_dev and geosrad_sw_driver_chou_dev, on every device of a multi-device context.  Unknown bits: GEOSRAD_EINVAL, the mode unchanged. */
 enum { GEOSRAD_OVERCAST_IRRAD = 1, GEOSRAD_OVERCAST_SORAD = 2 };
 int geosrad_set_overcast(geosrad_ctx *ctx, int flags);
 int geosrad_get_overcast(const geosrad_ctx *ctx);
@@ -361,6 +361,37 @@ enum { GEOSRAD_LWC_FLXU_INT, GEOSRAD_LWC_FLCU_INT, GEOSRAD_LWC_FLAU_INT, GEOSRAD
 enum { GEOSRAD_LWC_SFCEM_INT /*in-out*/, GEOSRAD_LWC_FLX_INT, GEOSRAD_LWC_FLXA_INT, GEOSRAD_LWC_FLC_INT, GEOSRAD_LWC_FLA_INT, GEOSRAD_LWC_DFDTSC,
        GEOSRAD_LWC_DFDTSNA, GEOSRAD_LWC_DFDTSCNA, GEOSRAD_LWC_TS_INT, GEOSRAD_LWC_NOUT };
 int geosrad_lw_chou_post_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm, const void *const *in, void *const *out);
+
+/* geosrad_lw_driver_chou_dev: the whole Chou-Suarez branch of LW_Driver in one call (GEOS_IrradGridComp.F90:1781-1785 the FCLD copy with
+ * the RADLW_BINARY_CLOUDS option, :1876-1912 T2M, the surface arguments FS / TG / EG / TV / EV / RV with NS = 1, CWC and REFF from the four
+ * species with MAPL_UNDEF radii replaced by 36 / 14 / 50 / 50 microns and metres turned into microns, :1966-1970 NA = 0 without aerosols,
+ * :2093-2108 `call IRRAD` and the derivatives it does not provide, :3604-3619 net fluxes, the sign of SFCEM, TS_INT, :3626-3650 the infrared
+ * cloud exports, :3654-3663 the refresh-time exports).  Fields in the GEOS layout and MODEL ordering (what irrad expects).
+ *   in : PLE (ncol,0:LM) Pa; T .. RS (ncol,LM), radii in metres, MAPL_UNDEF allowed; TS, EMIS (ncol); TAUA, SSAA, ASYA (ncol,LM,10) in
+ *        irrad's (tau, tau*ssa, tau*ssa*g) form, all three or none (none: NA = 0).  The three aerosol arrays are IN-OUT: rescaled in place
+ *        like irrad does (irrad.F90:655-678).  Nothing else is written: unlike the reference's `WHERE (RI == MAPL_UNDEF) RI = 36.e-6`
+ *        the imports stay as they are, and FCLD is not changed by binary_clouds.
+ *   consts: CO2_FIXED, MAPL_KAPPA, MAPL_UNDEF, TAUCRIT (the resource value, default 0.30; divided by 2.13 in the real kind, :3628).
+ *   trace, lcldmh, lcldlm: irrad's TRACE (.true. in the reference, :1487), ict, icb; 1 < lcldmh < lcldlm <= lm (:1917-1943), else
+ *        GEOSRAD_EINVAL.  The -DOVERCAST mode of the context (geosrad_set_overcast) applies as for geosrad_irrad_dev.
+ *   out: required FLXU_INT .. FLXAD_INT, DFDTS (ncol,0:LM) and SFCEM_INT (ncol), positive on return (:3611).  Optional (NULL = not
+ *        associated): FLX_INT, FLXA_INT, FLC_INT, FLA_INT, DFDTSC (= 0), DFDTSNA (= DFDTS), DFDTSCNA (= 0) (ncol,0:LM), TS_INT (ncol);
+ *        TAUIR (ncol,LM) = 0.5 (TAUDIAG(3) + TAUDIAG(4)); CLDTMP, CLDPRS (ncol) = T(L), PLE(L-1) of the first layer L from the top with
+ *        TAUIR(L) > TAUCRIT / 2.13, MAPL_UNDEF where there is none; TSREFF = TS, DSFDTS0 = -DFDTS(LM), SFCEM0 = SFCEM_INT, LWS0 =
+ *        FLX_INT(LM) + SFCEM_INT (needs FLX_INT, else GEOSRAD_EINVAL); and for parity tests T2M (ncol) and irrad's TAUDIAG (ncol,LM,10).
+ * Honours geosrad_set_chunk; results do not depend on the chunk size. */
+enum { GEOSRAD_LWK_PLE, GEOSRAD_LWK_T, GEOSRAD_LWK_Q, GEOSRAD_LWK_O3, GEOSRAD_LWK_CH4, GEOSRAD_LWK_N2O, GEOSRAD_LWK_CFC11, GEOSRAD_LWK_CFC12,
+       GEOSRAD_LWK_HCFC22, GEOSRAD_LWK_FCLD, GEOSRAD_LWK_QI, GEOSRAD_LWK_QL, GEOSRAD_LWK_QR, GEOSRAD_LWK_QS, GEOSRAD_LWK_RI, GEOSRAD_LWK_RL,
+       GEOSRAD_LWK_RR, GEOSRAD_LWK_RS, GEOSRAD_LWK_TS, GEOSRAD_LWK_EMIS, GEOSRAD_LWK_TAUA /*in-out, nullable*/, GEOSRAD_LWK_SSAA,
+       GEOSRAD_LWK_ASYA, GEOSRAD_LWK_NIN };
+enum { GEOSRAD_LWK_C_CO2_FIXED, GEOSRAD_LWK_C_KAPPA, GEOSRAD_LWK_C_UNDEF, GEOSRAD_LWK_C_TAUCRIT, GEOSRAD_LWK_NCONST };
+enum { GEOSRAD_LWK_FLXU_INT, GEOSRAD_LWK_FLCU_INT, GEOSRAD_LWK_FLAU_INT, GEOSRAD_LWK_FLXAU_INT, GEOSRAD_LWK_FLXD_INT, GEOSRAD_LWK_FLCD_INT,
+       GEOSRAD_LWK_FLAD_INT, GEOSRAD_LWK_FLXAD_INT, GEOSRAD_LWK_DFDTS, GEOSRAD_LWK_SFCEM_INT, GEOSRAD_LWK_FLX_INT, GEOSRAD_LWK_FLXA_INT,
+       GEOSRAD_LWK_FLC_INT, GEOSRAD_LWK_FLA_INT, GEOSRAD_LWK_DFDTSC, GEOSRAD_LWK_DFDTSNA, GEOSRAD_LWK_DFDTSCNA, GEOSRAD_LWK_TS_INT,
+       GEOSRAD_LWK_TAUIR, GEOSRAD_LWK_CLDTMP, GEOSRAD_LWK_CLDPRS, GEOSRAD_LWK_TSREFF, GEOSRAD_LWK_DSFDTS0, GEOSRAD_LWK_SFCEM0, GEOSRAD_LWK_LWS0,
+       GEOSRAD_LWK_T2M, GEOSRAD_LWK_TAUDIAG, GEOSRAD_LWK_NOUT };
+int geosrad_lw_driver_chou_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm, const void *const *in, const double *consts, int trace,
+                               int lcldmh, int lcldlm, int binary_clouds, void *const *out);
 
 /* geosrad_sw_driver_rrtmg_dev: the RRTMG branch of SORADCORE on the packed daytime columns (GEOS_SolarGridComp.F90:6113-6219
  * prep / flip incl. the in-place aerosol normalisation, :6330-6388 the rrtmg_sw call, :6395-6450 un-flip, cloud fractions,
