@@ -29,6 +29,12 @@ NBNDSW = 14
 NGPTSW = 112
 _SW_GAS = ["h2ovmr", "o3vmr", "co2vmr", "ch4vmr", "o2vmr"]
 _SW_COT = ["cotdtp", "cotdhp", "cotdmp", "cotdlp", "cotntp", "cotnhp", "cotnmp", "cotnlp"]
+# The SOLAR_RADVAL dummy arguments of rrtmg_sw in the reference's order (SW/rrtmg_sw_rad.F90:86-119) = the GEOSRAD_RV_* slots of
+# include/geosrad.h: 15 families (combined delta-scaled optical thickness; per phase l / i: un-scaled and delta-scaled optical thickness,
+# single-scattering albedo, asymmetry parameter; delta-scaled forward-scattering fraction), each a denominator `d` and a numerator `n`
+# for the whole column (tp) and the high / middle / low super-layer (hp, mp, lp)
+RADVAL_FAMILIES = ["cds", "cotl", "cdsl", "coti", "cdsi", "ssal", "sdsl", "ssai", "sdsi", "asml", "adsl", "asmi", "adsi", "forl", "fori"]
+RADVAL_NAMES = [f + dn + sl for f in RADVAL_FAMILIES for dn in "dn" for sl in ("tp", "hp", "mp", "lp")]
 
 _IN2D = ["h2ovmr", "o3vmr", "co2vmr", "ch4vmr", "n2ovmr", "o2vmr", "cfc11vmr", "cfc12vmr", "cfc22vmr", "ccl4vmr",
          "cldf", "ciwp", "clwp", "rei", "rel"]
@@ -190,9 +196,10 @@ class Context:
     def rrtmg_sw(self, rpart, ncol, nlay, scon, adjes, coszen, isolvar, play, plev, tlay, h2ovmr, o3vmr, co2vmr, ch4vmr, o2vmr,
                  iceflgsw, liqflgsw, cld, ciwp, clwp, rei, rel, dyofyr, zm, alat, iaer, tauaer, ssaaer, asmaer,
                  asdir, asdif, aldir, aldif, cloudLM, cloudMH, normFlx, do_drfband=False, bndscl=None, indsolvar=None, out=None,
-                 solcycfrac=None):
+                 solcycfrac=None, radval=False):
         """rrtmg_sw (SW/rrtmg_sw_rad.F90:68).  Returns dict(swuflx,swdflx,swuflxc,swdflxc (nlay+1,ncol); nirr..uvrf,
-        cotdtp..cotnlp (ncol); fswband[,drband,dfband] (14,ncol); clearCounts (4,ncol))."""
+        cotdtp..cotnlp (ncol); fswband[,drband,dfband] (14,ncol); clearCounts (4,ncol)).  radval=True: the reference's SOLAR_RADVAL
+        build (geosrad_rrtmg_sw_radval): also `radval` (120,ncol) and a view of each row under its name in RADVAL_NAMES."""
         dt = self.dtype
         c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=dt)
         gases = [c(x) for x in (h2ovmr, o3vmr, co2vmr, ch4vmr, o2vmr)]
@@ -208,30 +215,41 @@ class Context:
             if do_drfband:
                 out["drband"] = np.zeros((NBNDSW, ncol), dtype=dt); out["dfband"] = np.zeros((NBNDSW, ncol), dtype=dt)
             out["clearCounts"] = np.zeros((4, ncol), dtype=np.int32)
+        if radval and "radval" not in out:
+            out["radval"] = np.zeros((len(RADVAL_NAMES), ncol), dtype=dt)
         bs = None if bndscl is None else np.ascontiguousarray(bndscl, dtype=dt)
         ind = None if indsolvar is None else np.ascontiguousarray(indsolvar, dtype=dt)
         scf = None if solcycfrac is None else np.array([solcycfrac], dtype=dt)
         ci, cd = ctypes.c_int, ctypes.c_double
-        rc = self.L.geosrad_rrtmg_sw(
+        rc = (self.L.geosrad_rrtmg_sw_radval if radval else self.L.geosrad_rrtmg_sw)(
             self.h, ci(rpart), ci(ncol), ci(nlay), cd(scon), cd(adjes), _p(coszen), ci(isolvar), _p(play), _p(plev), _p(tlay),
             *[_p(a) for a in gases], ci(iceflgsw), ci(liqflgsw), *[_p(a) for a in cl5], ci(int(dyofyr)), _p(zm), _p(alat), ci(iaer),
             _p(tauaer), _p(ssaaer), _p(asmaer), _p(asdir), _p(asdif), _p(aldir), _p(aldif), ci(int(cloudLM)), ci(int(cloudMH)),
             ci(int(normFlx)), _p(out["clearCounts"]), _p(out["swuflx"]), _p(out["swdflx"]), _p(out["swuflxc"]), _p(out["swdflxc"]),
             *[_p(out[k]) for k in ("nirr", "nirf", "parr", "parf", "uvrr", "uvrf", "fswband")], *[_p(out[k]) for k in _SW_COT],
-            ci(1 if do_drfband else 0), _p(out.get("drband")), _p(out.get("dfband")), _p(bs), _p(ind), _p(scf))
+            ci(1 if do_drfband else 0), _p(out.get("drband")), _p(out.get("dfband")), _p(bs), _p(ind), _p(scf),
+            *([_p(out["radval"])] if radval else []))
         self._chk(rc)
+        if radval:
+            for k, name in enumerate(RADVAL_NAMES):
+                out[name] = out["radval"][k]
         return out
 
+    def rrtmg_sw_radval(self, *args, **kw):
+        """rrtmg_sw as the reference builds it with -DSOLAR_RADVAL (SW/rrtmg_sw_rad.F90:85-120): the arguments of rrtmg_sw; the result
+        also holds the 120 cloud-optics diagnostics cdsdtp .. forinlp (ncol each, keys RADVAL_NAMES)."""
+        return self.rrtmg_sw(*args, radval=True, **kw)
+
     def rrtmg_sw_columns(self, inp, scon=1361.0, adjes=1.0, isolvar=0, iceflg=3, liqflg=1, iaer=0, normFlx=0, do_drfband=False,
-                         bndscl=None, indsolvar=None, rpart=4, out=None, solcycfrac=None):
-        """Convenience: `inp` as produced by synth.make_columns."""
+                         bndscl=None, indsolvar=None, rpart=4, out=None, solcycfrac=None, radval=False):
+        """Convenience: `inp` as produced by synth.make_columns.  radval=True: see rrtmg_sw_radval."""
         nlay, ncol = inp["play"].shape
         aer = [inp.get(k) if iaer == 10 else None for k in ("tauaer_sw", "ssaaer_sw", "asmaer_sw")]
         return self.rrtmg_sw(rpart, ncol, nlay, scon, adjes, inp["coszen"], isolvar, inp["play"], inp["plev"], inp["tlay"],
                              *[inp[k] for k in _SW_GAS], iceflg, liqflg, inp["cldf"], inp["ciwp"], inp["clwp"], inp["rei"], inp["rel"],
                              inp["dyofyr"], inp["zm"], inp["alat"], iaer, *aer, inp["asdir"], inp["asdif"], inp["aldir"], inp["aldif"],
                              inp["cloudLM"], inp["cloudMH"], normFlx, do_drfband=do_drfband, bndscl=bndscl, indsolvar=indsolvar, out=out,
-                             solcycfrac=solcycfrac)
+                             solcycfrac=solcycfrac, radval=radval)
 
     def rrtmg_sw_taumol(self, inp, scon=1361.0, isolvar=0, bndscl=None, indsolvar=None, solcycfrac=None):
         """(taug, taur) numpy (ncol,112,nlay) and ssi (ncol,112) as left by the reference's taumol_sw."""
@@ -266,22 +284,28 @@ class Context:
         return o
 
     def rrtmg_sw_dev(self, stream, ncol, nlay, scon, adjes, isolvar, ptr, iceflg, liqflg, dyofyr, iaer, cloudLM, cloudMH, normFlx=0,
-                     do_drfband=False, bndscl=None, indsolvar=None, rpart=4, solcycfrac=None):
-        """`ptr`: dict name -> device address (int) for every argument array of rrtmg_sw (inputs and outputs)."""
+                     do_drfband=False, bndscl=None, indsolvar=None, rpart=4, solcycfrac=None, radval=False):
+        """`ptr`: dict name -> device address (int) for every argument array of rrtmg_sw (inputs and outputs).  radval=True
+        (rrtmg_sw_radval_dev): ptr["radval"] is the (120,ncol) device array of the SOLAR_RADVAL diagnostics."""
         dt = self.dtype
         v = lambda k: ctypes.c_void_p(ptr[k]) if ptr.get(k) else None
         bs = None if bndscl is None else np.ascontiguousarray(bndscl, dtype=dt)
         ind = None if indsolvar is None else np.ascontiguousarray(indsolvar, dtype=dt)
         scf = None if solcycfrac is None else np.array([solcycfrac], dtype=dt)
         ci, cd = ctypes.c_int, ctypes.c_double
-        rc = self.L.geosrad_rrtmg_sw_dev(
+        rc = (self.L.geosrad_rrtmg_sw_radval_dev if radval else self.L.geosrad_rrtmg_sw_dev)(
             self.h, ctypes.c_void_p(stream), ci(rpart), ci(ncol), ci(nlay), cd(scon), cd(adjes), v("coszen"), ci(isolvar), v("play"),
             v("plev"), v("tlay"), *[v(k) for k in _SW_GAS], ci(iceflg), ci(liqflg), v("cldf"), v("ciwp"), v("clwp"), v("rei"), v("rel"),
             ci(int(dyofyr)), v("zm"), v("alat"), ci(iaer), v("tauaer_sw"), v("ssaaer_sw"), v("asmaer_sw"), v("asdir"), v("asdif"),
             v("aldir"), v("aldif"), ci(int(cloudLM)), ci(int(cloudMH)), ci(int(normFlx)), v("clearCounts_sw"), v("swuflx"), v("swdflx"),
             v("swuflxc"), v("swdflxc"), *[v(k) for k in ("nirr", "nirf", "parr", "parf", "uvrr", "uvrf", "fswband")],
-            *[v(k) for k in _SW_COT], ci(1 if do_drfband else 0), v("drband"), v("dfband"), _p(bs), _p(ind), _p(scf))
+            *[v(k) for k in _SW_COT], ci(1 if do_drfband else 0), v("drband"), v("dfband"), _p(bs), _p(ind), _p(scf),
+            *([v("radval")] if radval else []))
         self._chk(rc)
+
+    def rrtmg_sw_radval_dev(self, *args, **kw):
+        """rrtmg_sw_dev plus ptr["radval"]: the SOLAR_RADVAL diagnostics, (120,ncol) on the device, rows in RADVAL_NAMES order."""
+        return self.rrtmg_sw_dev(*args, radval=True, **kw)
 
     # ---- Chou-Suarez LW, host arrays ---------------------------------------------------------------------
     def irrad(self, m, np_, ple, ta, wa, oa, tb, co2, trace, n2o, ch4, cfc11, cfc12, cfc22, cwc, fcld, ict, icb, reff,

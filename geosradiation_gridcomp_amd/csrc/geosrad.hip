@@ -27,6 +27,7 @@
 #include "lw_kernels.hpp"
 #include "sw_kernels.hpp"
 #include "mcica_kernels.hpp"
+#include "sw_radval_kernels.hpp"
 #include "chou_kernels.hpp"
 #include "sorad_kernels.hpp"
 #include "gridcomp_kernels.hpp"
@@ -590,7 +591,7 @@ struct geosrad_ctx {
     virtual int sw_dev(hipStream_t st, int ncol, int nlay, double scon, double adjes, int isolvar, const void *const *in, int iceflg,
                        int liqflg, int dyofyr, int iaer, int cloudLM, int cloudMH, int normFlx, int32_t *clearCounts, void *const *out,
                        int do_drfband, const void *bndscl, const void *indsolvar, const void *solcycfrac,
-                       void *const *dbg) = 0;
+                       void *const *dbg, void *radval) = 0;
     virtual int lw_driver_dev(hipStream_t st, int ncol, int lm, int nb, const void *const *in, const double *consts, int iceflg,
                               int liqflg, int doy, int lcldlm, int lcldmh, const int32_t *band_output, void *const *out, int nrats,
                               const int32_t *rat_gas, void *const *rat_out) = 0;
@@ -617,7 +618,7 @@ struct geosrad_ctx {
     virtual int sw_host(int ncol, int nlay, double scon, double adjes, int isolvar, const void *const *in, int iceflg, int liqflg,
                         int dyofyr, int iaer, int cloudLM, int cloudMH, int normFlx, int32_t *clearCounts, void *const *out,
                         int do_drfband, const void *bndscl, const void *indsolvar, const void *solcycfrac,
-                       void *const *dbg) = 0;
+                       void *const *dbg, void *radval) = 0;
     virtual int lit_index_dev(hipStream_t st, int ncol, const void *zth, int32_t *idx, int32_t *pos, int32_t *nlit_dev, int *nlit_host) = 0;
     virtual int lit_pack_dev(hipStream_t st, int pdim, int udim, int nlev, const int32_t *idx, const int32_t *nlit_dev, const void *unpacked,
                              void *packed) = 0;
@@ -671,7 +672,7 @@ template <typename R> struct Ctx : geosrad_ctx {
     std::vector<R> avgcyc_mg, avgcyc_sb;          // NRLSSI2 mgavgcyc / sbavgcyc (134 each), host only: isolvar == 1
     SwDev<R> *d_S = nullptr;
     bool have_sw = false;
-    char *d_ws_sw = nullptr; size_t ws_sw_bytes = 0; int ws_sw_ncol = 0, ws_sw_nlay = 0, ws_sw_planes = 0;
+    char *d_ws_sw = nullptr; size_t ws_sw_bytes = 0; int ws_sw_ncol = 0, ws_sw_nlay = 0, ws_sw_planes = 0; bool ws_sw_radval = false;
     // Chou-Suarez SW tables + workspace
     char *d_tab_so = nullptr; size_t tab_so_bytes = 0;
     SoradDev<R> h_O{};
@@ -1963,8 +1964,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 
-    struct WsSw { R *sc; uint32_t *scidx; uint8_t *colcloudy, *laycloudy; int32_t *perm, *nclear; R *alpha, *rcorr, *taucmc, *ssacmc, *asmcmc, *cotsum, *cell, *part, *bsfc, *cot; };
-    size_t ws_layout_sw(int nc, int nlay, WsSw *w, char *base, int planes) const
+    struct WsSw { R *sc; uint32_t *scidx; uint8_t *colcloudy, *laycloudy; int32_t *perm, *nclear; R *alpha, *rcorr, *taucmc, *ssacmc, *asmcmc, *cotsum, *cell, *part, *bsfc, *cot, *rvsum; };
+    size_t ws_layout_sw(int nc, int nlay, WsSw *w, char *base, int planes, bool radval) const
     {
         size_t off = 0;
         auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return base ? base + o : (char *)nullptr; };
@@ -1993,20 +1994,24 @@ template <typename R> struct Ctx : geosrad_ctx {
         p = take((size_t)4 * slots * (nlay + 1) * nc * sizeof(R)); if (w) w->part = (R *)p;
         p = take((size_t)3 * slots * nc * sizeof(R)); if (w) w->bsfc = (R *)p;
         p = take((size_t)8 * 6 * nc * sizeof(R)); if (w) w->cot = (R *)p;
+        // SOLAR_RADVAL layer sums of k_mcica<R, 2, true>, [3][15][20][nc]: only once a geosrad_rrtmg_sw_radval* call asked for them
+        if (w) w->rvsum = nullptr;
+        if (radval) { p = take((size_t)3 * RV_NSUM * RV_NPAR * nc * sizeof(R)); if (w) w->rvsum = (R *)p; }
         return off;
     }
     int sw_planes(bool dbg) const { return (sw_path == 2 && !dbg) ? (sizeof(R) == 4 ? 5 : 15) : 14; }
-    int ensure_ws_sw(int nc, int nlay, int planes)
+    int ensure_ws_sw(int nc, int nlay, int planes, bool radval)
     {
-        if (d_ws_sw && nc <= ws_sw_ncol && nlay == ws_sw_nlay && planes <= ws_sw_planes) return GEOSRAD_OK;
+        if (d_ws_sw && nc <= ws_sw_ncol && nlay == ws_sw_nlay && planes <= ws_sw_planes && (ws_sw_radval || !radval)) return GEOSRAD_OK;
         if (planes < ws_sw_planes) planes = ws_sw_planes;
+        radval = radval || ws_sw_radval;
         const int want = (d_ws_sw && nlay == ws_sw_nlay && nc < ws_sw_ncol) ? ws_sw_ncol : nc;
         if (d_ws_sw) { HIPCHK(hipFree(d_ws_sw)); d_ws_sw = nullptr; ws_sw_bytes = 0; }
-        const size_t need = ws_layout_sw(want, nlay, nullptr, nullptr, planes);
+        const size_t need = ws_layout_sw(want, nlay, nullptr, nullptr, planes, radval);
         hipError_t e = hipMalloc((void **)&d_ws_sw, need);
         if (e != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the SW workspace failed (" + std::to_string(need >> 20) +
                                                          " MiB); lower it with geosrad_set_chunk()");
-        ws_sw_bytes = need; ws_sw_ncol = want; ws_sw_nlay = nlay; ws_sw_planes = planes;
+        ws_sw_bytes = need; ws_sw_ncol = want; ws_sw_nlay = nlay; ws_sw_planes = planes; ws_sw_radval = radval;
         return GEOSRAD_OK;
     }
 
@@ -2114,10 +2119,10 @@ template <typename R> struct Ctx : geosrad_ctx {
     // ---- RRTMG_SW, device pointers -------------------------------------------------------------------------
     int sw_dev(hipStream_t st, int ncol, int nlay, double scon, double adjes, int isolvar, const void *const *in, int iceflg, int liqflg,
                int dyofyr, int iaer, int cloudLM, int cloudMH, int normFlx, int32_t *clearCounts, void *const *out, int do_drfband,
-               const void *bndscl, const void *indsolvar, const void *solcycfrac, void *const *dbg) override
+               const void *bndscl, const void *indsolvar, const void *solcycfrac, void *const *dbg, void *radval) override
     {
         return sw_run(st, ncol, nlay, scon, adjes, isolvar, in, iceflg, liqflg, dyofyr, iaer, cloudLM, cloudMH, normFlx, clearCounts, out,
-                      do_drfband, bndscl, indsolvar, solcycfrac, dbg, nullptr);
+                      do_drfband, bndscl, indsolvar, solcycfrac, dbg, nullptr, radval);
     }
 
     // RRTMG_SW band sweeps: k_sw_reform (lane = (column, unit of g-points); fp32 re-forms the cell optics in its second sweep and parks 12
@@ -2126,10 +2131,13 @@ template <typename R> struct Ctx : geosrad_ctx {
     // GEOSRAD_SW_PATH=bands selects the first mapping, k_sw_bands
     bool sw_reform_on() const { return sw_path == 2; }
 
-    // sw_na_out (SwOutIx order, all of SO_UFLX .. SO_COT0 + 7 non-null) requests an additional pass without the aerosol terms
+    // sw_na_out (SwOutIx order, all of SO_UFLX .. SO_COT0 + 7 non-null) requests an additional pass without the aerosol terms;
+    // radval ((GEOSRAD_RV_COUNT, ncol) device array) requests the SOLAR_RADVAL diagnostics: the RADVAL instantiation of k_mcica, then
+    // k_sw_radval - once per call, they do not depend on the aerosols
     int sw_run(hipStream_t st, int ncol, int nlay, double scon, double adjes, int isolvar, const void *const *in, int iceflg, int liqflg,
                int dyofyr, int iaer, int cloudLM, int cloudMH, int normFlx, int32_t *clearCounts, void *const *out, int do_drfband,
-               const void *bndscl, const void *indsolvar, const void *solcycfrac, void *const *dbg, void *const *sw_na_out)
+               const void *bndscl, const void *indsolvar, const void *solcycfrac, void *const *dbg, void *const *sw_na_out,
+               void *radval = nullptr)
     {
         HIPCHK(hipSetDevice(device));
         if (!have_sw) return fail(GEOSRAD_EINVAL, "RRTMG_SW tables not set: call geosrad_set_tables_sw first (rrtmg_sw_ini)");
@@ -2142,6 +2150,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             if (!in[k] && !((k == S_TAUAER || k == S_SSAAER || k == S_ASMAER) && iaer != 10)) return fail(GEOSRAD_EINVAL, "null input array");
         for (int k = 0; k < SO_DRBAND; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
         if (do_drfband && (!out[SO_DRBAND] || !out[SO_DFBAND])) return fail(GEOSRAD_EINVAL, "do_drfband set but drband/dfband null");
+        if (radval && dbg) return fail(GEOSRAD_EINVAL, "the stage dumps do not produce the SOLAR_RADVAL diagnostics");
         SwSolar<R> SV;
         int rc = sw_solar(scon, adjes, isolvar, (const R *)bndscl, (const R *)indsolvar, (const R *)solcycfrac, SV);
         if (rc) return rc;
@@ -2150,13 +2159,13 @@ template <typename R> struct Ctx : geosrad_ctx {
         const long cap = (long)(0xFFFFFFFFull / ((unsigned long long)nlay * 12ull * sizeof(R))) & ~255L;
         int nc_max = ncol < chunk ? ncol : chunk;
         if ((long)nc_max > cap) nc_max = (int)cap;
-        rc = ensure_ws_sw(nc_max, nlay, sw_planes(dbg != nullptr));
+        rc = ensure_ws_sw(nc_max, nlay, sw_planes(dbg != nullptr), radval != nullptr);
         if (rc) return rc;
 
         for (int c0 = 0; c0 < ncol; c0 += nc_max) {
             const int nc = (ncol - c0) < nc_max ? (ncol - c0) : nc_max;
             WsSw w;
-            ws_layout_sw(nc, nlay, &w, d_ws_sw, ws_sw_planes);
+            ws_layout_sw(nc, nlay, &w, d_ws_sw, ws_sw_planes, ws_sw_radval);
             SwArgs<R> A{};
             A.ncol = nc; A.ld = ncol; A.nlay = nlay; A.iceflg = iceflg; A.liqflg = liqflg; A.doy = dyofyr; A.cloudLM = cloudLM;
             A.cloudMH = cloudMH; A.iaer = iaer; A.normFlx = normFlx; A.do_drfband = do_drfband;
@@ -2197,9 +2206,24 @@ template <typename R> struct Ctx : geosrad_ctx {
                 rc = mc_plan(2, NG_SW, nlay, MP, nseg);
                 if (rc) return rc;
                 span_begin(3, st);
-                hipLaunchKernelGGL((k_mcica<R, 2>), dim3(xcd_grid(nc, 64, nseg)), dim3(64), 0, st, M, MP, (const LwDev<R> *)d_T,
-                                   (const SwDev<R> *)d_S);
+                M.rvsum = w.rvsum;
+                if (radval)
+                    hipLaunchKernelGGL((k_mcica<R, 2, true>), dim3(xcd_grid(nc, 64, nseg)), dim3(64), 0, st, M, MP, (const LwDev<R> *)d_T,
+                                       (const SwDev<R> *)d_S);
+                else
+                    hipLaunchKernelGGL((k_mcica<R, 2>), dim3(xcd_grid(nc, 64, nseg)), dim3(64), 0, st, M, MP, (const LwDev<R> *)d_T,
+                                       (const SwDev<R> *)d_S);
                 span_end(st);
+            }
+            if (radval) {
+                // the sub-columns are summed in the groups of the band sweeps' own cotd?? / cotn?? family (sw_radval_kernels.hpp)
+                SwRvGroups G{};
+                if (sw_reform_on()) {
+                    int sz[RV_NPAR];
+                    G.n = sw_reform_par_units<R>(sz);
+                    for (int k = 0, e = 0; k < G.n; k++) { e += sz[k]; G.end[k] = e; }
+                } else { G.n = 3; G.end[0] = 8; G.end[1] = 14; G.end[2] = 20; }
+                hipLaunchKernelGGL(k_sw_radval<R>, dim3(gx, 4), blk, 0, st, A, h_S, SV, G, (const R *)w.rvsum, (R *)radval + c0);
             }
             if (dbg && dbg[3])       // cldprmc_sw stage dump (6-entry dbg of geosrad_rrtmg_sw_cldprmc)
                 hipLaunchKernelGGL(k_sw_dump_cldprmc<R>, dim3(gx, nlay), blk, 0, st, A, (R *)dbg[3] + (size_t)c0 * NG_SW * nlay,
@@ -2259,10 +2283,11 @@ template <typename R> struct Ctx : geosrad_ctx {
     // ---- RRTMG_SW, host pointers ---------------------------------------------------------------------------
     int sw_host(int ncol, int nlay, double scon, double adjes, int isolvar, const void *const *in, int iceflg, int liqflg, int dyofyr,
                 int iaer, int cloudLM, int cloudMH, int normFlx, int32_t *clearCounts, void *const *out, int do_drfband, const void *bndscl,
-                const void *indsolvar, const void *solcycfrac, void *const *dbg) override
+                const void *indsolvar, const void *solcycfrac, void *const *dbg, void *radval) override
     {
         HIPCHK(hipSetDevice(device));
         if (ncol <= 0 || nlay <= 0) return fail(GEOSRAD_EINVAL, "bad ncol/nlay");
+        if (radval && dbg) return fail(GEOSRAD_EINVAL, "the stage dumps do not produce the SOLAR_RADVAL diagnostics");
         if (!dbg) {
             // production path: pinned staging + chunk pipeline (host_pipeline); the stage-dump test hooks keep the plain path below
             for (int k = 0; k < S_NIN; k++)
@@ -2287,12 +2312,15 @@ template <typename R> struct Ctx : geosrad_ctx {
                 ix_out[k] = (int)arrs.size(); arrs.push_back({nullptr, out[k], rows, E, 0});
             }
             ix_cc = (int)arrs.size(); arrs.push_back({nullptr, clearCounts, 4, sizeof(int32_t), 0});
+            const int ix_rv = radval ? (int)arrs.size() : -1;
+            if (radval) arrs.push_back({nullptr, radval, (size_t)GEOSRAD_RV_COUNT, E, 0});
             auto run = [&](hipStream_t st, int nc, int, char *dev, int) -> int {
                 const void *din[S_NIN]; void *dout[SO_NOUT];
                 for (int k = 0; k < S_NIN; k++) din[k] = ix_in[k] >= 0 ? dev + arrs[ix_in[k]].off : nullptr;
                 for (int k = 0; k < SO_NOUT; k++) dout[k] = ix_out[k] >= 0 ? dev + arrs[ix_out[k]].off : nullptr;
                 return sw_dev(st, nc, nlay, scon, adjes, isolvar, din, iceflg, liqflg, dyofyr, iaer, cloudLM, cloudMH, normFlx,
-                              (int32_t *)(dev + arrs[ix_cc].off), dout, do_drfband, bndscl, indsolvar, solcycfrac, nullptr);
+                              (int32_t *)(dev + arrs[ix_cc].off), dout, do_drfband, bndscl, indsolvar, solcycfrac, nullptr,
+                              ix_rv >= 0 ? dev + arrs[ix_rv].off : nullptr);
             };
             int rc = clear_slot(1);
             if (rc) return rc;
@@ -2332,7 +2360,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         void *ddbg[6] = {d_io + dbgo[0], d_io + dbgo[1], d_io + dbgo[2], nullptr, nullptr, nullptr};
         if (dbg && dbg[3]) for (int k = 3; k < 6; k++) ddbg[k] = d_io + dbgo[k];
         rc = sw_dev(stream, ncol, nlay, scon, adjes, isolvar, din, iceflg, liqflg, dyofyr, iaer, cloudLM, cloudMH, normFlx,
-                    (int32_t *)(d_io + cco), dout, do_drfband, bndscl, indsolvar, solcycfrac, dbg ? ddbg : nullptr);
+                    (int32_t *)(d_io + cco), dout, do_drfband, bndscl, indsolvar, solcycfrac, dbg ? ddbg : nullptr, nullptr);
         if (rc) return rc;
         rc = check(stream, 1);
         if (rc) return rc;
@@ -2850,7 +2878,7 @@ struct MultiCtx final : geosrad_ctx {
     }
     int sw_host(int ncol, int nlay, double scon, double adjes, int isolvar, const void *const *in, int iceflg, int liqflg, int dyofyr,
                 int iaer, int cloudLM, int cloudMH, int normFlx, int32_t *clearCounts, void *const *out, int do_drfband, const void *bndscl,
-                const void *indsolvar, const void *solcycfrac, void *const *dbg) override
+                const void *indsolvar, const void *solcycfrac, void *const *dbg, void *radval) override
     {
         if (dbg) return fail(GEOSRAD_EINVAL, "stage dumps need a single-device context");
         const size_t E = (size_t)real_kind;
@@ -2859,7 +2887,8 @@ struct MultiCtx final : geosrad_ctx {
             for (int j = 0; j < S_NIN; j++) i2[j] = off(in[j], (size_t)c0 * E);
             for (int j = 0; j < SO_NOUT; j++) o2[j] = off(out[j], (size_t)c0 * E);
             return k->sw_host(nc, nlay, scon, adjes, isolvar, i2, iceflg, liqflg, dyofyr, iaer, cloudLM, cloudMH, normFlx,
-                              clearCounts ? clearCounts + c0 : nullptr, o2, do_drfband, bndscl, indsolvar, solcycfrac, nullptr);
+                              clearCounts ? clearCounts + c0 : nullptr, o2, do_drfband, bndscl, indsolvar, solcycfrac, nullptr,
+                              off(radval, (size_t)c0 * E));
         });
     }
     int irrad_host(int m, int np, const void *const *in, double co2, int trace, int ict, int icb, int ns, int na, int nb, void *const *aer,
@@ -2894,7 +2923,7 @@ struct MultiCtx final : geosrad_ctx {
     int sorad_dev(hipStream_t, int, int, int, const void *const *, double, int, int, const void *, const void *, void *const *, int) override { return nodev("geosrad_sorad_dev"); }
     int irrad_dev(hipStream_t, int, int, const void *const *, double, int, int, int, int, int, int, void *const *, void *const *) override { return nodev("geosrad_irrad_dev"); }
     int sw_dev(hipStream_t, int, int, double, double, int, const void *const *, int, int, int, int, int, int, int, int32_t *, void *const *, int,
-               const void *, const void *, const void *, void *const *) override { return nodev("geosrad_rrtmg_sw_dev"); }
+               const void *, const void *, const void *, void *const *, void *) override { return nodev("geosrad_rrtmg_sw_dev"); }
     int lw_driver_dev(hipStream_t, int, int, int, const void *const *, const double *, int, int, int, int, int, const int32_t *, void *const *, int,
                       const int32_t *, void *const *) override { return nodev("geosrad_lw_driver_rrtmg_dev"); }
     int sw_driver_dev(hipStream_t, int, int, int, const void *const *, const double *, int, int, double, double, int, int, int, int, int, int,
@@ -3094,7 +3123,7 @@ int geosrad_rrtmg_sw(geosrad_ctx *c, int rpart, int ncol, int nlay, double scon,
     (void)rpart;
     SW_PACK();
     return c->sw_host(ncol, nlay, scon, adjes, isolvar, in, iceflgsw, liqflgsw, dyofyr, iaer, cloudLM, cloudMH, normFlx, clearCounts, out,
-                      do_drfband, bndscl, indsolvar, solcycfrac, nullptr);
+                      do_drfband, bndscl, indsolvar, solcycfrac, nullptr, nullptr);
 }
 
 int geosrad_rrtmg_sw_dev(geosrad_ctx *c, void *stream, int rpart, int ncol, int nlay, double scon, double adjes, const void *coszen,
@@ -3113,7 +3142,46 @@ int geosrad_rrtmg_sw_dev(geosrad_ctx *c, void *stream, int rpart, int ncol, int 
     (void)rpart;
     SW_PACK();
     return c->sw_dev((hipStream_t)stream, ncol, nlay, scon, adjes, isolvar, in, iceflgsw, liqflgsw, dyofyr, iaer, cloudLM, cloudMH, normFlx,
-                     clearCounts, out, do_drfband, bndscl, indsolvar, solcycfrac, nullptr);
+                     clearCounts, out, do_drfband, bndscl, indsolvar, solcycfrac, nullptr, nullptr);
+}
+
+int geosrad_rrtmg_sw_radval(geosrad_ctx *c, int rpart, int ncol, int nlay, double scon, double adjes, const void *coszen, int isolvar,
+                            const void *play, const void *plev, const void *tlay, const void *h2ovmr, const void *o3vmr,
+                            const void *co2vmr, const void *ch4vmr, const void *o2vmr, int iceflgsw, int liqflgsw, const void *cld,
+                            const void *ciwp, const void *clwp, const void *rei, const void *rel, int dyofyr, const void *zm,
+                            const void *alat, int iaer, const void *tauaer, const void *ssaaer, const void *asmaer, const void *asdir,
+                            const void *asdif, const void *aldir, const void *aldif, int cloudLM, int cloudMH, int normFlx,
+                            int32_t *clearCounts, void *swuflx, void *swdflx, void *swuflxc, void *swdflxc, void *nirr, void *nirf,
+                            void *parr, void *parf, void *uvrr, void *uvrf, void *fswband, void *cotdtp, void *cotdhp, void *cotdmp,
+                            void *cotdlp, void *cotntp, void *cotnhp, void *cotnmp, void *cotnlp, int do_drfband, void *drband,
+                            void *dfband, const void *bndscl, const void *indsolvar, const void *solcycfrac, void *radval)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    if (!radval) return c->fail(GEOSRAD_EINVAL, "geosrad_rrtmg_sw_radval: null radval array");
+    (void)rpart;
+    SW_PACK();
+    return c->sw_host(ncol, nlay, scon, adjes, isolvar, in, iceflgsw, liqflgsw, dyofyr, iaer, cloudLM, cloudMH, normFlx, clearCounts, out,
+                      do_drfband, bndscl, indsolvar, solcycfrac, nullptr, radval);
+}
+
+int geosrad_rrtmg_sw_radval_dev(geosrad_ctx *c, void *stream, int rpart, int ncol, int nlay, double scon, double adjes,
+                                const void *coszen, int isolvar, const void *play, const void *plev, const void *tlay,
+                                const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *o2vmr,
+                                int iceflgsw, int liqflgsw, const void *cld, const void *ciwp, const void *clwp, const void *rei,
+                                const void *rel, int dyofyr, const void *zm, const void *alat, int iaer, const void *tauaer,
+                                const void *ssaaer, const void *asmaer, const void *asdir, const void *asdif, const void *aldir,
+                                const void *aldif, int cloudLM, int cloudMH, int normFlx, int32_t *clearCounts, void *swuflx,
+                                void *swdflx, void *swuflxc, void *swdflxc, void *nirr, void *nirf, void *parr, void *parf, void *uvrr,
+                                void *uvrf, void *fswband, void *cotdtp, void *cotdhp, void *cotdmp, void *cotdlp, void *cotntp,
+                                void *cotnhp, void *cotnmp, void *cotnlp, int do_drfband, void *drband, void *dfband,
+                                const void *bndscl, const void *indsolvar, const void *solcycfrac, void *radval)
+{
+    if (!c || !clearCounts) return GEOSRAD_EINVAL;
+    if (!radval) return c->fail(GEOSRAD_EINVAL, "geosrad_rrtmg_sw_radval_dev: null radval array");
+    (void)rpart;
+    SW_PACK();
+    return c->sw_dev((hipStream_t)stream, ncol, nlay, scon, adjes, isolvar, in, iceflgsw, liqflgsw, dyofyr, iaer, cloudLM, cloudMH, normFlx,
+                     clearCounts, out, do_drfband, bndscl, indsolvar, solcycfrac, nullptr, radval);
 }
 
 int geosrad_rrtmg_sw_taumol(geosrad_ctx *c, int ncol, int nlay, double scon, int isolvar, const void *play, const void *plev,
@@ -3142,7 +3210,7 @@ int geosrad_rrtmg_sw_taumol(geosrad_ctx *c, int ncol, int nlay, double scon, int
          *cotnmp = q + 6 * cn, *cotnlp = q + 7 * cn, *drband = nullptr, *dfband = nullptr;
     SW_PACK();
     void *dbg[6] = {taug, taur, ssi, nullptr, nullptr, nullptr};
-    return c->sw_host(ncol, nlay, scon, 1.0, isolvar, in, 3, 1, 1, 0, 1, 2, 0, cc.data(), out, 0, bndscl, indsolvar, solcycfrac, dbg);
+    return c->sw_host(ncol, nlay, scon, 1.0, isolvar, in, 3, 1, 1, 0, 1, 2, 0, cc.data(), out, 0, bndscl, indsolvar, solcycfrac, dbg, nullptr);
 }
 
 int geosrad_rrtmg_sw_cldprmc(geosrad_ctx *c, int ncol, int nlay, const void *play, const void *plev, const void *tlay, const void *h2ovmr,
@@ -3169,7 +3237,7 @@ int geosrad_rrtmg_sw_cldprmc(geosrad_ctx *c, int ncol, int nlay, const void *pla
     q += 8 * cn;
     SW_PACK();
     void *dbg[6] = {q, q + cg, q + 2 * cg, taucmc, ssacmc, asmcmc};
-    return c->sw_host(ncol, nlay, 1361.0, 1.0, 0, in, iceflgsw, liqflgsw, dyofyr, 0, cloudLM, cloudMH, 0, cc.data(), out, 0, nullptr, nullptr, nullptr, dbg);
+    return c->sw_host(ncol, nlay, 1361.0, 1.0, 0, in, iceflgsw, liqflgsw, dyofyr, 0, cloudLM, cloudMH, 0, cc.data(), out, 0, nullptr, nullptr, nullptr, dbg, nullptr);
 }
 
 int geosrad_set_tables_chou_lw(geosrad_ctx *c, const void *blob, size_t n) { return c ? c->set_tables_chou_lw(blob, n) : GEOSRAD_EINVAL; }

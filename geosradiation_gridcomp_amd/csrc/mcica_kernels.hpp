@@ -323,6 +323,40 @@ GR_DEV void sw_cloud_optics(const SwCldCoef<R> &c, int iceflag, R ciwp, R clwp, 
         asmc = (scatliq * (gliq - forwliq) / ((R)1. - forwliq) + scatice * (gice - forwice) / ((R)1. - forwice)) / (scatliq + scatice);
 }
 
+// SOLAR_RADVAL sibling of sw_cloud_optics: the per-phase values the reference keeps beside the combined ones
+// (SW/rrtmg_sw_cldprmc.F90:321-351): un-scaled ?taormc / ?omormc / ?asormc, delta-scaled ?taucmc / ?omgcmc / ?asycmc and the
+// forward-scattering fraction forw?, of one phase (ext, ssa, g, forw: that phase's coefficients; wp: its water path).  A phase
+// without condensate enters with zero coefficients, as there.
+template <typename R> struct SwCldPhase { R taor, omor, asor, tauc, omgc, asyc, forw; };
+
+template <typename R>
+GR_DEV SwCldPhase<R> sw_cloud_phase(R extco, R ssaco, R g, R forw, R wp)
+{
+    const bool on = wp != 0;
+    const R e = on ? extco : (R)0, w = on ? ssaco : (R)0, gg = on ? g : (R)0, f = on ? forw : (R)0;
+    SwCldPhase<R> p;
+    p.taor = wp * e; p.omor = w; p.asor = gg;
+    p.omgc = w * ((R)1. - f) / ((R)1. - f * w);
+    p.tauc = ((R)1. - f * w) * p.taor;
+    p.asyc = (gg - f) / ((R)1. - f);
+    p.forw = f;
+    return p;
+}
+
+// the 15 layer sums per (super-layer, PAR sub-column) the SOLAR_RADVAL diagnostics are made of (SW/rrtmg_sw_spcvmc.F90:804-870):
+//   0            sum(taucmc)
+//   1 .. 7       liquid: sum(tau), sum(tau om), sum(tau om as) un-scaled; sum(tau), sum(tau om), sum(tau om asy), sum(tau om forw) scaled
+//   8 .. 14      ice, likewise
+constexpr int RV_NSUM = 15, RV_NPAR = 20, RV_G0 = 66;      // PAR sub-columns: the g-points of bands 24-26, 0-based 66 .. 85
+template <typename R> GR_DEV void rv_add_phase(R *a, const SwCldPhase<R> &p)
+{
+    const R so = p.taor * p.omor, ss = p.tauc * p.omgc;
+    // the optical thickness sums add the ROUNDED cell values, as the reference sums its stored ?taormc / ?taucmc arrays - and as cotsum
+    // does with taormc: un-fused adds, or the multiply that forms the cell value would be contracted into them
+    a[0] = nf_add(a[0], p.taor); a[1] += so; a[2] += so * p.asor;
+    a[3] = nf_add(a[3], p.tauc); a[4] += ss; a[5] += ss * p.asyc; a[6] += ss * p.forw;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // k_mcica: one thread per (column, segment of <= 4 consecutive sub-columns of one band).
 // The reference draws one KISS stream per column, sequentially over (sub-column, layer): per sub-column 2*nlay numbers
@@ -338,6 +372,9 @@ GR_DEV void sw_cloud_optics(const SwCldCoef<R> &c, int iceflag, R ciwp, R clwp, 
 //   MODE 1 (stand-alone generator API): quads of sub-columns; writes cldy/ciwp_stoch/clwp_stoch Fortran (nlay,nsubcol,ncol).
 //   MODE 2 (RRTMG_SW): quads of the 14 bands' g-points; fused generator + clearCounts + cldprmc_sw: writes
 //          taucmc / ssacmc / asmcmc planes and the PAR bands' super-layer sums of the un-scaled tau (cotsum).
+//          RADVAL (the reference's SOLAR_RADVAL build): the PAR bands' threads also form the 15 phase-split layer sums per super-layer
+//          (rv_add_phase) - accumulated for the super-layer the walk is in and flushed to rvsum [3][15][20][ncol] when it leaves it, so 15
+//          sums per sub-column are live, not 45.  The other instantiations compile as if the parameter did not exist.
 // ---------------------------------------------------------------------------------------------------
 constexpr int MC_S = 4;      // sub-columns per thread
 struct McSegDev { int start, count, band, pad; KissJump j; };      // j: jump to sub-column `start` (unused when start == 0)
@@ -354,12 +391,14 @@ template <typename R> struct McArgs {
     // MODE 0
     R *taucmc; uint8_t *laycloudy; int32_t *clearCounts; uint32_t *err;
     // MODE 1
-    int32_t *cldy; R *ciwp_s, *clwp_s;
+    // (k_mcica<R, 2, true> finds its extra output in the place of ciwp_s: the kernel arguments, and with them the instruction stream
+    // of the other instantiations, stay what they were)
+    int32_t *cldy; union { R *ciwp_s; R *rvsum; /* RADVAL: [3][RV_NSUM][RV_NPAR][ncol] */ }; R *clwp_s;
     // MODE 2
     R *ssacmc, *asmcmc, *cotsum;
 };
 
-template <typename R, int MODE>
+template <typename R, int MODE, bool RADVAL = false>
 __global__ void __launch_bounds__(64) k_mcica(McArgs<R> M, McPlan P, const LwDev<R> *__restrict__ Tp, const SwDev<R> *__restrict__ Sp)
 {
     // one-dimensional grid (lw_kernels.hpp band_block): the segments of a 64-column block are consecutive blocks of one XCD, so the
@@ -409,6 +448,31 @@ __global__ void __launch_bounds__(64) k_mcica(McArgs<R> M, McPlan P, const LwDev
     for (int s = 0; s < MC_S; s++) { cprev[s] = 0; c3prev[s] = 0; cs_lo[s] = 0; cs_mid[s] = 0; cs_hi[s] = 0; }
     uint32_t any_all = 0, any_hi = 0, any_mid = 0, any_lo = 0;      // bit s: sub-column s has a cloudy cell (in the super-layer)
     uint32_t err = 0;
+    // RADVAL: sums of the super-layer the walk is in (0 low, 1 mid, 2 high); rv_flush parks them and starts the next one
+    const bool rv_on = RADVAL && MODE == 2 && ib >= 24 && ib <= 26;
+    static_assert(!RADVAL || MODE == 2, "rvsum shares its place in McArgs with MODE 1's ciwp_s: the RADVAL sums exist in MODE 2 only");
+    R rv[RADVAL ? MC_S : 1][RV_NSUM];
+    int rv_cur = 0;
+    if constexpr (RADVAL) {
+#pragma unroll
+        for (int s = 0; s < MC_S; s++)
+#pragma unroll
+            for (int q = 0; q < RV_NSUM; q++) rv[s][q] = 0;
+    }
+    auto rv_flush = [&]() {
+        if constexpr (RADVAL) {
+#pragma unroll
+            for (int s = 0; s < MC_S; s++) {
+                if (s >= ns) continue;
+#pragma unroll
+                for (int q = 0; q < RV_NSUM; q++) {
+                    M.rvsum[((size_t)(rv_cur * RV_NSUM + q) * RV_NPAR + (s0 + s - RV_G0)) * n + col] = rv[s][q];
+                    rv[s][q] = 0;
+                }
+            }
+        }
+        rv_cur++;
+    };
 
     // The walk ends above the highest layer in which a column of the wave has cloud fraction: the reference walks on to the top
     // (the streams are consumed for every layer), but a layer without cloud fraction is clear in every sub-column whatever is drawn,
@@ -432,6 +496,10 @@ __global__ void __launch_bounds__(64) k_mcica(McArgs<R> M, McPlan P, const LwDev
         const R thr = nf_sub((R)1., cf);
         const R sigma = cf > (R)0.99 ? (R)0.5 : (cf > (R)0.9 ? (R)0.71 : (R)1.0);
         const bool in_hi = il >= hi0 && il <= hi1, in_mid = il >= mi0 && il <= mi1, in_lo = il >= lo0 && il <= lo1;
+        if (RADVAL && rv_on) {
+            const int sl = il < M.cloudLM ? 0 : (il < M.cloudMH ? 1 : 2);      // the super-layers of cotsum below
+            while (rv_cur < sl) rv_flush();
+        }
         // the draws of the segment's sub-columns first; then, if any sub-column of any column of the wave is cloudy here, the
         // condensate scaling factors of all of them together (four table values each) - not one look-up per cloudy sub-column
         // inside a per-lane branch, where each would wait for the one before
@@ -513,12 +581,21 @@ __global__ void __launch_bounds__(64) k_mcica(McArgs<R> M, McPlan P, const LwDev
                 }
                 // super-layer sums of the un-scaled tau for the PAR diagnostics (SW/rrtmg_sw_spcvmc.F90:760-800)
                 if (il < M.cloudLM) cs_lo[s] += taor; else if (il < M.cloudMH) cs_mid[s] += taor; else cs_hi[s] += taor;
+                if (RADVAL && rv_on && c) {
+                    R *const a = rv[RADVAL ? s : 0];
+                    a[0] += tauc;
+                    rv_add_phase<R>(a + 1, sw_cloud_phase<R>(swc.extcoliq, swc.ssacoliq, swc.gliq, swc.forwliq, cl));
+                    rv_add_phase<R>(a + 8, sw_cloud_phase<R>(swc.extcoice, swc.ssacoice, swc.gice, swc.forwice, ci));
+                }
             } else {
                 const size_t o = ((size_t)col * M.nsubcol + (s0 + s)) * nlay + il;
+                // (ciwp_s is MODE 1's alone: in MODE 2 the same place of McArgs holds rvsum, see the static_assert above)
                 M.cldy[o] = c ? 1 : 0; M.ciwp_s[o] = ci; M.clwp_s[o] = cl;
             }
         }
     }
+    if (RADVAL && rv_on)
+        while (rv_cur < 3) rv_flush();      // the super-layers the walk did not reach get zeros
     if (MODE == 2 && ib >= 24 && ib <= 26) {
 #pragma unroll
         for (int s = 0; s < MC_S; s++) {

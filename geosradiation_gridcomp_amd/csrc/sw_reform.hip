@@ -16,6 +16,14 @@ template <typename R> hipError_t sw_reform_launch(hipStream_t st, const SwArgs<R
 
 template <typename R> int sw_reform_nslot() { return swr_nslot<R>; }
 
+template <typename R> int sw_reform_par_units(int *sizes)
+{
+    int k = 0;
+    for (int jb = 24; jb <= 26; jb++)
+        for (int u = 0; u < swr_nunit(swr_u<R>, sw_band_ng(jb)); u++) sizes[k++] = swr_usize(swr_u<R>, sw_band_ng(jb), u);
+    return k;
+}
+
 template <typename R> hipError_t sw_reform_reduce(hipStream_t st, const SwArgs<R> &A, const SwOut<R> &O)
 {
     hipLaunchKernelGGL(k_swr_reduce<R>, dim3((unsigned)((A.ncol + 255) / 256), A.nlay + 2), dim3(256), 0, st, A, O);
@@ -26,11 +34,13 @@ template <typename R> hipError_t sw_reform_reduce(hipStream_t st, const SwArgs<R
 template hipError_t sw_reform_launch<float>(hipStream_t, const SwArgs<float> &, const SwDev<float> &, const SwSolar<float> &);
 template hipError_t sw_reform_reduce<float>(hipStream_t, const SwArgs<float> &, const SwOut<float> &);
 template int sw_reform_nslot<float>();
+template int sw_reform_par_units<float>(int *);
 #endif
 #if !defined(GEOSRAD_PART) || GEOSRAD_PART == 8
 template hipError_t sw_reform_launch<double>(hipStream_t, const SwArgs<double> &, const SwDev<double> &, const SwSolar<double> &);
 template hipError_t sw_reform_reduce<double>(hipStream_t, const SwArgs<double> &, const SwOut<double> &);
 template int sw_reform_nslot<double>();
+template int sw_reform_par_units<double>(int *);
 #endif
 
 }  // namespace geosrad

@@ -81,6 +81,9 @@ GR_DEV void swr_body(const SwArgs<R> &A, const SwDev<R> &T, const SwSolar<R> &SV
     else { albp = (ldg(A.asdir, cba) + ldg(A.aldir, cba)) / (R)2.; albd = (ldg(A.asdif, cba) + ldg(A.aldif, cba)) / (R)2.; }
 
     // ---- solar source of the band's g-points (taumolNN tail sections) -----------------------------------
+    // (this section exists three times, statement for statement: sw_kernels.hpp sw_band_body, sw_reform_kernels.hpp swr_body and
+    // sw_radval_kernels.hpp sw_solar_weights, whose PAR weights must be these - one shared device function changes the band kernels' instruction
+    // stream, so an edit here goes to all three)
     R zinc[NG];          // adjflux * ssi (without the cosine)
     {
         int js = 1; R fs = 0;

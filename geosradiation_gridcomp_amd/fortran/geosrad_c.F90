@@ -5,7 +5,7 @@ module geosrad_c
    use iso_fortran_env, only : error_unit
    implicit none
    private
-   public :: geosrad_ctx_handle, geosrad_fail, geosrad_warn, geosrad_data_path, geosrad_load_tables_sw, geosrad_rrtmg_sw, geosrad_load_tables_chou_lw, geosrad_load_tables_chou_sw, geosrad_irrad, geosrad_sorad
+   public :: geosrad_ctx_handle, geosrad_fail, geosrad_warn, geosrad_data_path, geosrad_load_tables_sw, geosrad_rrtmg_sw, geosrad_rrtmg_sw_radval, geosrad_load_tables_chou_lw, geosrad_load_tables_chou_sw, geosrad_irrad, geosrad_sorad
    public :: geosrad_create, geosrad_destroy, geosrad_last_error, geosrad_load_tables_lw, geosrad_load_inhomogeneity
    public :: geosrad_set_corr_lengths, geosrad_rrtmg_lw, geosrad_mcica, geosrad_clearcounts, geosrad_read_table
    public :: geosrad_set_overcast, geosrad_get_overcast, GEOSRAD_OVERCAST_IRRAD, GEOSRAD_OVERCAST_SORAD
@@ -46,6 +46,23 @@ module geosrad_c
             tauaer, ssaaer, asmaer, asdir, asdif, aldir, aldif, clearCounts, swuflx, swdflx, swuflxc, swdflxc, nirr, nirf, parr, &
             parf, uvrr, uvrf, fswband, cotdtp, cotdhp, cotdmp, cotdlp, cotntp, cotnhp, cotnmp, cotnlp, drband, dfband, bndscl, indsolvar, &
             solcycfrac
+      end function
+      ! rrtmg_sw of a -DSOLAR_RADVAL build: the same arguments plus radval, reals (ncol, 120), the dummies cdsdtp .. forinlp of
+      ! rrtmg_sw_rad.F90:86-119 in that order (include/geosrad.h GEOSRAD_RV_*)
+      integer(c_int) function geosrad_rrtmg_sw_radval(ctx, rpart, ncol, nlay, scon, adjes, coszen, isolvar, play, plev, tlay, &
+            h2ovmr, o3vmr, co2vmr, ch4vmr, o2vmr, iceflgsw, liqflgsw, cld, ciwp, clwp, rei, rel, dyofyr, zm, alat, &
+            iaer, tauaer, ssaaer, asmaer, asdir, asdif, aldir, aldif, cloudLM, cloudMH, normFlx, clearCounts, &
+            swuflx, swdflx, swuflxc, swdflxc, nirr, nirf, parr, parf, uvrr, uvrf, fswband, &
+            cotdtp, cotdhp, cotdmp, cotdlp, cotntp, cotnhp, cotnmp, cotnlp, do_drfband, drband, dfband, bndscl, indsolvar, &
+            solcycfrac, radval) bind(C, name='geosrad_rrtmg_sw_radval')
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: rpart, ncol, nlay, isolvar, iceflgsw, liqflgsw, dyofyr, iaer, cloudLM, cloudMH, normFlx, do_drfband
+         real(c_double), value :: scon, adjes
+         type(c_ptr), value :: coszen, play, plev, tlay, h2ovmr, o3vmr, co2vmr, ch4vmr, o2vmr, cld, ciwp, clwp, rei, rel, zm, alat, &
+            tauaer, ssaaer, asmaer, asdir, asdif, aldir, aldif, clearCounts, swuflx, swdflx, swuflxc, swdflxc, nirr, nirf, parr, &
+            parf, uvrr, uvrf, fswband, cotdtp, cotdhp, cotdmp, cotdlp, cotntp, cotnhp, cotnmp, cotnlp, drband, dfband, bndscl, indsolvar, &
+            solcycfrac, radval
       end function
       integer(c_int) function geosrad_load_tables_chou_lw(ctx, path) bind(C, name='geosrad_load_tables_chou_lw')
          import :: c_int, c_ptr, c_char

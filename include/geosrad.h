@@ -7,6 +7,7 @@
  *                                    GEOSirrad_GridComp/RRTMG/rrtmg_lw/gcm_model/src/rrtmg_lw_rad.F90:15-23,110-201
  *   geosrad_set_tables_lw         <- rrtmg_lw_init::rrtmg_lw_ini           .../src/rrtmg_lw_init.F90:22
  *   geosrad_rrtmg_sw[_dev]        <- rrtmg_sw_rad::rrtmg_sw
+ *   geosrad_rrtmg_sw_radval[_dev] <- rrtmg_sw_rad::rrtmg_sw built with -DSOLAR_RADVAL
  *                                    GEOSsolar_GridComp/RRTMG/rrtmg_sw/gcm_model/src/rrtmg_sw_rad.F90:68-124
  *   geosrad_set_tables_sw         <- rrtmg_sw_init::rrtmg_sw_ini           .../src/rrtmg_sw_init.F90:23
  *   geosrad_irrad[_dev]           <- irradmod::irrad                       GEOSirrad_GridComp/irrad.F90:27-35
@@ -223,6 +224,77 @@ int geosrad_rrtmg_sw_dev(geosrad_ctx *ctx, void *stream, int rpart, int ncol, in
                          void *cotntp, void *cotnhp, void *cotnmp, void *cotnlp,
                          int do_drfband, void *drband, void *dfband, const void *bndscl, const void *indsolvar,
                          const void *solcycfrac);
+/* ---- RRTMG_SW, SOLAR_RADVAL build ----------------------------------------------------------------------
+ * rrtmg_sw as the reference compiles it with -DSOLAR_RADVAL (GEOSsolar_GridComp/CMakeLists.txt:18-21): the cloud-optics
+ * validation diagnostics of the PAR super-band, the dummy arguments cdsdtp .. forinlp of SW/rrtmg_sw_rad.F90:86-119
+ * (declared :300 on), which spcvmc_sw accumulates beside cotd?? / cotn?? (SW/rrtmg_sw_spcvmc.F90:676-746, :749-1109) from the
+ * phase-split cloud optics of cldprmc_sw (SW/rrtmg_sw_cldprmc.F90:321-351, :394-410).  15 families, each a denominator `d` and a
+ * numerator `n` for the whole column (tp) and the high, middle and low pressure super-layers (hp, mp, lp):
+ *   cds            combined liquid + ice, delta-scaled optical thickness (cot?? is its un-scaled twin)
+ *   cotl cdsl coti cdsi   optical thickness of the liquid / ice phase, un-scaled (cot) / delta-scaled (cds)
+ *   ssal sdsl ssai sdsi   single-scattering albedo                    asml adsl asmi adsi   asymmetry parameter
+ *   forl fori             forward-scattering fraction (delta-scaled)
+ * The two entry points below are geosrad_rrtmg_sw / geosrad_rrtmg_sw_dev (same arguments, same results for every one of them) plus
+ * `radval`: reals (ncol, GEOSRAD_RV_COUNT), column fastest, slot k = the k-th of those dummy arguments in the reference's order
+ * (enum below); host pointer for geosrad_rrtmg_sw_radval (it takes the chunked pipeline and the shards of a geosrad_create_multi
+ * context like every other output), device pointer for geosrad_rrtmg_sw_radval_dev.  Cloud-free columns get zeros
+ * (rrtmg_sw_rad.F90:1540-1590), cloudy ones the sums (:1658-1720).  normFlx does not touch these outputs: the reference divides the
+ * fluxes and band fluxes only (:1769-1798).  The 20 PAR sub-columns are summed in the groups in which the band sweeps sum their own
+ * cotd?? / cotn?? family (k_sw_reform: its units of g-points; GEOSRAD_SW_PATH=bands: the three bands), not strictly in g-point order: a family
+ * that coincides with cot?? (cotl?? of a liquid-only column) then has its bits, and the 120 values may differ in the last bits between the
+ * two GEOSRAD_SW_PATH values and from the reference's sequential sum (measured 3.7e-7 relative in fp32).  The sums are formed once per call whatever iaer is (they do not depend on the aerosols);
+ * the workspace they need (3.6 KB per column in fp32) is taken at the first such call and reported by geosrad_workspace_bytes. */
+enum {
+    GEOSRAD_RV_CDSDTP, GEOSRAD_RV_CDSDHP, GEOSRAD_RV_CDSDMP, GEOSRAD_RV_CDSDLP, GEOSRAD_RV_CDSNTP, GEOSRAD_RV_CDSNHP, GEOSRAD_RV_CDSNMP, GEOSRAD_RV_CDSNLP,
+    GEOSRAD_RV_COTLDTP, GEOSRAD_RV_COTLDHP, GEOSRAD_RV_COTLDMP, GEOSRAD_RV_COTLDLP, GEOSRAD_RV_COTLNTP, GEOSRAD_RV_COTLNHP, GEOSRAD_RV_COTLNMP, GEOSRAD_RV_COTLNLP,
+    GEOSRAD_RV_CDSLDTP, GEOSRAD_RV_CDSLDHP, GEOSRAD_RV_CDSLDMP, GEOSRAD_RV_CDSLDLP, GEOSRAD_RV_CDSLNTP, GEOSRAD_RV_CDSLNHP, GEOSRAD_RV_CDSLNMP, GEOSRAD_RV_CDSLNLP,
+    GEOSRAD_RV_COTIDTP, GEOSRAD_RV_COTIDHP, GEOSRAD_RV_COTIDMP, GEOSRAD_RV_COTIDLP, GEOSRAD_RV_COTINTP, GEOSRAD_RV_COTINHP, GEOSRAD_RV_COTINMP, GEOSRAD_RV_COTINLP,
+    GEOSRAD_RV_CDSIDTP, GEOSRAD_RV_CDSIDHP, GEOSRAD_RV_CDSIDMP, GEOSRAD_RV_CDSIDLP, GEOSRAD_RV_CDSINTP, GEOSRAD_RV_CDSINHP, GEOSRAD_RV_CDSINMP, GEOSRAD_RV_CDSINLP,
+    GEOSRAD_RV_SSALDTP, GEOSRAD_RV_SSALDHP, GEOSRAD_RV_SSALDMP, GEOSRAD_RV_SSALDLP, GEOSRAD_RV_SSALNTP, GEOSRAD_RV_SSALNHP, GEOSRAD_RV_SSALNMP, GEOSRAD_RV_SSALNLP,
+    GEOSRAD_RV_SDSLDTP, GEOSRAD_RV_SDSLDHP, GEOSRAD_RV_SDSLDMP, GEOSRAD_RV_SDSLDLP, GEOSRAD_RV_SDSLNTP, GEOSRAD_RV_SDSLNHP, GEOSRAD_RV_SDSLNMP, GEOSRAD_RV_SDSLNLP,
+    GEOSRAD_RV_SSAIDTP, GEOSRAD_RV_SSAIDHP, GEOSRAD_RV_SSAIDMP, GEOSRAD_RV_SSAIDLP, GEOSRAD_RV_SSAINTP, GEOSRAD_RV_SSAINHP, GEOSRAD_RV_SSAINMP, GEOSRAD_RV_SSAINLP,
+    GEOSRAD_RV_SDSIDTP, GEOSRAD_RV_SDSIDHP, GEOSRAD_RV_SDSIDMP, GEOSRAD_RV_SDSIDLP, GEOSRAD_RV_SDSINTP, GEOSRAD_RV_SDSINHP, GEOSRAD_RV_SDSINMP, GEOSRAD_RV_SDSINLP,
+    GEOSRAD_RV_ASMLDTP, GEOSRAD_RV_ASMLDHP, GEOSRAD_RV_ASMLDMP, GEOSRAD_RV_ASMLDLP, GEOSRAD_RV_ASMLNTP, GEOSRAD_RV_ASMLNHP, GEOSRAD_RV_ASMLNMP, GEOSRAD_RV_ASMLNLP,
+    GEOSRAD_RV_ADSLDTP, GEOSRAD_RV_ADSLDHP, GEOSRAD_RV_ADSLDMP, GEOSRAD_RV_ADSLDLP, GEOSRAD_RV_ADSLNTP, GEOSRAD_RV_ADSLNHP, GEOSRAD_RV_ADSLNMP, GEOSRAD_RV_ADSLNLP,
+    GEOSRAD_RV_ASMIDTP, GEOSRAD_RV_ASMIDHP, GEOSRAD_RV_ASMIDMP, GEOSRAD_RV_ASMIDLP, GEOSRAD_RV_ASMINTP, GEOSRAD_RV_ASMINHP, GEOSRAD_RV_ASMINMP, GEOSRAD_RV_ASMINLP,
+    GEOSRAD_RV_ADSIDTP, GEOSRAD_RV_ADSIDHP, GEOSRAD_RV_ADSIDMP, GEOSRAD_RV_ADSIDLP, GEOSRAD_RV_ADSINTP, GEOSRAD_RV_ADSINHP, GEOSRAD_RV_ADSINMP, GEOSRAD_RV_ADSINLP,
+    GEOSRAD_RV_FORLDTP, GEOSRAD_RV_FORLDHP, GEOSRAD_RV_FORLDMP, GEOSRAD_RV_FORLDLP, GEOSRAD_RV_FORLNTP, GEOSRAD_RV_FORLNHP, GEOSRAD_RV_FORLNMP, GEOSRAD_RV_FORLNLP,
+    GEOSRAD_RV_FORIDTP, GEOSRAD_RV_FORIDHP, GEOSRAD_RV_FORIDMP, GEOSRAD_RV_FORIDLP, GEOSRAD_RV_FORINTP, GEOSRAD_RV_FORINHP, GEOSRAD_RV_FORINMP, GEOSRAD_RV_FORINLP,
+    GEOSRAD_RV_COUNT
+};
+int geosrad_rrtmg_sw_radval(geosrad_ctx *ctx, int rpart, int ncol, int nlay, double scon, double adjes,
+                            const void *coszen, int isolvar,
+                            const void *play, const void *plev, const void *tlay,
+                            const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *o2vmr,
+                            int iceflgsw, int liqflgsw,
+                            const void *cld, const void *ciwp, const void *clwp, const void *rei, const void *rel,
+                            int dyofyr, const void *zm, const void *alat,
+                            int iaer, const void *tauaer, const void *ssaaer, const void *asmaer,
+                            const void *asdir, const void *asdif, const void *aldir, const void *aldif,
+                            int cloudLM, int cloudMH, int normFlx,
+                            int32_t *clearCounts, void *swuflx, void *swdflx, void *swuflxc, void *swdflxc,
+                            void *nirr, void *nirf, void *parr, void *parf, void *uvrr, void *uvrf, void *fswband,
+                            void *cotdtp, void *cotdhp, void *cotdmp, void *cotdlp,
+                            void *cotntp, void *cotnhp, void *cotnmp, void *cotnlp,
+                            int do_drfband, void *drband, void *dfband, const void *bndscl, const void *indsolvar,
+                            const void *solcycfrac, void *radval);
+/* same, DEVICE pointers (radval included), asynchronous on `stream` */
+int geosrad_rrtmg_sw_radval_dev(geosrad_ctx *ctx, void *stream, int rpart, int ncol, int nlay, double scon, double adjes,
+                                const void *coszen, int isolvar,
+                                const void *play, const void *plev, const void *tlay,
+                                const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *o2vmr,
+                                int iceflgsw, int liqflgsw,
+                                const void *cld, const void *ciwp, const void *clwp, const void *rei, const void *rel,
+                                int dyofyr, const void *zm, const void *alat,
+                                int iaer, const void *tauaer, const void *ssaaer, const void *asmaer,
+                                const void *asdir, const void *asdif, const void *aldir, const void *aldif,
+                                int cloudLM, int cloudMH, int normFlx,
+                                int32_t *clearCounts, void *swuflx, void *swdflx, void *swuflxc, void *swdflxc,
+                                void *nirr, void *nirf, void *parr, void *parf, void *uvrr, void *uvrf, void *fswband,
+                                void *cotdtp, void *cotdhp, void *cotdmp, void *cotdlp,
+                                void *cotntp, void *cotnhp, void *cotnmp, void *cotnlp,
+                                int do_drfband, void *drband, void *dfband, const void *bndscl, const void *indsolvar,
+                                const void *solcycfrac, void *radval);
 /* Debug / test hook: taug, taur Fortran (nlay,112,ncol) and the solar source ssi (112,ncol) [sfluxzen when
  * isolvar < 0] as the reference's taumol_sw leaves them (SW/rrtmg_sw_taumol.F90:27); host pointers. */
 int geosrad_rrtmg_sw_taumol(geosrad_ctx *ctx, int ncol, int nlay, double scon, int isolvar,
