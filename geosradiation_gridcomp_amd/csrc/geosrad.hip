@@ -23,6 +23,7 @@
 #include <cstddef>
 #include <cstdint>
 #include "../../include/geosrad.h"
+#include "dev_buf.hpp"
 #include "lw_device.hpp"
 #include "lw_kernels.hpp"
 #include "sw_kernels.hpp"
@@ -388,8 +389,8 @@ struct geosrad_ctx {
     static constexpr int PIPE_SLOTS = 3, PIPE_LAG = 2;
     static constexpr int PIPE_FLAGGED = -77;      // host_pipeline: a chunk came back with the device error word set (the caller's check() names it)
     char *pipe_pin[PIPE_SLOTS][2] = {};      // [slot][0 = to the device, 1 = from the device]
-    char *pipe_dev[PIPE_SLOTS] = {};
-    size_t pipe_pin_bytes[2] = {0, 0}, pipe_dev_bytes = 0;      // [0] holds a chunk's inputs, [1] its outputs only
+    DevBuf<> pipe_dev[PIPE_SLOTS];           // all of one size
+    size_t pipe_pin_bytes[2] = {0, 0};       // [0] holds a chunk's inputs, [1] its outputs only
     uint32_t *pipe_err = nullptr;            // pinned: the solver's device error word as of each slot's copy-back
     hipStream_t pipe_h2d = nullptr, pipe_d2h = nullptr;
     hipEvent_t pipe_ev[PIPE_SLOTS][3] = {};      // per slot: h2d, compute, d2h done
@@ -397,13 +398,13 @@ struct geosrad_ctx {
     {
         for (int s = 0; s < PIPE_SLOTS; s++) {
             for (int d = 0; d < 2; d++) if (pipe_pin[s][d]) { (void)hipHostFree(pipe_pin[s][d]); pipe_pin[s][d] = nullptr; }
-            if (pipe_dev[s]) { (void)hipFree(pipe_dev[s]); pipe_dev[s] = nullptr; }
+            pipe_dev[s].release();
             for (int e = 0; e < 3; e++) if (pipe_ev[s][e]) { (void)hipEventDestroy(pipe_ev[s][e]); pipe_ev[s][e] = nullptr; }
         }
         if (pipe_h2d) { (void)hipStreamDestroy(pipe_h2d); pipe_h2d = nullptr; }
         if (pipe_d2h) { (void)hipStreamDestroy(pipe_d2h); pipe_d2h = nullptr; }
         if (pipe_err) { (void)hipHostFree(pipe_err); pipe_err = nullptr; }
-        pipe_pin_bytes[0] = pipe_pin_bytes[1] = pipe_dev_bytes = 0;
+        pipe_pin_bytes[0] = pipe_pin_bytes[1] = 0;
     }
     // a row into the write-once staging memory with non-temporal stores: no read-for-ownership of the destination lines (the rows,
     // 64 KB each, are below the size from which memcpy streams by itself)
@@ -481,25 +482,26 @@ struct geosrad_ctx {
             for (int s = 0; s < PIPE_SLOTS; s++) for (int e = 0; e < 3; e++) PIPECHK(hipEventCreateWithFlags(&pipe_ev[s][e], hipEventDisableTiming));
             PIPECHK(hipHostMalloc((void **)&pipe_err, PIPE_SLOTS * sizeof(uint32_t), hipHostMallocDefault));
         }
+        const size_t pipe_dev_bytes = pipe_dev[0].bytes;
         if (total_max > pipe_dev_bytes || in_bytes_max > pipe_pin_bytes[0] || out_bytes_max > pipe_pin_bytes[1]) {
             PIPECHK(hipDeviceSynchronize());
             const size_t want_dev = total_max > pipe_dev_bytes ? total_max : pipe_dev_bytes;
             const size_t want_pin[2] = {in_bytes_max > pipe_pin_bytes[0] ? in_bytes_max : pipe_pin_bytes[0],
                                         out_bytes_max > pipe_pin_bytes[1] ? out_bytes_max : pipe_pin_bytes[1]};
-            pipe_dev_bytes = pipe_pin_bytes[0] = pipe_pin_bytes[1] = 0;      // a failure below leaves "nothing allocated", not stale sizes
+            pipe_pin_bytes[0] = pipe_pin_bytes[1] = 0;      // a failure below leaves "nothing allocated", not stale sizes
             for (int s = 0; s < PIPE_SLOTS; s++) {
-                if (pipe_dev[s]) { (void)hipFree(pipe_dev[s]); pipe_dev[s] = nullptr; }
+                pipe_dev[s].release();
                 for (int d = 0; d < 2; d++) if (pipe_pin[s][d]) { (void)hipHostFree(pipe_pin[s][d]); pipe_pin[s][d] = nullptr; }
             }
             for (int s = 0; s < PIPE_SLOTS; s++) {
-                if (hipMalloc((void **)&pipe_dev[s], want_dev) != hipSuccess) { pipe_release(); return fail(GEOSRAD_ENOMEM, "hipMalloc of the host-API staging slot failed"); }
+                if (pipe_dev[s].resize(want_dev) != hipSuccess) { pipe_release(); return fail(GEOSRAD_ENOMEM, "hipMalloc of the host-API staging slot failed"); }
                 for (int d = 0; d < 2; d++)
                     if (hipHostMalloc((void **)&pipe_pin[s][d], want_pin[d] ? want_pin[d] : 256, hipHostMallocDefault) != hipSuccess) {
                         pipe_release();
                         return fail(GEOSRAD_ENOMEM, "hipHostMalloc of the pinned host-API staging slot failed");
                     }
             }
-            pipe_dev_bytes = want_dev; pipe_pin_bytes[0] = want_pin[0]; pipe_pin_bytes[1] = want_pin[1];
+            pipe_pin_bytes[0] = want_pin[0]; pipe_pin_bytes[1] = want_pin[1];
         }
         for (int s = 0; s < PIPE_SLOTS; s++) pipe_err[s] = 0;
         bool input_error = false;
@@ -648,6 +650,59 @@ enum LwIn { I_PLAY, I_PLEV, I_TLAY, I_TLEV, I_TSFC, I_EMIS, I_H2O, I_O3, I_CO2, 
             I_CCL4, I_CLDF, I_CIWP, I_CLWP, I_REI, I_REL, I_TAUAER, I_ZM, I_ALAT, I_NIN };
 enum LwOutIx { O_UFLX, O_DFLX, O_UFLXC, O_DFLXC, O_DUFLX, O_DUFLXC, O_OLRB, O_DOLRB, O_NOUT };
 
+// Shape of every host array of the pointer lists above, stated here once: Fortran (ncol, rows) of records of `rec` reals, the column
+// index the fastest but for the one inside a record (olrb is (16, ncol): one row of 16-real records; so are the stage dumps).  The
+// `*_host` functions stage `rows` rows per column from it, MultiCtx finds a shard's first column at `c0 * rec` reals.  L = layers.
+struct ArrShape { size_t rows, rec; };
+static inline ArrShape lw_in_shape(int k, size_t L)
+{
+    return {(k == I_PLEV || k == I_TLEV) ? L + 1 : (k == I_TSFC || k == I_ALAT) ? 1 : k == I_EMIS ? 16 : k == I_TAUAER ? 16 * L : L, 1};
+}
+static inline ArrShape lw_out_shape(int k, size_t L) { return (k == O_OLRB || k == O_DOLRB) ? ArrShape{1, 16} : ArrShape{L + 1, 1}; }
+static inline ArrShape lw_dump_shape(size_t L) { return {1, L * NG_LW}; }      // taug, pfracs: (nlay, 140, ncol)
+static inline ArrShape sw_in_shape(int k, size_t L)
+{
+    return {k == S_PLEV ? L + 1 : (k == S_TAUAER || k == S_SSAAER || k == S_ASMAER) ? (size_t)NB_SW * L : (k == S_ALAT || k >= S_COSZEN) ? 1 : L, 1};
+}
+static inline ArrShape sw_out_shape(int k, size_t L)
+{
+    return {k <= SO_DFLXC ? L + 1 : (k == SO_FSWBAND || k == SO_DRBAND || k == SO_DFBAND) ? (size_t)NB_SW : 1, 1};
+}
+static inline ArrShape sw_dump_shape(int k, size_t L) { return {1, (k == 2 ? 1 : L) * NG_SW}; }      // taug, taur, ssi (112, ncol), the three cldprmc planes
+static inline ArrShape ch_in_shape(int k, size_t L, size_t ns)
+{
+    return {k == C_PLE ? L + 1 : k == C_TB ? 1 : (k == C_CWC || k == C_REFF) ? 4 * L : (k == C_FS || k == C_TG || k == C_TV) ? ns
+            : (k == C_EG || k == C_EV || k == C_RV) ? ns * 10 : L, 1};
+}
+static inline ArrShape ch_aer_shape(size_t L, size_t nb) { return {L * nb, 1}; }
+static inline ArrShape ch_out_shape(int k, size_t L) { return {k == CO_SFCEM ? 1 : k == CO_TAUDIAG ? 10 * L : L + 1, 1}; }
+static inline ArrShape so_in_shape(int k, size_t L, size_t nb)
+{
+    return {(k == SI_COSZ || k >= SI_RSUVBM) ? 1 : k == SI_PL ? L + 1 : (k == SI_CWC || k == SI_REFF) ? 4 * L
+            : (k == SI_TAUA || k == SI_SSAA || k == SI_ASYA) ? L * nb : L, 1};
+}
+static inline ArrShape so_out_shape(int k, size_t L)
+{
+    return {(k == SOO_FLX || k == SOO_FLC || k == SOO_FLXU || k == SOO_FLCU) ? L + 1 : (k == SOO_SFCBAND || k == SOO_DRBAND || k == SOO_DFBAND) ? 8 : 1, 1};
+}
+
+// The arrays of one host-pointer call, added in host_pipeline's order (copied in only, both ways, back only).  src: copied in, dst:
+// copied back (null: the array only has its place on the device).  *at receives the array's device address before the solver is
+// enqueued for a chunk; the slot of an array that is not added keeps what the caller put there (null).
+struct HostArrs {
+    size_t E;      // bytes per real
+    std::vector<geosrad_ctx::PipeArr> arrs;
+    std::vector<const void **> at;
+    explicit HostArrs(size_t real_bytes) : E(real_bytes) {}
+    void add(const void *src, void *dst, ArrShape s, const void **at_, size_t ebytes = 0)      // ebytes 0: reals
+    {
+        arrs.push_back({src, dst, s.rows, s.rec * (ebytes ? ebytes : E), 0});
+        at.push_back(at_);
+    }
+    void add(const void *src, void *dst, ArrShape s, void **at_, size_t ebytes = 0) { add(src, dst, s, (const void **)at_, ebytes); }
+    void add_clear_counts(int32_t *dst, void **at_) { add(nullptr, dst, {4, 1}, at_, sizeof(int32_t)); }      // (ncol, 4); a null dst stays on the device
+};
+
 // The library is built from this one source as three objects compiled in parallel (GEOSRAD_PART = 4: the fp32
 // instantiation of Ctx and of every kernel, 8: the fp64 one, 0: the extern "C" layer); without GEOSRAD_PART it is
 // a single translation unit.
@@ -660,84 +715,57 @@ namespace {
 template <typename R> struct Ctx : geosrad_ctx {
     using R2 = typename Vec2<R>::T;
     // tables
-    char *d_tab = nullptr; size_t tab_bytes = 0;
-    char *d_xcw = nullptr; size_t xcw_bytes = 0;
+    DevBuf<> d_tab, d_xcw;
     size_t so_lds_set = 0;       // dynamic-LDS limit granted to k_sorad_col so far
     LwDev<R> h_T{};            // host copy (device pointers inside)
-    LwDev<R> *d_T = nullptr;
+    DevBuf<LwDev<R>> d_T;
     bool have_lw = false;
     // RRTMG_SW tables
-    char *d_tab_sw = nullptr; size_t tab_sw_bytes = 0;
+    DevBuf<> d_tab_sw;
     SwDev<R> h_S{};
     std::vector<R> avgcyc_mg, avgcyc_sb;          // NRLSSI2 mgavgcyc / sbavgcyc (134 each), host only: isolvar == 1
-    SwDev<R> *d_S = nullptr;
+    DevBuf<SwDev<R>> d_S;
     bool have_sw = false;
-    char *d_ws_sw = nullptr; size_t ws_sw_bytes = 0; int ws_sw_ncol = 0, ws_sw_nlay = 0, ws_sw_planes = 0; bool ws_sw_radval = false;
+    DevBuf<> d_ws_sw; int ws_sw_ncol = 0, ws_sw_nlay = 0, ws_sw_planes = 0; bool ws_sw_radval = false;
     // Chou-Suarez SW tables + workspace
-    char *d_tab_so = nullptr; size_t tab_so_bytes = 0;
+    DevBuf<> d_tab_so;
     SoradDev<R> h_O{};
-    SoradDev<R> *d_O = nullptr;
+    DevBuf<SoradDev<R>> d_O;
     bool have_sorad = false;
-    char *d_ws_so = nullptr; size_t ws_so_bytes = 0;
-    char *d_ws_swc = nullptr; size_t ws_swc_bytes = 0;      // sw_driver_chou_dev: the arrays SORADCORE prepares for sorad
+    DevBuf<> d_ws_so;
+    DevBuf<> d_ws_swc;      // sw_driver_chou_dev: the arrays SORADCORE prepares for sorad
     // Chou-Suarez LW tables + workspace
-    char *d_tab_ch = nullptr; size_t tab_ch_bytes = 0;
+    DevBuf<> d_tab_ch;
     ChouDev<R> h_C{};
-    ChouDev<R> *d_C = nullptr;
+    DevBuf<ChouDev<R>> d_C;
     bool have_chou = false;
-    char *d_ws_ch = nullptr; size_t ws_ch_bytes = 0;
-    char *d_ws_lwk = nullptr; size_t ws_lwk_bytes = 0;      // lw_driver_chou_dev: irrad's per-column surface arguments (+ TAUDIAG when not exported)
-    char *d_ws_drvs[2] = {nullptr, nullptr}; size_t ws_drvs_bytes[2] = {0, 0};      // RRTMG-side arrays of the LW / SW GridComp drivers (separate: the two may run on two streams)
+    DevBuf<> d_ws_ch;
+    DevBuf<> d_ws_lwk;      // lw_driver_chou_dev: irrad's per-column surface arguments (+ TAUDIAG when not exported)
+    DevBuf<> d_ws_drvs[2];      // RRTMG-side arrays of the LW / SW GridComp drivers (separate: the two may run on two streams)
     // McICA segment plans (jump-ahead constants), cached per (mode, nsubcol, nlay, inhomogeneous?)
-    struct PlanEntry { McSegDev *d_seg; int nseg; KissJump jsub, jhalf; };
+    struct PlanEntry { DevBuf<McSegDev> d_seg; int nseg; KissJump jsub, jhalf; };
     std::map<std::tuple<int, int, int, int>, PlanEntry> plans;
     // workspace
-    char *d_ws = nullptr; size_t ws_bytes = 0; int ws_ncol = 0, ws_nlay = 0;
-    char *d_zero = nullptr; size_t zero_bytes = 0;      // all-zero (nlay, ncol) plane of the RATS passes
-    int *d_bandflags = nullptr;                         // Update_Flx band exports: "band has a non-zero flux somewhere"
-    uint32_t *d_err = nullptr;
-    // staging for host-pointer entry points
-    char *d_io = nullptr; size_t io_bytes = 0;
+    DevBuf<> d_ws; int ws_ncol = 0, ws_nlay = 0;
+    DevBuf<> d_zero;      // all-zero (nlay, ncol) plane of the RATS passes
+    DevBuf<int> d_bandflags;      // Update_Flx band exports: "band has a non-zero flux somewhere"
+    DevBuf<uint32_t> d_err;
+    // plain staging of mcica_host, the one host-pointer entry point that does not go through host_pipeline
+    DevBuf<> d_io;
 
     Ctx() { for (int i = 0; i < 4; i++) { h_T.aam[i] = 0; h_T.ram[i] = 0; } }
-    ~Ctx() override
-    {
-        if (d_tab) (void)hipFree(d_tab);
-        if (d_xcw) (void)hipFree(d_xcw);
-        if (d_T) (void)hipFree(d_T);
-        if (d_ws) (void)hipFree(d_ws);
-        if (d_zero) (void)hipFree(d_zero);
-        if (d_bandflags) (void)hipFree(d_bandflags);
-        for (auto &pe : plans) if (pe.second.d_seg) (void)hipFree(pe.second.d_seg);
-        if (d_tab_sw) (void)hipFree(d_tab_sw);
-        if (d_tab_ch) (void)hipFree(d_tab_ch);
-        if (d_tab_so) (void)hipFree(d_tab_so);
-        if (d_O) (void)hipFree(d_O);
-        if (d_ws_so) (void)hipFree(d_ws_so);
-        if (d_ws_swc) (void)hipFree(d_ws_swc);
-        if (d_C) (void)hipFree(d_C);
-        if (d_ws_ch) (void)hipFree(d_ws_ch);
-        if (d_ws_lwk) (void)hipFree(d_ws_lwk);
-        for (char *q : d_ws_drvs) if (q) (void)hipFree(q);
-        if (d_S) (void)hipFree(d_S);
-        if (d_ws_sw) (void)hipFree(d_ws_sw);
-        if (d_err) (void)hipFree(d_err);
-        if (d_io) (void)hipFree(d_io);
-        if (d_mc) (void)hipFree(d_mc);
-        for (auto &e : sa_jumps) if (e.second) (void)hipFree(e.second);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~Ctx() override { if (stream) (void)hipStreamDestroy(stream); }      // the buffers free themselves
 
     int init() override
     {
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        HIPCHK(hipMalloc((void **)&d_err, 256));
+        HIPCHK(d_err.resize(256));
         HIPCHK(hipMemset(d_err, 0, 256));
-        HIPCHK(hipMalloc((void **)&d_T, sizeof(LwDev<R>)));
-        HIPCHK(hipMalloc((void **)&d_S, sizeof(SwDev<R>)));
-        HIPCHK(hipMalloc((void **)&d_C, sizeof(ChouDev<R>)));
-        HIPCHK(hipMalloc((void **)&d_O, sizeof(SoradDev<R>)));
+        HIPCHK(d_T.resize(sizeof(LwDev<R>)));
+        HIPCHK(d_S.resize(sizeof(SwDev<R>)));
+        HIPCHK(d_C.resize(sizeof(ChouDev<R>)));
+        HIPCHK(d_O.resize(sizeof(SoradDev<R>)));
         if (lw_bands_lds_bytes<R>() > 64 * 1024) {      // the LDS copy of the LW transmittance table (fp32 build)
             const int lds = (int)lw_bands_lds_bytes<R>();
             HIPCHK(hipFuncSetAttribute((const void *)k_lw_bands<R, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -861,10 +889,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         }
         if (!missing.empty()) return fail(GEOSRAD_ETABLE, "missing/ill-shaped table entries: " + missing);
 
-        if (d_tab) { HIPCHK(hipFree(d_tab)); d_tab = nullptr; }
-        tab_bytes = S.stage.size();
-        HIPCHK(hipMalloc((void **)&d_tab, tab_bytes));
-        HIPCHK(hipMemcpy(d_tab, S.stage.data(), tab_bytes, hipMemcpyHostToDevice));
+        HIPCHK(d_tab.resize(S.stage.size()));
+        HIPCHK(hipMemcpy(d_tab, S.stage.data(), d_tab.bytes, hipMemcpyHostToDevice));
         for (auto &f : fix) *f.first = (const R *)(d_tab + f.second);
         have_lw = true;
         return sync_T();
@@ -885,9 +911,9 @@ template <typename R> struct Ctx : geosrad_ctx {
             return fail(GEOSRAD_ETABLE, "xcw blob missing / wrong precision");
         auto ii = B.e.find("ih");
         if (ii != B.e.end() && *(const int32_t *)ii->second.data != ih) return fail(GEOSRAD_ETABLE, "xcw blob is for a different ih");
-        if (!d_xcw) HIPCHK(hipMalloc((void **)&d_xcw, 140000 * sizeof(R)));
+        HIPCHK(d_xcw.reserve(140000 * sizeof(R)));
         HIPCHK(hipMemcpy(d_xcw, it->second.data, 140000 * sizeof(R), hipMemcpyHostToDevice));
-        h_T.xcw = (const R *)d_xcw;
+        h_T.xcw = (const R *)d_xcw.p;
         return sync_T();
     }
 
@@ -901,7 +927,14 @@ template <typename R> struct Ctx : geosrad_ctx {
         return sync_T();
     }
 
-    size_t workspace_bytes() const override { return ws_bytes + ws_sw_bytes + ws_ch_bytes + ws_lwk_bytes + ws_so_bytes + ws_drvs_bytes[0] + ws_drvs_bytes[1] + io_bytes + tab_bytes + tab_sw_bytes + tab_ch_bytes; }
+    // not counted: d_ws_swc, d_mc, d_zero, d_xcw, d_tab_so, the fixed-size structs and McICA plans, the pipeline slots
+    size_t workspace_bytes() const override
+    {
+        size_t t = 0;
+        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
+            t += b->bytes;
+        return t;
+    }
 
     // ---- workspace -------------------------------------------------------------------------------------
     struct Ws { R *sc; uint32_t *scidx; R *pwvcm; uint8_t *colcloudy, *laycloudy; int32_t *perm, *nclear; R *taucmc, *alpha, *rcorr; uint16_t *s1, *s2; R *part;
@@ -938,12 +971,10 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (d_ws && nc <= ws_ncol && nlay == ws_nlay) return GEOSRAD_OK;
         // grow-only in columns for a given nlay
         const int want = (d_ws && nlay == ws_nlay && nc < ws_ncol) ? ws_ncol : nc;
-        if (d_ws) { HIPCHK(hipFree(d_ws)); d_ws = nullptr; ws_bytes = 0; }
         const size_t need = ws_layout(want, nlay, nullptr, nullptr);
-        hipError_t e = hipMalloc((void **)&d_ws, need);
-        if (e != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the LW workspace failed (" + std::to_string(need >> 20) +
+        if (d_ws.resize(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the LW workspace failed (" + std::to_string(need >> 20) +
                                                          " MiB); lower it with geosrad_set_chunk()");
-        ws_bytes = need; ws_ncol = want; ws_nlay = nlay;
+        ws_ncol = want; ws_nlay = nlay;
         return GEOSRAD_OK;
     }
 
@@ -973,10 +1004,9 @@ template <typename R> struct Ctx : geosrad_ctx {
             pe.nseg = (int)segs.size();
             pe.jsub = make_kiss_jump(per);
             pe.jhalf = make_kiss_jump(2ull * (uint64_t)nlay);
-            pe.d_seg = nullptr;
-            HIPCHK(hipMalloc((void **)&pe.d_seg, segs.size() * sizeof(McSegDev)));
-            HIPCHK(hipMemcpy(pe.d_seg, segs.data(), segs.size() * sizeof(McSegDev), hipMemcpyHostToDevice));
-            it = plans.emplace(key, pe).first;
+            HIPCHK(pe.d_seg.resize(segs.size() * sizeof(McSegDev)));
+            HIPCHK(hipMemcpy(pe.d_seg, segs.data(), pe.d_seg.bytes, hipMemcpyHostToDevice));
+            it = plans.emplace(key, std::move(pe)).first;
         }
         out.seg = it->second.d_seg; out.nseg = it->second.nseg; out.jsub = it->second.jsub; out.jhalf = it->second.jhalf;
         nseg_out = it->second.nseg;
@@ -1020,11 +1050,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             // a second set of band partials, so that the main call's stay available to the bands a gas does not touch
             const size_t zplane = al((size_t)nlay * ncol * sizeof(R));
             const size_t need = zplane + (size_t)6 * NB_LW * (nlay + 1) * nc_max * sizeof(R);
-            if (need > zero_bytes) {
-                if (d_zero) { HIPCHK(hipFree(d_zero)); d_zero = nullptr; zero_bytes = 0; }
-                if (hipMalloc((void **)&d_zero, need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the RATS workspace failed");
-                zero_bytes = need;
-            }
+            if (d_zero.reserve(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the RATS workspace failed");
             HIPCHK(hipMemsetAsync(d_zero, 0, zplane, st));
             rat_part = (R *)(d_zero + zplane);
         }
@@ -1114,9 +1140,9 @@ template <typename R> struct Ctx : geosrad_ctx {
             // (rrtmg_lw_setcoef.F90:206-272) is 0 / amttl = exactly zero.
             for (int r = 0; rats && r < rats->n; r++) {
                 LwArgs<R> B = A;
-                const R *z = (const R *)d_zero;
+                const R *z = (const R *)d_zero.p;
                 switch (rats->gas[r]) {
-                case GEOSRAD_RAT_H2O: B.h2o = z; B.pwvcm = (R *)d_zero; break;      // pwvcm is only read from here on
+                case GEOSRAD_RAT_H2O: B.h2o = z; B.pwvcm = (R *)d_zero.p; break;      // pwvcm is only read from here on
                 case GEOSRAD_RAT_O3: B.o3 = z; break;
                 case GEOSRAD_RAT_CO2: B.co2 = z; break;
                 case GEOSRAD_RAT_CH4: B.ch4 = z; break;
@@ -1157,10 +1183,7 @@ template <typename R> struct Ctx : geosrad_ctx {
     // ---- GridComp drivers (gridcomp_kernels.hpp) ---------------------------------------------------------------------------
     int drv_reserve(int which, size_t need)
     {
-        if (need <= ws_drvs_bytes[which]) return GEOSRAD_OK;
-        if (d_ws_drvs[which]) { HIPCHK(hipFree(d_ws_drvs[which])); d_ws_drvs[which] = nullptr; ws_drvs_bytes[which] = 0; }
-        if (hipMalloc((void **)&d_ws_drvs[which], need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the driver workspace failed");
-        ws_drvs_bytes[which] = need;
+        if (d_ws_drvs[which].reserve(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the driver workspace failed");
         return GEOSRAD_OK;
     }
 
@@ -1390,11 +1413,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (out[GEOSRAD_LWK_LWS0] && !out[GEOSRAD_LWK_FLX_INT]) return fail(GEOSRAD_EINVAL, "LWS0 was requested without FLX_INT, which it is computed from");
         const size_t cell = (size_t)ncol * sizeof(R);
         const size_t o_td = al(34 * cell), need = o_td + (out[GEOSRAD_LWK_TAUDIAG] ? 0 : al((size_t)10 * lm * cell));
-        if (need > ws_lwk_bytes) {
-            if (d_ws_lwk) { HIPCHK(hipFree(d_ws_lwk)); d_ws_lwk = nullptr; ws_lwk_bytes = 0; }
-            if (hipMalloc((void **)&d_ws_lwk, need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "LW_Driver (Chou-Suarez) workspace");
-            ws_lwk_bytes = need;
-        }
+        if (d_ws_lwk.reserve(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "LW_Driver (Chou-Suarez) workspace");
         auto I = [&](int k) { return (const R *)in[k]; };
         auto O = [&](int k) { return (R *)out[k]; };
         // 16-byte accesses (4 floats / 2 doubles per thread) when the column count and every address the two kernels touch allow
@@ -1402,7 +1421,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         bool wide = ncol % VW == 0;
         for (int k : {GEOSRAD_LWK_PLE, GEOSRAD_LWK_T, GEOSRAD_LWK_TS, GEOSRAD_LWK_EMIS}) wide = wide && ((uintptr_t)in[k] & 15) == 0;
         for (int k = GEOSRAD_LWK_DFDTS; k < GEOSRAD_LWK_NOUT; k++) wide = wide && ((uintptr_t)out[k] & 15) == 0;
-        R *ws = (R *)d_ws_lwk;                 // T2M, FS, TG, TV (ncol); EG, EV, RV (ncol,10); 256-byte aligned base, ncol % VW == 0 keeps 16
+        R *ws = (R *)d_ws_lwk.p;               // T2M, FS, TG, TV (ncol); EG, EV, RV (ncol,10); 256-byte aligned base, ncol % VW == 0 keeps 16
         LwkSurf<R> S{};
         S.ncol = ncol; S.lm = lm; S.mkappa = -(R)consts[GEOSRAD_LWK_C_KAPPA];
         S.ple = I(GEOSRAD_LWK_PLE); S.t = I(GEOSRAD_LWK_T); S.ts = I(GEOSRAD_LWK_TS); S.emis = I(GEOSRAD_LWK_EMIS);
@@ -1468,11 +1487,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         const size_t cell = (size_t)ncol * sizeof(R);
         const size_t o_plh = 0, o_o3 = o_plh + al((size_t)(lm + 1) * cell), o_qq = o_o3 + al((size_t)lm * cell), o_rr = o_qq + al((size_t)4 * lm * cell),
                      o_zero = o_rr + al((size_t)4 * lm * cell), need = o_zero + (aer ? 0 : al((size_t)8 * lm * cell));
-        if (need > ws_swc_bytes) {
-            if (d_ws_swc) { HIPCHK(hipFree(d_ws_swc)); d_ws_swc = nullptr; ws_swc_bytes = 0; }
-            if (hipMalloc((void **)&d_ws_swc, need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "SORADCORE (Chou-Suarez) workspace");
-            ws_swc_bytes = need;
-        }
+        if (d_ws_swc.reserve(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "SORADCORE (Chou-Suarez) workspace");
         SwcPrep<R> P{};
         P.ncol = ncol; P.lm = lm;
         P.ple = (const R *)in[GEOSRAD_SWC_PLE]; P.ox = (const R *)in[GEOSRAD_SWC_OX];
@@ -1560,7 +1575,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         HIPCHK(hipSetDevice(device));
         if (ncol <= 0 || !band_output || !wn1 || !wn2 || !tsinst || !ts_int || !olrb_int || !dolrb_int) return fail(GEOSRAD_EINVAL, "bad arguments");
         if (!olrb_exp && !tbrb_exp) return GEOSRAD_OK;
-        if (!d_bandflags) HIPCHK(hipMalloc((void **)&d_bandflags, 16 * sizeof(int)));
+        HIPCHK(d_bandflags.reserve(16 * sizeof(int)));
         HIPCHK(hipMemsetAsync(d_bandflags, 0, 16 * sizeof(int), st));
         LwBandUpd<R> U{};
         U.ncol = ncol; U.undef = (R)undef;
@@ -1776,113 +1791,54 @@ template <typename R> struct Ctx : geosrad_ctx {
     // host-pointer entry points start from a clean slot of their own solver (stream-ordered on the internal stream)
     int clear_slot(int which) { HIPCHK(hipMemsetAsync(d_err + which, 0, 4, stream)); return GEOSRAD_OK; }
 
-    int ensure_io(size_t bytes)
+    // One host-pointer call through the chunk pipeline (pinned staging + host_pipeline): run(stream, columns) enqueues the solver for one
+    // chunk, whose device arrays are where H.add() said.  which: the solver's slot of input assertions (0 RRTMG_LW, 1 RRTMG_SW) - the
+    // call starts from a clean slot and ends with its check(), which turns a flagged chunk into the reference's message; -1: a scheme
+    // without assertions, the caller synchronises.
+    int host_call(int ncol, HostArrs &H, int which, const std::function<int(hipStream_t, int)> &run)
     {
-        if (bytes <= io_bytes) return GEOSRAD_OK;
-        if (d_io) { HIPCHK(hipFree(d_io)); d_io = nullptr; io_bytes = 0; }
-        hipError_t e = hipMalloc((void **)&d_io, bytes);
-        if (e != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the host-API staging buffer failed");
-        io_bytes = bytes;
-        return GEOSRAD_OK;
+        auto chunk = [&](hipStream_t st, int nc, int, char *dev, int) -> int {
+            for (size_t i = 0; i < H.arrs.size(); i++) *H.at[i] = dev + H.arrs[i].off;
+            return run(st, nc);
+        };
+        if (which < 0) return host_pipeline(ncol, H.arrs, chunk);
+        int rc = clear_slot(which);
+        if (rc) return rc;
+        rc = host_pipeline(ncol, H.arrs, chunk, d_err + which);
+        if (rc && rc != PIPE_FLAGGED) return rc;
+        return check(stream, which);
     }
 
     // ---- RRTMG_LW, host pointers --------------------------------------------------------------------------------
+    // taug / pfracs (the geosrad_rrtmg_lw_taumol stage dump): per-column records behind the regular outputs.  A test hook for small
+    // batches: each record is nlay x 140 reals (40 KB a column in fp32), and the three device and pinned slots are sized for
+    // min(ncol, 16 384) columns of them - 1.3 GB a slot for the two arrays at a full chunk.
     int lw_host(int ncol, int nlay, int dudTs, const void *const *in, int iceflg, int liqflg, int dyofyr, int cloudLM, int cloudMH,
                 int32_t *clearCounts, void *const *out, const int32_t *band_output, void *taug, void *pfracs) override
     {
         HIPCHK(hipSetDevice(device));
         if (ncol <= 0 || nlay <= 0) return fail(GEOSRAD_EINVAL, "bad ncol/nlay");
-        if (!taug) {
-            // production path: pinned staging + chunk pipeline (host_pipeline); the taug / pfracs test hook keeps the plain path below
-            for (int k = 0; k < I_NIN; k++) if (!in[k] && k != I_TAUAER) return fail(GEOSRAD_EINVAL, "null input array");
-            for (int k = 0; k < 4; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
-            bool any_bo = false;
-            if (band_output) for (int b = 0; b < 16; b++) any_bo |= band_output[b] != 0;
-            const size_t L = (size_t)nlay, E = sizeof(R);
-            std::vector<PipeArr> arrs;
-            int ix_in[I_NIN], ix_out[O_NOUT], ix_cc = -1;
-            for (int k = 0; k < I_NIN; k++) {
-                ix_in[k] = -1;
-                if (!in[k]) continue;
-                const size_t rows = (k == I_PLEV || k == I_TLEV) ? L + 1 : (k == I_TSFC || k == I_ALAT) ? 1 : k == I_EMIS ? 16 : k == I_TAUAER ? 16 * L : L;
-                ix_in[k] = (int)arrs.size(); arrs.push_back({in[k], nullptr, rows, E, 0});
-            }
-            // olrb / dolrb_dTs, Fortran (16, ncol): 16 reals per column; the reference leaves un-requested bands untouched, so the
-            // caller's content makes the round trip
-            for (int k = 0; k < O_NOUT; k++) ix_out[k] = -1;
-            if (any_bo && out[O_OLRB]) { ix_out[O_OLRB] = (int)arrs.size(); arrs.push_back({out[O_OLRB], out[O_OLRB], 1, 16 * E, 0}); }
-            if (any_bo && dudTs && out[O_DOLRB]) { ix_out[O_DOLRB] = (int)arrs.size(); arrs.push_back({out[O_DOLRB], out[O_DOLRB], 1, 16 * E, 0}); }
-            for (int k = 0; k < O_OLRB; k++) {
-                if (!out[k] || ((k == O_DUFLX || k == O_DUFLXC) && !dudTs)) continue;
-                ix_out[k] = (int)arrs.size(); arrs.push_back({nullptr, out[k], L + 1, E, 0});
-            }
-            ix_cc = (int)arrs.size(); arrs.push_back({nullptr, clearCounts, 4, sizeof(int32_t), 0});      // dst may be null: stays on the device
-            auto run = [&](hipStream_t st, int nc, int, char *dev, int) -> int {
-                const void *din[I_NIN]; void *dout[O_NOUT];
-                for (int k = 0; k < I_NIN; k++) din[k] = ix_in[k] >= 0 ? dev + arrs[ix_in[k]].off : nullptr;
-                for (int k = 0; k < O_NOUT; k++) dout[k] = ix_out[k] >= 0 ? dev + arrs[ix_out[k]].off : nullptr;
-                return lw_dev(st, nc, nlay, dudTs, din, iceflg, liqflg, dyofyr, cloudLM, cloudMH, (int32_t *)(dev + arrs[ix_cc].off), dout,
-                              band_output, nullptr, nullptr, nullptr);
-            };
-            int rc = clear_slot(0);
-            if (rc) return rc;
-            rc = host_pipeline(ncol, arrs, run, d_err);
-            if (rc && rc != PIPE_FLAGGED) return rc;
-            return check(stream, 0);
-        }
-        const size_t cl = (size_t)ncol * nlay, cv = (size_t)ncol * (nlay + 1);
-        size_t insz[I_NIN];
-        for (int k = 0; k < I_NIN; k++) insz[k] = cl;
-        insz[I_PLEV] = insz[I_TLEV] = cv; insz[I_TSFC] = insz[I_ALAT] = ncol; insz[I_EMIS] = (size_t)ncol * 16;
-        insz[I_TAUAER] = cl * 16;
-        size_t outsz[O_NOUT] = {cv, cv, cv, cv, cv, cv, (size_t)ncol * 16, (size_t)ncol * 16};
-        size_t off = 0;
-        auto take = [&](size_t nreal) { size_t o = off; off += al(nreal * sizeof(R)); return o; };
-        size_t ino[I_NIN], outo[O_NOUT];
-        for (int k = 0; k < I_NIN; k++) ino[k] = in[k] ? take(insz[k]) : (size_t)-1;
-        for (int k = 0; k < O_NOUT; k++) outo[k] = take(outsz[k]);
-        const size_t cco = take((size_t)ncol * 4 * sizeof(int32_t) / sizeof(R) + 4);
-        size_t dbgo[2] = {0, 0};
-        if (taug) { dbgo[0] = take(cl * NG_LW); dbgo[1] = take(cl * NG_LW); }
-        int rc = ensure_io(off);
-        if (rc) return rc;
-        const void *din[I_NIN]; void *dout[O_NOUT];
-        for (int k = 0; k < I_NIN; k++) {
-            din[k] = in[k] ? d_io + ino[k] : nullptr;
-            if (in[k]) HIPCHK(hipMemcpyAsync(d_io + ino[k], in[k], insz[k] * sizeof(R), hipMemcpyHostToDevice, stream));
-        }
-        for (int k = 0; k < O_NOUT; k++) dout[k] = d_io + outo[k];
-        if (band_output) {   // the reference leaves un-requested bands untouched: round-trip the caller's content
-            bool any = false;
-            for (int b = 0; b < 16; b++) any |= band_output[b] != 0;
-            if (any && out[O_OLRB]) HIPCHK(hipMemcpyAsync(dout[O_OLRB], out[O_OLRB], outsz[O_OLRB] * sizeof(R), hipMemcpyHostToDevice, stream));
-            if (any && dudTs && out[O_DOLRB]) HIPCHK(hipMemcpyAsync(dout[O_DOLRB], out[O_DOLRB], outsz[O_DOLRB] * sizeof(R), hipMemcpyHostToDevice, stream));
-        }
-        void *dout_eff[O_NOUT];
-        for (int k = 0; k < O_NOUT; k++) dout_eff[k] = out[k] ? dout[k] : nullptr;
-        rc = lw_dev(stream, ncol, nlay, dudTs, din, iceflg, liqflg, dyofyr, cloudLM, cloudMH, (int32_t *)(d_io + cco), dout_eff,
-                    band_output, taug ? d_io + dbgo[0] : nullptr, taug ? d_io + dbgo[1] : nullptr, nullptr);
-        if (rc) return rc;
-        rc = check(stream, 0);
-        if (rc) return rc;
+        for (int k = 0; k < I_NIN; k++) if (!in[k] && k != I_TAUAER) return fail(GEOSRAD_EINVAL, "null input array");
+        for (int k = 0; k < 4; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
         bool any_bo = false;
         if (band_output) for (int b = 0; b < 16; b++) any_bo |= band_output[b] != 0;
-        for (int k = 0; k < O_NOUT; k++) {
-            if (!out[k]) continue;
-            if ((k == O_DUFLX || k == O_DUFLXC) && !dudTs) continue;
-            if (k == O_OLRB && !any_bo) continue;
-            if (k == O_DOLRB && !(any_bo && dudTs)) continue;
-            HIPCHK(hipMemcpyAsync(out[k], dout[k], outsz[k] * sizeof(R), hipMemcpyDeviceToHost, stream));
-        }
-        if (clearCounts) HIPCHK(hipMemcpyAsync(clearCounts, d_io + cco, (size_t)ncol * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        if (taug) {
-            HIPCHK(hipMemcpyAsync(taug, d_io + dbgo[0], cl * NG_LW * sizeof(R), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(pfracs, d_io + dbgo[1], cl * NG_LW * sizeof(R), hipMemcpyDeviceToHost, stream));
-        }
-        HIPCHK(hipStreamSynchronize(stream));
-        return GEOSRAD_OK;
+        const size_t L = (size_t)nlay;
+        HostArrs H(sizeof(R));
+        const void *din[I_NIN] = {};
+        void *dout[O_NOUT] = {}, *dcc = nullptr, *ddump[2] = {};
+        for (int k = 0; k < I_NIN; k++) if (in[k]) H.add(in[k], nullptr, lw_in_shape(k, L), &din[k]);
+        // olrb / dolrb_dTs: the reference leaves un-requested bands untouched, so the caller's content makes the round trip
+        for (int k : {O_OLRB, O_DOLRB})
+            if (any_bo && out[k] && (k == O_OLRB || dudTs)) H.add(out[k], out[k], lw_out_shape(k, L), &dout[k]);
+        for (int k = 0; k < O_OLRB; k++)
+            if (out[k] && (dudTs || (k != O_DUFLX && k != O_DUFLXC))) H.add(nullptr, out[k], lw_out_shape(k, L), &dout[k]);
+        H.add_clear_counts(clearCounts, &dcc);
+        if (taug) { H.add(nullptr, taug, lw_dump_shape(L), &ddump[0]); H.add(nullptr, pfracs, lw_dump_shape(L), &ddump[1]); }
+        return host_call(ncol, H, 0, [&](hipStream_t st, int nc) {
+            return lw_dev(st, nc, nlay, dudTs, din, iceflg, liqflg, dyofyr, cloudLM, cloudMH, (int32_t *)dcc, dout, band_output, ddump[0],
+                          ddump[1], nullptr);
+        });
     }
-
 
     // =====================================================================================================
     // RRTMG_SW
@@ -1950,14 +1906,12 @@ template <typename R> struct Ctx : geosrad_ctx {
             }
         }
         if (!S.missing.empty()) return fail(GEOSRAD_ETABLE, "missing/ill-shaped table entries: " + S.missing);
-        if (d_tab_sw) { HIPCHK(hipFree(d_tab_sw)); d_tab_sw = nullptr; }
-        tab_sw_bytes = S.stage.size();
-        HIPCHK(hipMalloc((void **)&d_tab_sw, tab_sw_bytes));
-        HIPCHK(hipMemcpy(d_tab_sw, S.stage.data(), tab_sw_bytes, hipMemcpyHostToDevice));
+        HIPCHK(d_tab_sw.resize(S.stage.size()));
+        HIPCHK(hipMemcpy(d_tab_sw, S.stage.data(), d_tab_sw.bytes, hipMemcpyHostToDevice));
         for (auto &f : S.fix) *f.first = (const R *)(d_tab_sw + f.second);
         // sw_eval reaches a band's upper-atmosphere tables as the lower ones' base + a 32-bit byte offset (one allocation, staged in this order)
         for (int b = 1; b <= NB_SW; b++)
-            if ((T.b[b].absb && T.b[b].absb < T.b[b].absa) || (T.b[b].x1 && T.b[b].x1 < T.b[b].x0) || tab_sw_bytes >= ((size_t)1 << 32))
+            if ((T.b[b].absb && T.b[b].absb < T.b[b].absa) || (T.b[b].x1 && T.b[b].x1 < T.b[b].x0) || d_tab_sw.bytes >= ((size_t)1 << 32))
                 return fail(GEOSRAD_ETABLE, "internal: RRTMG_SW table staging order");
         HIPCHK(hipMemcpy(d_S, &h_S, sizeof(SwDev<R>), hipMemcpyHostToDevice));
         have_sw = true;
@@ -2006,12 +1960,10 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (planes < ws_sw_planes) planes = ws_sw_planes;
         radval = radval || ws_sw_radval;
         const int want = (d_ws_sw && nlay == ws_sw_nlay && nc < ws_sw_ncol) ? ws_sw_ncol : nc;
-        if (d_ws_sw) { HIPCHK(hipFree(d_ws_sw)); d_ws_sw = nullptr; ws_sw_bytes = 0; }
         const size_t need = ws_layout_sw(want, nlay, nullptr, nullptr, planes, radval);
-        hipError_t e = hipMalloc((void **)&d_ws_sw, need);
-        if (e != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the SW workspace failed (" + std::to_string(need >> 20) +
+        if (d_ws_sw.resize(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the SW workspace failed (" + std::to_string(need >> 20) +
                                                          " MiB); lower it with geosrad_set_chunk()");
-        ws_sw_bytes = need; ws_sw_ncol = want; ws_sw_nlay = nlay; ws_sw_planes = planes; ws_sw_radval = radval;
+        ws_sw_ncol = want; ws_sw_nlay = nlay; ws_sw_planes = planes; ws_sw_radval = radval;
         return GEOSRAD_OK;
     }
 
@@ -2288,100 +2240,26 @@ template <typename R> struct Ctx : geosrad_ctx {
         HIPCHK(hipSetDevice(device));
         if (ncol <= 0 || nlay <= 0) return fail(GEOSRAD_EINVAL, "bad ncol/nlay");
         if (radval && dbg) return fail(GEOSRAD_EINVAL, "the stage dumps do not produce the SOLAR_RADVAL diagnostics");
-        if (!dbg) {
-            // production path: pinned staging + chunk pipeline (host_pipeline); the stage-dump test hooks keep the plain path below
-            for (int k = 0; k < S_NIN; k++)
-                if (!in[k] && !((k == S_TAUAER || k == S_SSAAER || k == S_ASMAER) && iaer != 10)) return fail(GEOSRAD_EINVAL, "null input array");
-            for (int k = 0; k < SO_DRBAND; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
-            if (do_drfband && (!out[SO_DRBAND] || !out[SO_DFBAND])) return fail(GEOSRAD_EINVAL, "do_drfband set but drband/dfband null");
-            const size_t L = (size_t)nlay, E = sizeof(R);
-            std::vector<PipeArr> arrs;
-            int ix_in[S_NIN], ix_out[SO_NOUT], ix_cc = -1;
-            for (int k = 0; k < S_NIN; k++) {
-                ix_in[k] = -1;
-                const bool aer = (k == S_TAUAER || k == S_SSAAER || k == S_ASMAER);
-                if (!in[k] || (aer && iaer != 10)) continue;
-                const size_t rows = k == S_PLEV ? L + 1 : aer ? (size_t)NB_SW * L
-                                  : (k == S_ALAT || k == S_COSZEN || k == S_ASDIR || k == S_ASDIF || k == S_ALDIR || k == S_ALDIF) ? 1 : L;
-                ix_in[k] = (int)arrs.size(); arrs.push_back({in[k], nullptr, rows, E, 0});
-            }
-            for (int k = 0; k < SO_NOUT; k++) {
-                ix_out[k] = -1;
-                if ((k == SO_DRBAND || k == SO_DFBAND) && !do_drfband) continue;
-                const size_t rows = k <= SO_DFLXC ? L + 1 : (k == SO_FSWBAND || k == SO_DRBAND || k == SO_DFBAND) ? (size_t)NB_SW : 1;
-                ix_out[k] = (int)arrs.size(); arrs.push_back({nullptr, out[k], rows, E, 0});
-            }
-            ix_cc = (int)arrs.size(); arrs.push_back({nullptr, clearCounts, 4, sizeof(int32_t), 0});
-            const int ix_rv = radval ? (int)arrs.size() : -1;
-            if (radval) arrs.push_back({nullptr, radval, (size_t)GEOSRAD_RV_COUNT, E, 0});
-            auto run = [&](hipStream_t st, int nc, int, char *dev, int) -> int {
-                const void *din[S_NIN]; void *dout[SO_NOUT];
-                for (int k = 0; k < S_NIN; k++) din[k] = ix_in[k] >= 0 ? dev + arrs[ix_in[k]].off : nullptr;
-                for (int k = 0; k < SO_NOUT; k++) dout[k] = ix_out[k] >= 0 ? dev + arrs[ix_out[k]].off : nullptr;
-                return sw_dev(st, nc, nlay, scon, adjes, isolvar, din, iceflg, liqflg, dyofyr, iaer, cloudLM, cloudMH, normFlx,
-                              (int32_t *)(dev + arrs[ix_cc].off), dout, do_drfband, bndscl, indsolvar, solcycfrac, nullptr,
-                              ix_rv >= 0 ? dev + arrs[ix_rv].off : nullptr);
-            };
-            int rc = clear_slot(1);
-            if (rc) return rc;
-            rc = host_pipeline(ncol, arrs, run, d_err + 1);
-            if (rc && rc != PIPE_FLAGGED) return rc;
-            return check(stream, 1);
-        }
-        const size_t cl = (size_t)ncol * nlay, cv = (size_t)ncol * (nlay + 1);
-        size_t insz[S_NIN];
-        for (int k = 0; k < S_NIN; k++) insz[k] = cl;
-        insz[S_PLEV] = cv; insz[S_ALAT] = insz[S_COSZEN] = insz[S_ASDIR] = insz[S_ASDIF] = insz[S_ALDIR] = insz[S_ALDIF] = ncol;
-        insz[S_TAUAER] = insz[S_SSAAER] = insz[S_ASMAER] = cl * NB_SW;
-        size_t outsz[SO_NOUT];
-        for (int k = 0; k < SO_NOUT; k++) outsz[k] = ncol;
-        outsz[SO_UFLX] = outsz[SO_DFLX] = outsz[SO_UFLXC] = outsz[SO_DFLXC] = cv;
-        outsz[SO_FSWBAND] = outsz[SO_DRBAND] = outsz[SO_DFBAND] = (size_t)ncol * NB_SW;
-        size_t off = 0;
-        auto take = [&](size_t nreal) { size_t o = off; off += al(nreal * sizeof(R)); return o; };
-        size_t ino[S_NIN], outo[SO_NOUT];
-        for (int k = 0; k < S_NIN; k++) {
-            const bool aer = (k == S_TAUAER || k == S_SSAAER || k == S_ASMAER);
-            ino[k] = (in[k] && !(aer && iaer != 10)) ? take(insz[k]) : (size_t)-1;
-        }
-        for (int k = 0; k < SO_NOUT; k++) outo[k] = take(outsz[k]);
-        const size_t cco = take((size_t)ncol * 4 * sizeof(int32_t) / sizeof(R) + 4);
-        size_t dbgo[6] = {0, 0, 0, 0, 0, 0};
-        if (dbg) { dbgo[0] = take(cl * NG_SW); dbgo[1] = take(cl * NG_SW); dbgo[2] = take((size_t)ncol * NG_SW); }
-        if (dbg && dbg[3]) { dbgo[3] = take(cl * NG_SW); dbgo[4] = take(cl * NG_SW); dbgo[5] = take(cl * NG_SW); }
-        int rc = ensure_io(off);
-        if (rc) return rc;
-        const void *din[S_NIN]; void *dout[SO_NOUT];
-        for (int k = 0; k < S_NIN; k++) {
-            din[k] = ino[k] != (size_t)-1 ? d_io + ino[k] : nullptr;
-            if (din[k]) HIPCHK(hipMemcpyAsync(d_io + ino[k], in[k], insz[k] * sizeof(R), hipMemcpyHostToDevice, stream));
-        }
-        for (int k = 0; k < SO_NOUT; k++) dout[k] = (out[k] || k < SO_DRBAND) ? d_io + outo[k] : nullptr;
-        void *ddbg[6] = {d_io + dbgo[0], d_io + dbgo[1], d_io + dbgo[2], nullptr, nullptr, nullptr};
-        if (dbg && dbg[3]) for (int k = 3; k < 6; k++) ddbg[k] = d_io + dbgo[k];
-        rc = sw_dev(stream, ncol, nlay, scon, adjes, isolvar, din, iceflg, liqflg, dyofyr, iaer, cloudLM, cloudMH, normFlx,
-                    (int32_t *)(d_io + cco), dout, do_drfband, bndscl, indsolvar, solcycfrac, dbg ? ddbg : nullptr, nullptr);
-        if (rc) return rc;
-        rc = check(stream, 1);
-        if (rc) return rc;
-        for (int k = 0; k < SO_NOUT; k++) {
-            if (!out[k]) continue;
-            if ((k == SO_DRBAND || k == SO_DFBAND) && !do_drfband) continue;
-            HIPCHK(hipMemcpyAsync(out[k], dout[k], outsz[k] * sizeof(R), hipMemcpyDeviceToHost, stream));
-        }
-        if (clearCounts) HIPCHK(hipMemcpyAsync(clearCounts, d_io + cco, (size_t)ncol * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        if (dbg) {
-            HIPCHK(hipMemcpyAsync(dbg[0], ddbg[0], cl * NG_SW * sizeof(R), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(dbg[1], ddbg[1], cl * NG_SW * sizeof(R), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(dbg[2], ddbg[2], (size_t)ncol * NG_SW * sizeof(R), hipMemcpyDeviceToHost, stream));
-            if (dbg[3])
-                for (int k = 3; k < 6; k++) HIPCHK(hipMemcpyAsync(dbg[k], ddbg[k], cl * NG_SW * sizeof(R), hipMemcpyDeviceToHost, stream));
-        }
-        HIPCHK(hipStreamSynchronize(stream));
-        return GEOSRAD_OK;
+        auto aer = [](int k) { return k == S_TAUAER || k == S_SSAAER || k == S_ASMAER; };
+        for (int k = 0; k < S_NIN; k++) if (!in[k] && !(aer(k) && iaer != 10)) return fail(GEOSRAD_EINVAL, "null input array");
+        for (int k = 0; k < SO_DRBAND; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
+        if (do_drfband && (!out[SO_DRBAND] || !out[SO_DFBAND])) return fail(GEOSRAD_EINVAL, "do_drfband set but drband/dfband null");
+        const size_t L = (size_t)nlay;
+        HostArrs H(sizeof(R));
+        const void *din[S_NIN] = {};
+        void *dout[SO_NOUT] = {}, *dcc = nullptr, *drv = nullptr, *ddump[6] = {};
+        for (int k = 0; k < S_NIN; k++) if (in[k] && !(aer(k) && iaer != 10)) H.add(in[k], nullptr, sw_in_shape(k, L), &din[k]);
+        for (int k = 0; k < SO_NOUT; k++) if (k < SO_DRBAND || do_drfband) H.add(nullptr, out[k], sw_out_shape(k, L), &dout[k]);
+        H.add_clear_counts(clearCounts, &dcc);
+        if (radval) H.add(nullptr, radval, {(size_t)GEOSRAD_RV_COUNT, 1}, &drv);
+        // the stage dumps of geosrad_rrtmg_sw_taumol (taug, taur, ssi) and geosrad_rrtmg_sw_cldprmc (+ the three cloud planes): test
+        // hooks for small batches, like lw_host's (up to five records of nlay x 112 reals a column in every staging slot)
+        for (int k = 0; dbg && k < 6; k++) if (dbg[k]) H.add(nullptr, dbg[k], sw_dump_shape(k, L), &ddump[k]);
+        return host_call(ncol, H, 1, [&](hipStream_t st, int nc) {
+            return sw_dev(st, nc, nlay, scon, adjes, isolvar, din, iceflg, liqflg, dyofyr, iaer, cloudLM, cloudMH, normFlx, (int32_t *)dcc,
+                          dout, do_drfband, bndscl, indsolvar, solcycfrac, dbg ? ddump : nullptr, drv);
+        });
     }
-
-    // ---- stand-alone McICA generator, host pointers ------------------------------------------------------------------
 
     // =====================================================================================================
     // Chou-Suarez longwave (irrad)
@@ -2409,10 +2287,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         S.raw(&T.h21, "h21", 26 * 31); S.raw(&T.h22, "h22", 26 * 31); S.raw(&T.h23, "h23", 26 * 31);
         S.raw(&T.h81, "h81", 26 * 31); S.raw(&T.h82, "h82", 26 * 31); S.raw(&T.h83, "h83", 26 * 31);
         if (!S.missing.empty()) return fail(GEOSRAD_ETABLE, "missing/ill-shaped table entries: " + S.missing);
-        if (d_tab_ch) { HIPCHK(hipFree(d_tab_ch)); d_tab_ch = nullptr; }
-        tab_ch_bytes = S.stage.size();
-        HIPCHK(hipMalloc((void **)&d_tab_ch, tab_ch_bytes));
-        HIPCHK(hipMemcpy(d_tab_ch, S.stage.data(), tab_ch_bytes, hipMemcpyHostToDevice));
+        HIPCHK(d_tab_ch.resize(S.stage.size()));
+        HIPCHK(hipMemcpy(d_tab_ch, S.stage.data(), d_tab_ch.bytes, hipMemcpyHostToDevice));
         for (auto &f : S.fix) *f.first = (const R *)(d_tab_ch + f.second);
         HIPCHK(hipMemcpy(d_C, &h_C, sizeof(ChouDev<R>), hipMemcpyHostToDevice));
         have_chou = true;
@@ -2443,11 +2319,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         const int K1 = np + 1, K2 = np + 2;
         const int nc_max = m < chunk ? m : chunk;
         const size_t need = al((size_t)nc_max * CF_NFIELD * K1 * sizeof(R)) + al((size_t)nc_max * CH_NB * CH_NKIND * K2 * sizeof(R));
-        if (need > ws_ch_bytes) {
-            if (d_ws_ch) { HIPCHK(hipFree(d_ws_ch)); d_ws_ch = nullptr; ws_ch_bytes = 0; }
-            if (hipMalloc((void **)&d_ws_ch, need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the irrad workspace failed");
-            ws_ch_bytes = need;
-        }
+        if (d_ws_ch.reserve(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the irrad workspace failed");
         const int nband = trace ? 10 : 9;      // irrad.F90:478 (band 10 only with trace gases)
 #ifndef GEOSRAD_EXP_LDS_PAD
 #define GEOSRAD_EXP_LDS_PAD 0
@@ -2471,7 +2343,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             A.fs = P(C_FS); A.tg = P(C_TG); A.eg = P(C_EG); A.tv = P(C_TV); A.ev = P(C_EV); A.rv = P(C_RV);
             A.taua = aer[0] ? (R *)aer[0] + c0 : nullptr; A.ssaa = aer[1] ? (R *)aer[1] + c0 : nullptr; A.asya = aer[2] ? (R *)aer[2] + c0 : nullptr;
             A.taudiag = (R *)out[CO_TAUDIAG] + c0;
-            A.rec = (R *)d_ws_ch; A.part = (R *)(d_ws_ch + al((size_t)nc_max * CF_NFIELD * K1 * sizeof(R)));
+            A.rec = (R *)d_ws_ch.p; A.part = (R *)(d_ws_ch + al((size_t)nc_max * CF_NFIELD * K1 * sizeof(R)));
             A.err = d_err + 2;
             span_begin(10, st);
             const dim3 gp((unsigned)((nc + 63) / 64), (unsigned)chou_prep_tiles<R>(np));
@@ -2498,39 +2370,23 @@ template <typename R> struct Ctx : geosrad_ctx {
     int irrad_host(int m, int np, const void *const *in, double co2, int trace, int ict, int icb, int ns, int na, int nb, void *const *aer,
                    void *const *out) override
     {
-        // host arrays: pinned staging + chunk pipeline (host_pipeline), like rrtmg_lw / rrtmg_sw - transfers of a chunk overlap the
-        // kernels of its neighbours (irrad is 0.33 ms of kernels per 1 000 columns against 0.08 ms of transfers)
+        // host arrays through the chunk pipeline like rrtmg_lw / rrtmg_sw - transfers of a chunk overlap the kernels of its neighbours
+        // (irrad is 0.33 ms of kernels per 1 000 columns against 0.08 ms of transfers)
         HIPCHK(hipSetDevice(device));
         if (m <= 0 || np <= 0 || ns < 1 || nb < 1) return fail(GEOSRAD_EINVAL, "bad m/np/ns/nb");
         for (int k = 0; k < C_NIN; k++) if (!in[k]) return fail(GEOSRAD_EINVAL, "null input array");
         for (int k = 0; k < CO_NOUT; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
-        const size_t L = (size_t)np, E = sizeof(R);
-        std::vector<PipeArr> arrs;
-        int ix_in[C_NIN], ix_aer[3] = {-1, -1, -1}, ix_out[CO_NOUT];
-        for (int k = 0; k < C_NIN; k++) {
-            const size_t rows = k == C_PLE ? L + 1 : k == C_TB ? 1 : (k == C_CWC || k == C_REFF) ? 4 * L
-                              : (k == C_FS || k == C_TG || k == C_TV) ? (size_t)ns : (k == C_EG || k == C_EV || k == C_RV) ? (size_t)ns * 10 : L;
-            ix_in[k] = (int)arrs.size(); arrs.push_back({in[k], nullptr, rows, E, 0});
-        }
-        for (int k = 0; k < 3; k++)
-            if (na > 0 && aer[k]) { ix_aer[k] = (int)arrs.size(); arrs.push_back({aer[k], aer[k], L * (size_t)nb, E, 0}); }      // rescaled in place
-        for (int k = 0; k < CO_NOUT; k++) {
-            const size_t rows = k == CO_SFCEM ? 1 : k == CO_TAUDIAG ? 10 * L : L + 1;
-            ix_out[k] = (int)arrs.size(); arrs.push_back({nullptr, out[k], rows, E, 0});
-        }
-        auto run = [&](hipStream_t st, int nc, int, char *dev, int) -> int {
-            const void *din[C_NIN]; void *dout[CO_NOUT]; void *daer[3];
-            for (int k = 0; k < C_NIN; k++) din[k] = dev + arrs[ix_in[k]].off;
-            for (int k = 0; k < CO_NOUT; k++) dout[k] = dev + arrs[ix_out[k]].off;
-            for (int k = 0; k < 3; k++) daer[k] = ix_aer[k] >= 0 ? dev + arrs[ix_aer[k]].off : nullptr;
-            return irrad_dev(st, nc, np, din, co2, trace, ict, icb, ns, na, nb, daer, dout);
-        };
-        int rc = host_pipeline(m, arrs, run);
+        HostArrs H(sizeof(R));
+        const void *din[C_NIN] = {};
+        void *dout[CO_NOUT] = {}, *daer[3] = {};
+        for (int k = 0; k < C_NIN; k++) H.add(in[k], nullptr, ch_in_shape(k, np, ns), &din[k]);
+        for (int k = 0; k < 3; k++) if (na > 0 && aer[k]) H.add(aer[k], aer[k], ch_aer_shape(np, nb), &daer[k]);      // rescaled in place
+        for (int k = 0; k < CO_NOUT; k++) H.add(nullptr, out[k], ch_out_shape(k, np), &dout[k]);
+        const int rc = host_call(m, H, -1, [&](hipStream_t st, int nc) { return irrad_dev(st, nc, np, din, co2, trace, ict, icb, ns, na, nb, daer, dout); });
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(stream));      // the Chou schemes have no input assertions (neither has the reference)
         return GEOSRAD_OK;
     }
-
 
     // =====================================================================================================
     // Chou-Suarez shortwave (sorad)
@@ -2552,10 +2408,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         T.aib_uv = S.scalar("aib_uv"); T.aib_nir = S.scalar("aib_nir");
         S.raw(&T.coa, "coa", 62 * 101); S.raw(&T.cah, "cah", 43 * 37); S.raw(&T.caib, "caib", 11 * 9 * 11); S.raw(&T.caif, "caif", 9 * 11);
         if (!S.missing.empty()) return fail(GEOSRAD_ETABLE, "missing/ill-shaped table entries: " + S.missing);
-        if (d_tab_so) { HIPCHK(hipFree(d_tab_so)); d_tab_so = nullptr; }
-        tab_so_bytes = S.stage.size();
-        HIPCHK(hipMalloc((void **)&d_tab_so, tab_so_bytes));
-        HIPCHK(hipMemcpy(d_tab_so, S.stage.data(), tab_so_bytes, hipMemcpyHostToDevice));
+        HIPCHK(d_tab_so.resize(S.stage.size()));
+        HIPCHK(hipMemcpy(d_tab_so, S.stage.data(), d_tab_so.bytes, hipMemcpyHostToDevice));
         for (auto &f : S.fix) *f.first = (const R *)(d_tab_so + f.second);
         HIPCHK(hipMemcpy(d_O, &h_O, sizeof(SoradDev<R>), hipMemcpyHostToDevice));
         have_sorad = true;
@@ -2595,12 +2449,8 @@ template <typename R> struct Ctx : geosrad_ctx {
                 so_lds_set = so_lds;
             }
         }
-        if (need > ws_so_bytes) {
-            if (d_ws_so) { HIPCHK(hipFree(d_ws_so)); d_ws_so = nullptr; ws_so_bytes = 0; }
-            if (hipMalloc((void **)&d_ws_so, need) != hipSuccess)
-                return fail(GEOSRAD_ENOMEM, "hipMalloc of the sorad workspace failed (" + std::to_string(need >> 20) + " MiB); lower it with geosrad_set_chunk()");
-            ws_so_bytes = need;
-        }
+        if (d_ws_so.reserve(need) != hipSuccess)
+            return fail(GEOSRAD_ENOMEM, "hipMalloc of the sorad workspace failed (" + std::to_string(need >> 20) + " MiB); lower it with geosrad_set_chunk()");
         for (int c0 = 0; c0 < m; c0 += nc_max) {
             const int nc = (m - c0) < nc_max ? (m - c0) : nc_max;
             SoradArgs<R> A{};
@@ -2671,40 +2521,26 @@ template <typename R> struct Ctx : geosrad_ctx {
     int sorad_host(int m, int np, int nb, const void *const *in, double co2, int ict, int icb, const void *hk_uv, const void *hk_ir,
                    void *const *out, int do_drfband) override
     {
-        // host arrays: pinned staging + chunk pipeline (host_pipeline)
+        // host arrays through the chunk pipeline
         HIPCHK(hipSetDevice(device));
         if (m <= 0 || np <= 0 || nb < 1) return fail(GEOSRAD_EINVAL, "bad m/np/nb");
         for (int k = 0; k < SI_NIN; k++) if (!in[k]) return fail(GEOSRAD_EINVAL, "null input array");
-        const size_t L = (size_t)np, E = sizeof(R);
-        std::vector<PipeArr> arrs;
-        int ix_in[SI_NIN], ix_out[SOO_NOUT];
-        for (int k = 0; k < SI_NIN; k++) {
-            const size_t rows = (k == SI_COSZ || k == SI_RSUVBM || k == SI_RSUVDF || k == SI_RSIRBM || k == SI_RSIRDF) ? 1 : k == SI_PL ? L + 1
-                              : (k == SI_CWC || k == SI_REFF) ? 4 * L : (k == SI_TAUA || k == SI_SSAA || k == SI_ASYA) ? L * (size_t)nb : L;
-            ix_in[k] = (int)arrs.size(); arrs.push_back({in[k], nullptr, rows, E, 0});
-        }
-        for (int k = 0; k < SOO_NOUT; k++) {
-            const size_t rows = (k == SOO_FLX || k == SOO_FLC || k == SOO_FLXU || k == SOO_FLCU) ? L + 1
-                              : (k == SOO_SFCBAND || k == SOO_DRBAND || k == SOO_DFBAND) ? 8 : 1;
-            // an output the caller does not take (or drband / dfband without do_drfband) still has its place on the device
-            void *dst = ((k == SOO_DRBAND || k == SOO_DFBAND) && !do_drfband) ? nullptr : out[k];
-            ix_out[k] = (int)arrs.size(); arrs.push_back({nullptr, dst, rows, E, 0});
-        }
-        auto run = [&](hipStream_t st, int nc, int, char *dev, int) -> int {
-            const void *din[SI_NIN]; void *dout[SOO_NOUT];
-            for (int k = 0; k < SI_NIN; k++) din[k] = dev + arrs[ix_in[k]].off;
-            for (int k = 0; k < SOO_NOUT; k++) dout[k] = dev + arrs[ix_out[k]].off;
-            return sorad_dev(st, nc, np, nb, din, co2, ict, icb, hk_uv, hk_ir, dout, do_drfband);
-        };
-        int rc = host_pipeline(m, arrs, run);
+        HostArrs H(sizeof(R));
+        const void *din[SI_NIN] = {};
+        void *dout[SOO_NOUT] = {};
+        for (int k = 0; k < SI_NIN; k++) H.add(in[k], nullptr, so_in_shape(k, np, nb), &din[k]);
+        // an output the caller does not take (or drband / dfband without do_drfband) still has its place on the device
+        for (int k = 0; k < SOO_NOUT; k++)
+            H.add(nullptr, ((k == SOO_DRBAND || k == SOO_DFBAND) && !do_drfband) ? nullptr : out[k], so_out_shape(k, np), &dout[k]);
+        const int rc = host_call(m, H, -1, [&](hipStream_t st, int nc) { return sorad_dev(st, nc, np, nb, din, co2, ict, icb, hk_uv, hk_ir, dout, do_drfband); });
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(stream));      // the Chou schemes have no input assertions (neither has the reference)
         return GEOSRAD_OK;
     }
 
     // ---- stand-alone McICA generator ---------------------------------------------------------------------------------
-    char *d_mc = nullptr; size_t mc_bytes = 0;      // alpha / rcorr scratch of the stand-alone generator
-    std::map<std::tuple<int, int, int>, KissJump *> sa_jumps;      // (nsubcol, nlay, inhomogeneous?) -> jump to every sub-column
+    DevBuf<> d_mc;      // alpha / rcorr scratch of the stand-alone generator
+    std::map<std::tuple<int, int, int>, DevBuf<KissJump>> sa_jumps;      // (nsubcol, nlay, inhomogeneous?) -> jump to every sub-column
     int mcica_dev(hipStream_t st, int ncol, int nsubcol, int nlay, const void *zmid, const void *alat, int doy, const void *play,
                   const void *cldfrac, const void *ciwp, const void *clwp, double cwp_tiny, const int32_t *so, int32_t *cldy,
                   void *ciwp_s, void *clwp_s) override
@@ -2722,12 +2558,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         }
         const size_t cl = (size_t)ncol * nlay;
         const size_t need = 2 * al(cl * sizeof(R));
-        if (need > mc_bytes) {
-            if (d_mc) { HIPCHK(hipFree(d_mc)); d_mc = nullptr; mc_bytes = 0; }
-            if (hipMalloc((void **)&d_mc, need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the McICA scratch failed");
-            mc_bytes = need;
-        }
-        R *d_alpha = (R *)d_mc, *d_rcorr = (R *)(d_mc + al(cl * sizeof(R)));
+        if (d_mc.reserve(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the McICA scratch failed");
+        R *d_alpha = (R *)d_mc.p, *d_rcorr = (R *)(d_mc + al(cl * sizeof(R)));
         const unsigned gx = (unsigned)((ncol + 255) / 256);
         span_begin(2, st);
         hipLaunchKernelGGL(k_overlap<R>, dim3(gx, nlay), dim3(256), 0, st, ncol, ncol, nlay, doy, (const R *)zmid, (const R *)alat,
@@ -2755,13 +2587,13 @@ template <typename R> struct Ctx : geosrad_ctx {
                 const uint64_t per = (uint64_t)(inhomo ? 4 : 2) * (uint64_t)nlay;
                 std::vector<KissJump> js((size_t)nsubcol);
                 for (int q = 0; q < nsubcol; q++) js[q] = make_kiss_jump((uint64_t)q * per);
-                KissJump *dj = nullptr;
-                HIPCHK(hipMalloc((void **)&dj, js.size() * sizeof(KissJump)));
-                HIPCHK(hipMemcpy(dj, js.data(), js.size() * sizeof(KissJump), hipMemcpyHostToDevice));
-                it = sa_jumps.emplace(key, dj).first;
+                DevBuf<KissJump> dj;
+                HIPCHK(dj.resize(js.size() * sizeof(KissJump)));
+                HIPCHK(hipMemcpy(dj, js.data(), dj.bytes, hipMemcpyHostToDevice));
+                it = sa_jumps.emplace(key, std::move(dj)).first;
             }
             if (lds > 65536) HIPCHK(hipFuncSetAttribute((const void *)k_mcica_sa<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_mcica_sa<R>), dim3((unsigned)nblk), dim3(64), lds, st, M, (const KissJump *)it->second, MP.jhalf,
+            hipLaunchKernelGGL((k_mcica_sa<R>), dim3((unsigned)nblk), dim3(64), lds, st, M, (const KissJump *)it->second.p, MP.jhalf,
                                (const LwDev<R> *)d_T);
         } else {
             // lane = column (tiles beyond 64 KB of LDS: fp64 with more than 127 layers)
@@ -2776,6 +2608,8 @@ template <typename R> struct Ctx : geosrad_ctx {
                    const void *ciwp, const void *clwp, double cwp_tiny, const int32_t *so, int32_t *cldy, void *ciwp_s,
                    void *clwp_s) override
     {
+        // not through host_pipeline: the outputs are 12 B x nlay x nsubcol per column (173 KB at 72 x 200), so a 16 384-column chunk would
+        // make each of the three pinned and device slots 2.8 GB.  The one user of d_io.
         HIPCHK(hipSetDevice(device));
         if (ncol <= 0 || nlay < 4 || nsubcol <= 0) return fail(GEOSRAD_EINVAL, "bad ncol/nlay/nsubcol");
         const size_t cl = (size_t)ncol * nlay, co = cl * nsubcol;
@@ -2784,13 +2618,12 @@ template <typename R> struct Ctx : geosrad_ctx {
         const size_t o_z = take(cl * sizeof(R)), o_p = take(cl * sizeof(R)), o_f = take(cl * sizeof(R)), o_i = take(cl * sizeof(R)),
                      o_l = take(cl * sizeof(R)), o_a = take((size_t)ncol * sizeof(R)), o_cy = take(co * 4), o_ci = take(co * sizeof(R)),
                      o_cl = take(co * sizeof(R));
-        int rc = ensure_io(off);
-        if (rc) return rc;
+        if (d_io.reserve(off) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the host-API staging buffer failed");
         const void *src[6] = {zmid, play, cldfrac, ciwp, clwp, alat};
         const size_t dst[6] = {o_z, o_p, o_f, o_i, o_l, o_a};
         for (int k = 0; k < 6; k++)
             HIPCHK(hipMemcpyAsync(d_io + dst[k], src[k], (k == 5 ? (size_t)ncol : cl) * sizeof(R), hipMemcpyHostToDevice, stream));
-        rc = mcica_dev(stream, ncol, nsubcol, nlay, d_io + o_z, d_io + o_a, doy, d_io + o_p, d_io + o_f, d_io + o_i, d_io + o_l, cwp_tiny, so,
+        const int rc = mcica_dev(stream, ncol, nsubcol, nlay, d_io + o_z, d_io + o_a, doy, d_io + o_p, d_io + o_f, d_io + o_i, d_io + o_l, cwp_tiny, so,
                        (int32_t *)(d_io + o_cy), d_io + o_ci, d_io + o_cl);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(cldy, d_io + o_cy, co * 4, hipMemcpyDeviceToHost, stream));
@@ -2851,8 +2684,9 @@ struct MultiCtx final : geosrad_ctx {
         for (int s = 0; s < nk; s++) if (rc[s]) { last_error = kid[s]->last_error; return rc[s]; }
         return GEOSRAD_OK;
     }
-    static const void *off(const void *p, size_t bytes) { return p ? (const char *)p + bytes : nullptr; }
-    static void *off(void *p, size_t bytes) { return p ? (char *)p + bytes : nullptr; }
+    // a shard's part of a caller's array: its first column lies c0 records in (ArrShape::rec reals each)
+    const void *off(const void *p, int c0, ArrShape s = {1, 1}) const { return p ? (const char *)p + (size_t)c0 * s.rec * (size_t)real_kind : nullptr; }
+    void *off(void *p, int c0, ArrShape s = {1, 1}) const { return p ? (char *)p + (size_t)c0 * s.rec * (size_t)real_kind : nullptr; }
 
     int set_tables_lw(const void *b, size_t n) override { return all([&](geosrad_ctx *k) { return k->set_tables_lw(b, n); }); }
     int set_tables_sw(const void *b, size_t n) override { return all([&](geosrad_ctx *k) { return k->set_tables_sw(b, n); }); }
@@ -2867,11 +2701,10 @@ struct MultiCtx final : geosrad_ctx {
                 int32_t *clearCounts, void *const *out, const int32_t *band_output, void *taug, void *pfracs) override
     {
         if (taug || pfracs) return fail(GEOSRAD_EINVAL, "stage dumps need a single-device context");
-        const size_t E = (size_t)real_kind;
         return run_shards(ncol, [&](geosrad_ctx *k, int c0, int nc) {
             const void *i2[I_NIN]; void *o2[O_NOUT];
-            for (int j = 0; j < I_NIN; j++) i2[j] = off(in[j], (size_t)c0 * E);
-            for (int j = 0; j < O_NOUT; j++) o2[j] = off(out[j], (size_t)c0 * E * ((j == O_OLRB || j == O_DOLRB) ? 16 : 1));
+            for (int j = 0; j < I_NIN; j++) i2[j] = off(in[j], c0, lw_in_shape(j, nlay));
+            for (int j = 0; j < O_NOUT; j++) o2[j] = off(out[j], c0, lw_out_shape(j, nlay));
             return k->lw_host(nc, nlay, dudTs, i2, iceflg, liqflg, dyofyr, cloudLM, cloudMH, clearCounts ? clearCounts + c0 : nullptr, o2,
                               band_output, nullptr, nullptr);
         });
@@ -2881,36 +2714,33 @@ struct MultiCtx final : geosrad_ctx {
                 const void *indsolvar, const void *solcycfrac, void *const *dbg, void *radval) override
     {
         if (dbg) return fail(GEOSRAD_EINVAL, "stage dumps need a single-device context");
-        const size_t E = (size_t)real_kind;
         return run_shards(ncol, [&](geosrad_ctx *k, int c0, int nc) {
             const void *i2[S_NIN]; void *o2[SO_NOUT];
-            for (int j = 0; j < S_NIN; j++) i2[j] = off(in[j], (size_t)c0 * E);
-            for (int j = 0; j < SO_NOUT; j++) o2[j] = off(out[j], (size_t)c0 * E);
+            for (int j = 0; j < S_NIN; j++) i2[j] = off(in[j], c0, sw_in_shape(j, nlay));
+            for (int j = 0; j < SO_NOUT; j++) o2[j] = off(out[j], c0, sw_out_shape(j, nlay));
             return k->sw_host(nc, nlay, scon, adjes, isolvar, i2, iceflg, liqflg, dyofyr, iaer, cloudLM, cloudMH, normFlx,
                               clearCounts ? clearCounts + c0 : nullptr, o2, do_drfband, bndscl, indsolvar, solcycfrac, nullptr,
-                              off(radval, (size_t)c0 * E));
+                              off(radval, c0));
         });
     }
     int irrad_host(int m, int np, const void *const *in, double co2, int trace, int ict, int icb, int ns, int na, int nb, void *const *aer,
                    void *const *out) override
     {
-        const size_t E = (size_t)real_kind;
         return run_shards(m, [&](geosrad_ctx *k, int c0, int nc) {
             const void *i2[C_NIN]; void *a2[3], *o2[CO_NOUT];
-            for (int j = 0; j < C_NIN; j++) i2[j] = off(in[j], (size_t)c0 * E);
-            for (int j = 0; j < 3; j++) a2[j] = off(aer[j], (size_t)c0 * E);
-            for (int j = 0; j < CO_NOUT; j++) o2[j] = off(out[j], (size_t)c0 * E);
+            for (int j = 0; j < C_NIN; j++) i2[j] = off(in[j], c0, ch_in_shape(j, np, ns));
+            for (int j = 0; j < 3; j++) a2[j] = off(aer[j], c0, ch_aer_shape(np, nb));
+            for (int j = 0; j < CO_NOUT; j++) o2[j] = off(out[j], c0, ch_out_shape(j, np));
             return k->irrad_host(nc, np, i2, co2, trace, ict, icb, ns, na, nb, a2, o2);
         });
     }
     int sorad_host(int m, int np, int nb, const void *const *in, double co2, int ict, int icb, const void *hk_uv, const void *hk_ir,
                    void *const *out, int do_drfband) override
     {
-        const size_t E = (size_t)real_kind;
         return run_shards(m, [&](geosrad_ctx *k, int c0, int nc) {
             const void *i2[SI_NIN]; void *o2[SOO_NOUT];
-            for (int j = 0; j < SI_NIN; j++) i2[j] = off(in[j], (size_t)c0 * E);
-            for (int j = 0; j < SOO_NOUT; j++) o2[j] = off(out[j], (size_t)c0 * E);
+            for (int j = 0; j < SI_NIN; j++) i2[j] = off(in[j], c0, so_in_shape(j, np, nb));
+            for (int j = 0; j < SOO_NOUT; j++) o2[j] = off(out[j], c0, so_out_shape(j, np));
             return k->sorad_host(nc, np, nb, i2, co2, ict, icb, hk_uv, hk_ir, o2, do_drfband);
         });
     }
@@ -3043,32 +2873,33 @@ int geosrad_get_overcast(const geosrad_ctx *c) { return c ? c->overcast : 0; }
 
 int geosrad_set_tables_lw(geosrad_ctx *c, const void *blob, size_t n) { return c ? c->set_tables_lw(blob, n) : GEOSRAD_EINVAL; }
 
-static int read_file(geosrad_ctx *c, const char *path, std::vector<char> &buf)
+// a whole coefficient file; false with the reason in err
+static bool read_file(const char *path, std::vector<char> &buf, std::string &err)
 {
     FILE *f = path ? fopen(path, "rb") : nullptr;
-    if (!f) return c->fail(GEOSRAD_ETABLE, std::string("cannot open table file: ") + (path ? path : "(null)"));
+    if (!f) { err = std::string("cannot open table file: ") + (path ? path : "(null)"); return false; }
     fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET);
     buf.resize(n > 0 ? (size_t)n : 0);
     size_t got = n > 0 ? fread(buf.data(), 1, (size_t)n, f) : 0;
     fclose(f);
-    if (got != buf.size()) return c->fail(GEOSRAD_ETABLE, std::string("short read: ") + path);
-    return GEOSRAD_OK;
+    if (got != buf.size()) { err = std::string("short read: ") + path; return false; }
+    return true;
 }
-int geosrad_load_tables_lw(geosrad_ctx *c, const char *path)
+// geosrad_load_*: read the file, hand it to the setter
+static int load_file(geosrad_ctx *c, const char *path, const std::function<int(const void *, size_t)> &set)
 {
     if (!c) return GEOSRAD_EINVAL;
     std::vector<char> buf;
-    int rc = read_file(c, path, buf);
-    return rc ? rc : c->set_tables_lw(buf.data(), buf.size());
+    std::string err;
+    if (!read_file(path, buf, err)) return c->fail(GEOSRAD_ETABLE, err);
+    return set(buf.data(), buf.size());
 }
+int geosrad_load_tables_lw(geosrad_ctx *c, const char *path) { return load_file(c, path, [&](const void *b, size_t n) { return c->set_tables_lw(b, n); }); }
 int geosrad_set_inhomogeneity(geosrad_ctx *c, int ih, const void *blob, size_t n) { return c ? c->set_inhomogeneity(ih, blob, n) : GEOSRAD_EINVAL; }
 int geosrad_load_inhomogeneity(geosrad_ctx *c, int ih, const char *path)
 {
-    if (!c) return GEOSRAD_EINVAL;
-    if (ih == 0) return c->set_inhomogeneity(0, nullptr, 0);
-    std::vector<char> buf;
-    int rc = read_file(c, path, buf);
-    return rc ? rc : c->set_inhomogeneity(ih, buf.data(), buf.size());
+    if (c && ih == 0) return c->set_inhomogeneity(0, nullptr, 0);
+    return load_file(c, path, [&](const void *b, size_t n) { return c->set_inhomogeneity(ih, b, n); });
 }
 int geosrad_set_corr_lengths(geosrad_ctx *c, const double *adl, const double *rdl) { return c ? c->set_corr(adl, rdl) : GEOSRAD_EINVAL; }
 
@@ -3078,14 +2909,10 @@ int geosrad_set_corr_lengths(geosrad_ctx *c, const double *adl, const double *rd
 int geosrad_read_table(const char *path, const char *name, int real_kind, void *dst, size_t count)
 {
     if (!path || !name || !dst || (real_kind != 4 && real_kind != 8)) return GEOSRAD_EINVAL;
-    FILE *f = fopen(path, "rb");
-    if (!f) return GEOSRAD_ETABLE;
-    fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET);
-    std::vector<char> buf(n > 0 ? (size_t)n : 0);
-    const size_t got = n > 0 ? fread(buf.data(), 1, (size_t)n, f) : 0;
-    fclose(f);
+    std::vector<char> buf;
+    std::string err;
     Blob B;
-    if (got != buf.size() || !B.parse(buf.data(), buf.size())) return GEOSRAD_ETABLE;
+    if (!read_file(path, buf, err) || !B.parse(buf.data(), buf.size())) return GEOSRAD_ETABLE;
     auto it = B.e.find(name);
     if (it == B.e.end() || it->second.kind != real_kind || it->second.count != count) return GEOSRAD_ETABLE;
     memcpy(dst, it->second.data, count * (size_t)real_kind);
@@ -3094,13 +2921,7 @@ int geosrad_read_table(const char *path, const char *name, int real_kind, void *
 
 
 int geosrad_set_tables_sw(geosrad_ctx *c, const void *blob, size_t n) { return c ? c->set_tables_sw(blob, n) : GEOSRAD_EINVAL; }
-int geosrad_load_tables_sw(geosrad_ctx *c, const char *path)
-{
-    if (!c) return GEOSRAD_EINVAL;
-    std::vector<char> buf;
-    int rc = read_file(c, path, buf);
-    return rc ? rc : c->set_tables_sw(buf.data(), buf.size());
-}
+int geosrad_load_tables_sw(geosrad_ctx *c, const char *path) { return load_file(c, path, [&](const void *b, size_t n) { return c->set_tables_sw(b, n); }); }
 
 #define SW_PACK()                                                                                                              \
     const void *in[S_NIN] = {play, plev, tlay, h2ovmr, o3vmr, co2vmr, ch4vmr, o2vmr, cld, ciwp, clwp, rei, rel, zm, alat, tauaer,     \
@@ -3241,13 +3062,7 @@ int geosrad_rrtmg_sw_cldprmc(geosrad_ctx *c, int ncol, int nlay, const void *pla
 }
 
 int geosrad_set_tables_chou_lw(geosrad_ctx *c, const void *blob, size_t n) { return c ? c->set_tables_chou_lw(blob, n) : GEOSRAD_EINVAL; }
-int geosrad_load_tables_chou_lw(geosrad_ctx *c, const char *path)
-{
-    if (!c) return GEOSRAD_EINVAL;
-    std::vector<char> buf;
-    int rc = read_file(c, path, buf);
-    return rc ? rc : c->set_tables_chou_lw(buf.data(), buf.size());
-}
+int geosrad_load_tables_chou_lw(geosrad_ctx *c, const char *path) { return load_file(c, path, [&](const void *b, size_t n) { return c->set_tables_chou_lw(b, n); }); }
 
 #define CH_PACK()                                                                                                                   \
     const void *in[C_NIN] = {ple, ta, wa, oa, tb, n2o, ch4, cfc11, cfc12, cfc22, cwc, fcld, reff, fs, tg, eg, tv, ev, rv};             \
@@ -3279,13 +3094,7 @@ int geosrad_irrad_dev(geosrad_ctx *c, void *stream, int m, int np, const void *p
 }
 
 int geosrad_set_tables_chou_sw(geosrad_ctx *c, const void *blob, size_t n) { return c ? c->set_tables_chou_sw(blob, n) : GEOSRAD_EINVAL; }
-int geosrad_load_tables_chou_sw(geosrad_ctx *c, const char *path)
-{
-    if (!c) return GEOSRAD_EINVAL;
-    std::vector<char> buf;
-    int rc = read_file(c, path, buf);
-    return rc ? rc : c->set_tables_chou_sw(buf.data(), buf.size());
-}
+int geosrad_load_tables_chou_sw(geosrad_ctx *c, const char *path) { return load_file(c, path, [&](const void *b, size_t n) { return c->set_tables_chou_sw(b, n); }); }
 
 #define SO_PACK()                                                                                                                    \
     const void *in[SI_NIN] = {cosz, pl, ta, wa, oa, cwc, fcld, reff, taua, ssaa, asya, rsuvbm, rsuvdf, rsirbm, rsirdf};                 \
@@ -3532,9 +3341,9 @@ static __global__ void k_dbg_fast64(int n, const double *__restrict__ a, const d
 int geosrad_dbg_fast64(int n, const double *a, const double *b, double *quot, double *rcp, double *root)
 {
     if (n <= 0 || !a || !b || !quot || !rcp || !root) return GEOSRAD_EINVAL;
-    double *d = nullptr;
+    DevBuf<double> d;
     const size_t nb = (size_t)n * sizeof(double);
-    if (hipMalloc(&d, 5 * nb) != hipSuccess) return GEOSRAD_EHIP;
+    if (d.resize(5 * nb) != hipSuccess) return GEOSRAD_EHIP;
     int rc = GEOSRAD_OK;
     if (hipMemcpy(d, a, nb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d + n, b, nb, hipMemcpyHostToDevice) != hipSuccess) rc = GEOSRAD_EHIP;
     if (rc == GEOSRAD_OK) {
@@ -3542,7 +3351,6 @@ int geosrad_dbg_fast64(int n, const double *a, const double *b, double *quot, do
         if (hipMemcpy(quot, d + 2 * (size_t)n, nb, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(rcp, d + 3 * (size_t)n, nb, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(root, d + 4 * (size_t)n, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = GEOSRAD_EHIP;
     }
-    (void)hipFree(d);
     return rc;
 }
 
@@ -3589,21 +3397,17 @@ int geosrad_clearcounts(geosrad_ctx *c, int ncol, int nsubcol, int nlay, int clo
     if (!c || !cldy || !cnt || ncol <= 0) return GEOSRAD_EINVAL;
     if (cloudLM == cloudMH) return c->fail(GEOSRAD_EINPUT, "invalid pressure super-layers!");
     if (hipSetDevice(c->device) != hipSuccess) return c->fail(GEOSRAD_EHIP, "hipSetDevice");
-    int32_t *d_in = nullptr, *d_out = nullptr;
+    DevBuf<int32_t> d_in, d_out;
     const size_t nin = (size_t)ncol * nsubcol * nlay * 4;
-    if (hipMalloc((void **)&d_in, nin) != hipSuccess || hipMalloc((void **)&d_out, (size_t)ncol * 16) != hipSuccess) {
-        if (d_in) (void)hipFree(d_in);
-        return c->fail(GEOSRAD_ENOMEM, "hipMalloc failed in geosrad_clearcounts");
-    }
+    if (d_in.resize(nin) != hipSuccess || d_out.resize((size_t)ncol * 16) != hipSuccess) return c->fail(GEOSRAD_ENOMEM, "hipMalloc failed in geosrad_clearcounts");
     int rc = GEOSRAD_OK;
     if (hipMemcpy(d_in, cldy, nin, hipMemcpyHostToDevice) != hipSuccess) rc = c->fail(GEOSRAD_EHIP, "hipMemcpy H2D");
     if (!rc) {
         hipLaunchKernelGGL(k_clearcounts, dim3((unsigned)((ncol + 63) / 64)), dim3(64), 0, c->stream, ncol, nsubcol, nlay, cloudLM, cloudMH,
-                           (const int32_t *)d_in, d_out);
+                           (const int32_t *)d_in, d_out.p);
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(cnt, d_out, (size_t)ncol * 16, hipMemcpyDeviceToHost) != hipSuccess)
             rc = c->fail(GEOSRAD_EHIP, "k_clearcounts failed");
     }
-    (void)hipFree(d_in); (void)hipFree(d_out);
     return rc;
 }
 

@@ -199,6 +199,59 @@ def test_chunking_is_invisible(gpu_ctx):
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)
 
 
+@pytest.mark.parametrize("rk", [4, 8])
+def test_taumol_dump_through_ragged_chunks(gpu_ctx, rk):
+    """The stage dump rides the chunk pipeline of the host entry points: taug / pfracs are per-column records of nlay x 140 reals behind
+    the regular outputs.  150 columns as one chunk and as chunks of 64 + 64 + 22 must give the same bits - a wrong record size or chunk
+    offset shows from the second chunk on."""
+    from geosradiation_gridcomp_amd import synth
+    ctx = gpu_ctx[rk]
+    inp = synth.make_columns(150, 72, start=5150, aerosol=True)
+    a = ctx.rrtmg_lw_taumol(inp)
+    try:
+        ctx.set_chunk(64)
+        b = ctx.rrtmg_lw_taumol(inp)
+    finally:
+        ctx.set_chunk(131072)
+    for k, x, y in zip(("taug", "pfracs"), a, b):
+        assert (x[64:] != 0).any() and (x[128:] != 0).any(), k       # every chunk delivered something
+        np.testing.assert_array_equal(x, y, err_msg=k)
+
+
+def test_flagged_stage_dump_call_names_the_input(gpu_ctx):
+    """An input assertion tripped in the second chunk of a stage-dump call (70 columns in chunks of 64 + 6, a negative tlay in column
+    66): the flagged chunk's dump records are not scattered into the caller's arrays and the call raises the reference's message, word
+    for word what it raised before the dumps went through the pipeline.  Through rrtmg_lw_taumol (the C entry point itself, so that
+    the caller's arrays can be looked at after the error) and rrtmg_sw_taumol; the context works afterwards.  (tlay, not play: a
+    negative pressure is a known defect of the RRTMG_LW kernels)"""
+    import ctypes
+    from geosradiation_gridcomp_amd import api, synth
+    from geosradiation_gridcomp_amd.api import GeosradInputError
+    ctx = gpu_ctx[4]
+    n, nlay = 70, 72
+    inp = synth.make_columns(n, nlay, start=5150, aerosol=True)
+    bad = dict(inp); bad["tlay"] = inp["tlay"].copy(); bad["tlay"][10, 66] = -1.0
+    a = {k: np.ascontiguousarray(bad[k], dtype=ctx.dtype) for k in ["play", "plev", "tlay", "tlev", "tsfc", "emis", "tauaer"] + api._IN2D[:10]}
+    taug = np.full((n, 140, nlay), -777.0, dtype=ctx.dtype); pfr = np.full_like(taug, -777.0)
+    P = lambda x: ctypes.c_void_p(x.ctypes.data)
+    try:
+        ctx.set_chunk(64)
+        rc = ctx.L.geosrad_rrtmg_lw_taumol(ctx.h, ctypes.c_int(n), ctypes.c_int(nlay), P(a["play"]), P(a["plev"]), P(a["tlay"]), P(a["tlev"]),
+                                           P(a["tsfc"]), P(a["emis"]), *[P(a[k]) for k in api._IN2D[:10]], P(a["tauaer"]), P(taug), P(pfr))
+        assert rc == 5 and ctx.L.geosrad_last_error(ctx.h).decode() == "negative values in input: tlay"
+        assert (taug[64:] == -777.0).all() and (pfr[64:] == -777.0).all()      # the offending chunk was not delivered
+        with pytest.raises(GeosradInputError) as e:
+            ctx.rrtmg_lw_taumol(bad)
+        assert str(e.value) == "negative values in input: tlay"
+        with pytest.raises(GeosradInputError) as e:
+            ctx.rrtmg_sw_taumol(bad)
+        assert str(e.value) == "negative values in input: tlay"
+        good, _ = ctx.rrtmg_lw_taumol(inp)
+    finally:
+        ctx.set_chunk(131072)
+    assert np.isfinite(good).all() and (good[66] != 0).any()
+
+
 def test_reference_error_stops_become_errors(gpu_ctx):
     from geosradiation_gridcomp_amd.api import GeosradInputError
     ctx = gpu_ctx[4]
@@ -579,6 +632,8 @@ def test_multi_device_context_is_bitwise_the_single_device_one(gpu_ctx):
         a = one.rrtmg_lw_columns(inp, band_output=np.ones(16, np.int32)); b = two.rrtmg_lw_columns(inp, band_output=np.ones(16, np.int32))
         for k in ("uflx", "dflx", "uflxc", "dflxc", "duflx_dTs", "duflxc_dTs", "clearCounts", "olrb", "dolrb_dTs"):
             np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+        # olrb / dolrb_dTs are (16, ncol): the second shard starts 16 reals per column in, the one record offset that is not 1
+        assert (b["olrb"][(n + 1) // 2:] != 0).any(axis=1).all() and (b["dolrb_dTs"][(n + 1) // 2:] != 0).any(axis=1).all()
         a = one.rrtmg_sw_columns(inp, iaer=10, normFlx=1, do_drfband=True); b = two.rrtmg_sw_columns(inp, iaer=10, normFlx=1, do_drfband=True)
         for k in ("swuflx", "swdflx", "swuflxc", "swdflxc", "nirr", "parf", "fswband", "drband", "dfband", "clearCounts", "cotdtp"):
             np.testing.assert_array_equal(a[k], b[k], err_msg=k)

@@ -136,6 +136,27 @@ def test_sw_chunking_and_determinism(gpu_ctx):
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)        # batching is invisible
 
 
+@pytest.mark.parametrize("rk", [4, 8])
+def test_sw_stage_dumps_through_ragged_chunks(gpu_ctx, rk):
+    """The stage dumps ride the chunk pipeline of the host entry points as per-column records behind the regular outputs (taug, taur and
+    the three cldprmc planes nlay x 112 reals, ssi 112).  150 columns as one chunk and as chunks of 64 + 64 + 22 must give the same
+    bits - a wrong record size or chunk offset shows from the second chunk on."""
+    from geosradiation_gridcomp_amd import synth
+    ctx = gpu_ctx[rk]
+    inp = synth.make_columns(150, 72, start=5150, cloudy_frac=0.6)
+    ctx.set_inhomogeneity(1)
+    try:
+        a = list(ctx.rrtmg_sw_taumol(inp, isolvar=0)) + list(ctx.rrtmg_sw_cldprmc(inp))
+        ctx.set_chunk(64)
+        b = list(ctx.rrtmg_sw_taumol(inp, isolvar=0)) + list(ctx.rrtmg_sw_cldprmc(inp))
+    finally:
+        ctx.set_chunk(131072)
+        ctx.set_inhomogeneity(0)
+    for k, x, y in zip(("taug", "taur", "ssi", "taucmc", "ssacmc", "asmcmc"), a, b):
+        assert (x[64:] != 0).any() and (x[128:] != 0).any(), k       # every chunk delivered something
+        np.testing.assert_array_equal(x, y, err_msg=k)
+
+
 def test_sw_reference_error_stops_become_errors(gpu_ctx):
     from geosradiation_gridcomp_amd import synth
     from geosradiation_gridcomp_amd.api import GeosradInputError
