@@ -1,4 +1,4 @@
-// dev_buf.hpp -- the one owner of a device allocation in the host layer (geosrad.hip).
+// dev_buf.hpp -- the one owner of a device allocation (DevBuf) and the one way to cut it into planes (Carve) in geosrad.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +34,21 @@ template <typename T = char> struct DevBuf {
     // at least n bytes: grow-only, a smaller request keeps the allocation
     hipError_t reserve(size_t n) { return n <= bytes ? hipSuccess : resize(n); }
     operator T *() const { return p; }
+};
+
+// Hands out consecutive pieces of one allocation as typed pointers, each starting on a 256-byte boundary of it.  Without a base it only
+// measures: every take returns null, and `off` ends as the bytes the same sequence of takes needs (a zero-count take has an address but
+// no bytes).  A layout is one function of a Carve, run once on Carve() to size the allocation and once on Carve(buffer) to address it.
+struct Carve {
+    char *base;
+    size_t off = 0;
+    explicit Carve(void *b = nullptr) : base((char *)b) {}
+    template <typename T> T *take(size_t count)
+    {
+        const size_t o = off;
+        off += (count * sizeof(T) + 255) & ~(size_t)255;
+        return base ? (T *)(base + o) : nullptr;
+    }
 };
 
 }  // namespace geosrad

@@ -73,11 +73,8 @@ struct Blob {
     }
 };
 
-#define HIPCHK(call)                                                                           \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) { return fail(GEOSRAD_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); } \
-    } while (0)
+// inside a context's member functions: a failed HIP call becomes GEOSRAD_EHIP with the call's text in last_error (geosrad_ctx::hip_rc)
+#define HIPCHK(call) do { if (const int rc_ = hip_rc(#call, (call))) return rc_; } while (0)
 
 // ---- KISS jump-ahead constants (see mcica_kernels.hpp: KissJump) --------------------------------------------
 static uint32_t xs_step(uint32_t x) { x ^= x << 13; x ^= x >> 17; x ^= x << 5; return x; }
@@ -372,6 +369,7 @@ struct geosrad_ctx {
         spans.clear();
     }
     int fail(int code, const std::string &msg) { last_error = msg; return code; }
+    int hip_rc(const char *what, hipError_t e) { return e == hipSuccess ? GEOSRAD_OK : fail(GEOSRAD_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
 
     // ---- host-pointer entry points: chunk pipeline --------------------------------------------------------------------------
     // The reference interface hands over host arrays, Fortran (ncol, rows): column index fastest.  A batch goes through the GPU in
@@ -475,16 +473,15 @@ struct geosrad_ctx {
         };
         layout(cn);
         const size_t total_max = total, in_bytes_max = in_end, out_bytes_max = total - out_begin;
-#define PIPECHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(GEOSRAD_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
         if (!pipe_h2d) {
-            PIPECHK(hipStreamCreateWithFlags(&pipe_h2d, hipStreamNonBlocking));
-            PIPECHK(hipStreamCreateWithFlags(&pipe_d2h, hipStreamNonBlocking));
-            for (int s = 0; s < PIPE_SLOTS; s++) for (int e = 0; e < 3; e++) PIPECHK(hipEventCreateWithFlags(&pipe_ev[s][e], hipEventDisableTiming));
-            PIPECHK(hipHostMalloc((void **)&pipe_err, PIPE_SLOTS * sizeof(uint32_t), hipHostMallocDefault));
+            HIPCHK(hipStreamCreateWithFlags(&pipe_h2d, hipStreamNonBlocking));
+            HIPCHK(hipStreamCreateWithFlags(&pipe_d2h, hipStreamNonBlocking));
+            for (int s = 0; s < PIPE_SLOTS; s++) for (int e = 0; e < 3; e++) HIPCHK(hipEventCreateWithFlags(&pipe_ev[s][e], hipEventDisableTiming));
+            HIPCHK(hipHostMalloc((void **)&pipe_err, PIPE_SLOTS * sizeof(uint32_t), hipHostMallocDefault));
         }
         const size_t pipe_dev_bytes = pipe_dev[0].bytes;
         if (total_max > pipe_dev_bytes || in_bytes_max > pipe_pin_bytes[0] || out_bytes_max > pipe_pin_bytes[1]) {
-            PIPECHK(hipDeviceSynchronize());
+            HIPCHK(hipDeviceSynchronize());
             const size_t want_dev = total_max > pipe_dev_bytes ? total_max : pipe_dev_bytes;
             const size_t want_pin[2] = {in_bytes_max > pipe_pin_bytes[0] ? in_bytes_max : pipe_pin_bytes[0],
                                         out_bytes_max > pipe_pin_bytes[1] ? out_bytes_max : pipe_pin_bytes[1]};
@@ -520,29 +517,29 @@ struct geosrad_ctx {
             if (k < nchunks) {
                 const int s = k % PIPE_SLOTS, c0 = cstart[k], nc = cstart[k + 1] - c0;
                 double t0 = now();
-                if (k >= PIPE_SLOTS) PIPECHK(hipEventSynchronize(pipe_ev[s][0]));   // the slot's previous transfer has left the staging memory
+                if (k >= PIPE_SLOTS) HIPCHK(hipEventSynchronize(pipe_ev[s][0]));   // the slot's previous transfer has left the staging memory
                 double t1 = now(); t_w += t1 - t0;
                 layout(nc);
                 const size_t in_bytes = in_end, out_bytes = total - out_begin;
                 pipe_copy(arrs, pipe_pin[s][0], 0, ld_host, c0, nc, true);
                 t0 = now(); t_g += t0 - t1;
-                if (k >= PIPE_SLOTS) PIPECHK(hipStreamWaitEvent(pipe_h2d, pipe_ev[s][2], 0));   // ... and its previous chunk has been copied out of the device slot
-                if (in_bytes) PIPECHK(hipMemcpyAsync(pipe_dev[s], pipe_pin[s][0], in_bytes, hipMemcpyHostToDevice, pipe_h2d));
-                PIPECHK(hipEventRecord(pipe_ev[s][0], pipe_h2d));
-                PIPECHK(hipStreamWaitEvent(stream, pipe_ev[s][0], 0));
+                if (k >= PIPE_SLOTS) HIPCHK(hipStreamWaitEvent(pipe_h2d, pipe_ev[s][2], 0));   // ... and its previous chunk has been copied out of the device slot
+                if (in_bytes) HIPCHK(hipMemcpyAsync(pipe_dev[s], pipe_pin[s][0], in_bytes, hipMemcpyHostToDevice, pipe_h2d));
+                HIPCHK(hipEventRecord(pipe_ev[s][0], pipe_h2d));
+                HIPCHK(hipStreamWaitEvent(stream, pipe_ev[s][0], 0));
                 const int rc = run(stream, nc, c0, pipe_dev[s], cn);
                 if (rc) { (void)hipDeviceSynchronize(); return rc; }
-                PIPECHK(hipEventRecord(pipe_ev[s][1], stream));
-                PIPECHK(hipStreamWaitEvent(pipe_d2h, pipe_ev[s][1], 0));
-                if (out_bytes) PIPECHK(hipMemcpyAsync(pipe_pin[s][1], pipe_dev[s] + out_begin, out_bytes, hipMemcpyDeviceToHost, pipe_d2h));
-                if (err_dev) PIPECHK(hipMemcpyAsync(&pipe_err[s], err_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, pipe_d2h));
-                PIPECHK(hipEventRecord(pipe_ev[s][2], pipe_d2h));
+                HIPCHK(hipEventRecord(pipe_ev[s][1], stream));
+                HIPCHK(hipStreamWaitEvent(pipe_d2h, pipe_ev[s][1], 0));
+                if (out_bytes) HIPCHK(hipMemcpyAsync(pipe_pin[s][1], pipe_dev[s] + out_begin, out_bytes, hipMemcpyDeviceToHost, pipe_d2h));
+                if (err_dev) HIPCHK(hipMemcpyAsync(&pipe_err[s], err_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, pipe_d2h));
+                HIPCHK(hipEventRecord(pipe_ev[s][2], pipe_d2h));
                 t_e += now() - t0;
             }
             if (k >= PIPE_LAG && k - PIPE_LAG < nchunks) {
                 const int j = k - PIPE_LAG, s = j % PIPE_SLOTS, c0 = cstart[j], nc = cstart[j + 1] - c0;
                 double t0 = now();
-                PIPECHK(hipEventSynchronize(pipe_ev[s][2]));
+                HIPCHK(hipEventSynchronize(pipe_ev[s][2]));
                 double t1 = now(); t_w += t1 - t0;
                 if (err_dev && pipe_err[s]) { input_error = true; break; }      // this chunk (or one enqueued behind it) tripped an input assertion
                 layout(nc);
@@ -550,12 +547,11 @@ struct geosrad_ctx {
                 t_s += now() - t1;
             }
         }
-        if (input_error) { PIPECHK(hipDeviceSynchronize()); return PIPE_FLAGGED; }
+        if (input_error) { HIPCHK(hipDeviceSynchronize()); return PIPE_FLAGGED; }
         if (trace)
             fprintf(stderr, "geosrad host pipeline: %d columns, %d chunks of %d, %.1f MB in / %.1f MB out per chunk: total %.1f ms = gather %.1f + "
                             "scatter %.1f + enqueue %.1f + waiting for the GPU %.1f\n", ncol, nchunks, cn, in_bytes_max / 1e6, out_bytes_max / 1e6,
                     now() - t_begin, t_g, t_s, t_e, t_w);
-#undef PIPECHK
         return GEOSRAD_OK;
     }
     virtual ~geosrad_ctx() { pipe_release(); }
@@ -937,47 +933,67 @@ template <typename R> struct Ctx : geosrad_ctx {
     }
 
     // ---- workspace -------------------------------------------------------------------------------------
-    struct Ws { R *sc; uint32_t *scidx; R *pwvcm; uint8_t *colcloudy, *laycloudy; int32_t *perm, *nclear; R *taucmc, *alpha, *rcorr; uint16_t *s1, *s2; R *part;
-                uint32_t *pfcode; R *pffs; };
-    static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-    size_t ws_layout(int nc, int nlay, Ws *w, char *base) const
+    // the LW workspace of nc columns, straight into the kernels' arguments: on Carve() the bytes it takes, on Carve(d_ws) its planes
+    size_t ws_layout(int nc, int nlay, LwArgs<R> &w, Carve c) const
     {
-        size_t off = 0;
-        auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return base ? base + o : (char *)nullptr; };
         const size_t cl = (size_t)nlay * nc;
-        char *p;
-        p = take(SC_NFIELD * cl * sizeof(R)); if (w) w->sc = (R *)p;
-        p = take(cl * 4); if (w) w->scidx = (uint32_t *)p;
-        p = take((size_t)nc * sizeof(R)); if (w) w->pwvcm = (R *)p;
-        p = take(nc); if (w) w->colcloudy = (uint8_t *)p;
-        p = take((size_t)nc * 4); if (w) w->perm = (int32_t *)p;
-        p = take(4); if (w) w->nclear = (int32_t *)p;
-        p = take(cl); if (w) w->laycloudy = (uint8_t *)p;
-        p = take(cl * sizeof(R)); if (w) w->alpha = (R *)p;
-        p = take(cl * sizeof(R)); if (w) w->rcorr = (R *)p;
-        p = take(NG_LW * cl * sizeof(R)); if (w) w->taucmc = (R *)p;
+        w.sc = c.take<R>(SC_NFIELD * cl);
+        w.scidx = c.take<uint32_t>(cl);
+        w.pwvcm = c.take<R>(nc);
+        w.colcloudy = c.take<uint8_t>(nc);
+        w.perm = c.take<int32_t>(nc);
+        w.nclear = c.take<int32_t>(1);
+        w.laycloudy = c.take<uint8_t>(cl);
+        w.alpha = c.take<R>(cl);
+        w.rcorr = c.take<R>(cl);
+        w.taucmc = c.take<R>(NG_LW * cl);
         const size_t clp = (size_t)nlay * (((size_t)nc + 255) & ~(size_t)255);      // tiled by 256-column block
         // parked cells of the band sweeps: a 2-byte Pade index per (layer, g-point) and stream (lw_kernels.hpp band_body)
-        p = take(NG_LW * clp * sizeof(uint16_t)); if (w) w->s1 = (uint16_t *)p;
-        p = take(NG_LW * clp * sizeof(uint16_t)); if (w) w->s2 = (uint16_t *)p;
-        p = take((size_t)6 * NB_LW * (nlay + 1) * nc * sizeof(R)); if (w) w->part = (R *)p;
+        w.s1 = c.take<uint16_t>(NG_LW * clp);
+        w.s2 = c.take<uint16_t>(NG_LW * clp);
+        w.part = c.take<R>((size_t)6 * NB_LW * (nlay + 1) * nc);
         // split path: the Planck-fraction selector of every (band, layer, column) (lw_split_kernels.hpp)
-        p = take(lw_split_path ? NB_LW * cl * 4 : 0); if (w) w->pfcode = (uint32_t *)p;
-        p = take(lw_split_path ? NB_LW * cl * sizeof(R) : 0); if (w) w->pffs = (R *)p;
-        return off;
+        w.pfcode = c.take<uint32_t>(lw_split_path ? NB_LW * cl : 0);
+        w.pffs = c.take<R>(lw_split_path ? NB_LW * cl : 0);
+        return c.off;
     }
     int ensure_ws(int nc, int nlay)
     {
         if (d_ws && nc <= ws_ncol && nlay == ws_nlay) return GEOSRAD_OK;
         // grow-only in columns for a given nlay
         const int want = (d_ws && nlay == ws_nlay && nc < ws_ncol) ? ws_ncol : nc;
-        const size_t need = ws_layout(want, nlay, nullptr, nullptr);
+        LwArgs<R> w;
+        const size_t need = ws_layout(want, nlay, w, Carve());
         if (d_ws.resize(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the LW workspace failed (" + std::to_string(need >> 20) +
                                                          " MiB); lower it with geosrad_set_chunk()");
         ws_ncol = want; ws_nlay = nlay;
         return GEOSRAD_OK;
     }
 
+    // ---- what every `_dev` entry point is made of ------------------------------------------------------------------------
+    static unsigned grid256(size_t n) { return (unsigned)((n + 255) / 256); }      // 256-thread blocks over n items
+    // a caller's array from column c0 on; an array that is not there stays null
+    static const R *colp(const void *p, size_t c0) { return p ? (const R *)p + c0 : nullptr; }
+    static R *colp(void *p, size_t c0) { return p ? (R *)p + c0 : nullptr; }
+    // columns a solver takes at once: the context's chunk, below `cap` where 32-bit byte offsets into one workspace plane set one
+    int chunk_cols(int n, long cap = 0x7FFFFFFFL) const { const long nc = n < chunk ? n : chunk; return (int)(nc > cap ? cap : nc); }
+    // body(c0, nc) for every chunk of [0, n), then the launches' status; a body that returns non-zero ends the walk with that code
+    template <typename F> int chunk_walk(int n, int nc_max, F &&body)
+    {
+        for (int c0 = 0; c0 < n; c0 += nc_max)
+            if (const int rc = body(c0, (n - c0) < nc_max ? (n - c0) : nc_max)) return rc;
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+    // 16-byte accesses (VW reals per thread) when the column count and every address of the listed pointer arrays allow
+    static constexpr int VW = 16 / (int)sizeof(R);
+    struct PtrList { const void *const *p; int n; };
+    static bool wide16(int ncol, std::initializer_list<PtrList> lists)
+    {
+        bool wide = ncol % VW == 0;
+        for (const PtrList &l : lists) for (int k = 0; k < l.n; k++) wide = wide && ((uintptr_t)l.p[k] & 15) == 0;
+        return wide;
+    }
 
     // quads of sub-columns that never straddle a band; jump distances in units of draws
     int mc_plan(int mode, int nsubcol, int nlay, McPlan &out, int &nseg_out)
@@ -1013,6 +1029,94 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 
+    // The front end of both RRTMG solvers for one chunk, MODE 0: RRTMG_LW (A: LwArgs), 2: RRTMG_SW (A: SwArgs) - input assertions and the
+    // clear | cloudy partition in one profile slot, setcoef, the overlap correlations, the McICA sub-columns with their cloud optics
+    // (threads of clear columns exit at once).  radval: the RADVAL instantiation of the generator, which also fills rvsum.
+    template <int MODE, typename Args> int rrtmg_front(hipStream_t st, const Args &A, bool radval = false, R *rvsum = nullptr)
+    {
+        constexpr bool SW = MODE == 2;
+        const dim3 blk(256);
+        const unsigned gx = grid256(A.ncol);
+        const LwDev<R> *dT = d_T;
+        const SwDev<R> *dS = SW ? (const SwDev<R> *)d_S : nullptr;
+        span_begin(SW ? 6 : 0, st);
+        if constexpr (SW) {
+            hipLaunchKernelGGL(k_sw_validate<R>, dim3(gx), blk, 0, st, A);
+            if (A.iaer == 10) hipLaunchKernelGGL(k_sw_validate_aer<R>, dim3(gx, A.nlay), blk, 0, st, A);
+        } else hipLaunchKernelGGL(k_validate_pwv<R>, dim3(gx), blk, 0, st, A, d_T);
+        hipLaunchKernelGGL(k_partition, dim3(1), dim3(1024), 0, st, A.ncol, (const uint8_t *)A.colcloudy, A.perm, A.nclear);
+        span_end(st);
+        span_begin(SW ? 7 : 1, st);
+        if constexpr (SW) hipLaunchKernelGGL(k_sw_setcoef<R>, dim3(gx, A.nlay), blk, 0, st, A, dS);
+        else hipLaunchKernelGGL(k_setcoef<R>, dim3(gx, A.nlay), blk, 0, st, A, d_T);
+        span_end(st);
+        span_begin(2, st);
+        hipLaunchKernelGGL(k_overlap<R>, dim3(gx, A.nlay), blk, 0, st, A.ncol, A.ld, A.nlay, A.doy, A.zm, A.alat, (const int32_t *)A.perm,
+                           (const int32_t *)A.nclear, dT, A.alpha, A.rcorr, A.laycloudy);
+        span_end(st);
+        McArgs<R> M{};
+        M.ncol = A.ncol; M.ld = A.ld; M.nlay = A.nlay; M.nsubcol = SW ? NG_SW : NG_LW; M.doy = A.doy; M.cloudLM = A.cloudLM; M.cloudMH = A.cloudMH;
+        M.iceflg = A.iceflg; M.liqflg = A.liqflg;
+        // seed_order = [1,2,3,4] (rrtmg_lw_rad.F90:546) | [4,3,2,1] (SW/rrtmg_sw_rad.F90:1401)
+        for (int k = 0; k < 4; k++) M.so[k] = SW ? 4 - k : 1 + k;
+        M.cwp_tiny = (R)1.e-20;                                       // rrtmg_lw_rad.F90:544
+        M.play = A.play; M.ciwp = A.ciwp; M.clwp = A.clwp; M.rei = A.rei; M.rel = A.rel;
+        M.alpha = A.alpha; M.rcorr = A.rcorr; M.perm = A.perm; M.nclear = A.nclear; M.cftop = A.colcloudy;
+        M.taucmc = A.taucmc; M.laycloudy = A.laycloudy; M.clearCounts = A.clearCounts; M.err = A.err;
+        if constexpr (SW) { M.cldf = A.cld; M.ssacmc = A.ssacmc; M.asmcmc = A.asmcmc; M.cotsum = A.cotsum; M.rvsum = rvsum; }
+        else M.cldf = A.cldf;
+        McPlan MP; int nseg = 0;
+        if (const int rc = mc_plan(MODE, M.nsubcol, A.nlay, MP, nseg)) return rc;
+        const dim3 grid(xcd_grid(A.ncol, 64, nseg));
+        span_begin(3, st);
+        if constexpr (SW) {
+            if (radval) hipLaunchKernelGGL((k_mcica<R, 2, true>), grid, dim3(64), 0, st, M, MP, dT, dS);
+            else hipLaunchKernelGGL((k_mcica<R, 2>), grid, dim3(64), 0, st, M, MP, dT, dS);
+        } else hipLaunchKernelGGL((k_mcica<R, 0>), grid, dim3(64), 0, st, M, MP, dT, dS);
+        span_end(st);
+        return GEOSRAD_OK;
+    }
+
+    // RRTMG_LW band sweeps of one chunk and the band reduction behind them.  lw_cols: (layer, g-point) intermediates in LDS, fluxes written
+    // directly (lw_cols_kernels.hpp), no reduction; with A.dbg_taug the stage-dump instantiation; lw_split; else lw_bands: lane = column
+    // with the parked cells (2-byte Pade indices) in HBM.  allow_cols: false for a call with RATS diagnostics, whose passes need the
+    // per-band partials of the reduction - such a call takes that path throughout.  O.part_alt: the pass's own partials (RATS).
+    int lw_sweeps(hipStream_t st, const LwArgs<R> &A, const LwOut<R> &O, bool allow_cols)
+    {
+        const dim3 blk(256);
+        const unsigned gx = grid256(A.ncol);
+        const size_t lds = lw_bands_lds_bytes<R>();
+        const bool cols = lw_cols_path && allow_cols;
+        LwArgs<R> S = A;      // a RATS pass sweeps into the partials its reduction takes the gas's bands from, and reduces with A's
+        if (O.part_alt) S.part = const_cast<R *>(O.part_alt);
+        span_begin(4, st);
+        if (cols) {
+            if (const int rc = hip_rc("lw_cols_launch", lw_cols_launch<R>(st, S, O, h_T, A.dbg_taug != nullptr))) return rc;
+        } else if (A.dbg_taug) {
+            hipLaunchKernelGGL((k_lw_bands<R, true, true>), dim3(gx, NB_LW), blk, lds, st, S, h_T);
+        } else if (lw_split_path) {
+            if (const int rc = hip_rc("lw_split_launch", lw_split_launch<R>(st, S, h_T))) return rc;
+        } else {
+            // (both instantiations band-major, heaviest band first: see band_block in lw_kernels.hpp)
+            hipLaunchKernelGGL((k_lw_bands<R, false, false>), dim3(gx, NB_LW), blk, lds, st, S, h_T);
+            if constexpr (sizeof(R) == 4)      // the 768-thread cloud-free blocks: run instead of the 256-thread ones when the batch has many cloud-free columns
+                hipLaunchKernelGGL((k_lw_bands<R, false, false, LW_WIDE_BLOCK>), dim3((unsigned)((A.ncol + LW_WIDE_BLOCK - 1) / LW_WIDE_BLOCK), NB_LW),
+                                   dim3(LW_WIDE_BLOCK), lds, st, S, h_T);
+            hipLaunchKernelGGL((k_lw_bands<R, true, false>), dim3(gx, NB_LW), blk, lds, st, S, h_T);
+        }
+        span_end(st);
+        if (!cols) { span_begin(5, st); hipLaunchKernelGGL(k_lw_reduce<R>, dim3(gx, A.nlay + 1), blk, 0, st, A, O); span_end(st); }
+        return GEOSRAD_OK;
+    }
+
+    // the array checks lw_host makes before it stages anything and lw_dev makes in its own order
+    int lw_check_arrays(const void *const *in, void *const *out)
+    {
+        for (int k = 0; k < I_NIN; k++) if (!in[k] && k != I_TAUAER) return fail(GEOSRAD_EINVAL, "null input array");
+        for (int k = 0; k < 4; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
+        return GEOSRAD_OK;
+    }
+
     // ---- RRTMG_LW, device pointers ---------------------------------------------------------------------------
     int lw_dev(hipStream_t st, int ncol, int nlay, int dudTs, const void *const *in, int iceflg, int liqflg, int dyofyr,
                int cloudLM, int cloudMH, int32_t *clearCounts, void *const *out, const int32_t *band_output, void *dbg_taug,
@@ -1025,9 +1129,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (iceflg < 0 || iceflg > 4) return fail(GEOSRAD_EINPUT, "cldprmc: invalid iceflag");
         if (liqflg != 1) return fail(GEOSRAD_EINPUT, "cldprmc: invalid liqflag");
         if (cloudLM == cloudMH) return fail(GEOSRAD_EINPUT, "invalid pressure super-layers!");
-        for (int k = 0; k < I_NIN; k++)
-            if (!in[k] && k != I_TAUAER) return fail(GEOSRAD_EINVAL, "null input array");
-        for (int k = 0; k < 4; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
+        if (const int rc = lw_check_arrays(in, out)) return rc;
         if (dudTs && (!out[O_DUFLX] || !out[O_DUFLXC])) return fail(GEOSRAD_EINVAL, "dudTs set but duflx_dTs/duflxc_dTs null");
         bool any_bo = false;
         LwOut<R> O{};
@@ -1035,100 +1137,49 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (any_bo && (!out[O_OLRB] || (dudTs && !out[O_DOLRB]))) return fail(GEOSRAD_EINVAL, "band_output set but olrb/dolrb_dTs null");
 
         // one band's [layer][g<=16][column] plane of (a,bbu) pairs must stay below 4 GiB (32-bit byte offsets)
-        const long cap = (long)(0xFFFFFFFFull / ((unsigned long long)nlay * 16ull * sizeof(R2))) & ~255L;
-        int nc_max = ncol < chunk ? ncol : chunk;
-        if ((long)nc_max > cap) nc_max = (int)cap;
-        int rc = ensure_ws(nc_max, nlay);
-        if (rc) return rc;
-        R *rat_part = nullptr;
-        if (rats && rats->n > 0) {
-            if (rats->n > GEOSRAD_RAT_NGAS || !rats->uflx || !rats->dflx || (dudTs && !rats->duflx_dTs))
+        const int nc_max = chunk_cols(ncol, (long)(0xFFFFFFFFull / ((unsigned long long)nlay * 16ull * sizeof(R2))) & ~255L);
+        if (const int rc = ensure_ws(nc_max, nlay)) return rc;
+        const int nrats = rats ? rats->n : 0;
+        R *zero = nullptr, *rat_part = nullptr;
+        if (nrats > 0) {
+            if (nrats > GEOSRAD_RAT_NGAS || !rats->uflx || !rats->dflx || (dudTs && !rats->duflx_dTs))
                 return fail(GEOSRAD_EINVAL, "RATS: at most 8 gases; uflx_rat / dflx_rat (and duflx_dTs_rat with dudTs) must not be null");
-            for (int r = 0; r < rats->n; r++)
+            for (int r = 0; r < nrats; r++)
                 if (rats->gas[r] < 0 || rats->gas[r] >= GEOSRAD_RAT_NGAS) return fail(GEOSRAD_EINVAL, "RATS: unknown gas code");
             // an all-zero (nlay, ncol) plane stands for the removed gas's mixing ratio (and for pwvcm of a dry column); behind it
             // a second set of band partials, so that the main call's stay available to the bands a gas does not touch
-            const size_t zplane = al((size_t)nlay * ncol * sizeof(R));
-            const size_t need = zplane + (size_t)6 * NB_LW * (nlay + 1) * nc_max * sizeof(R);
-            if (d_zero.reserve(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the RATS workspace failed");
-            HIPCHK(hipMemsetAsync(d_zero, 0, zplane, st));
-            rat_part = (R *)(d_zero + zplane);
+            auto carve = [&](Carve c) {
+                zero = c.take<R>((size_t)nlay * ncol);
+                rat_part = c.take<R>((size_t)6 * NB_LW * (nlay + 1) * nc_max);
+                return c.off;
+            };
+            if (d_zero.reserve(carve(Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the RATS workspace failed");
+            carve(Carve(d_zero));
+            HIPCHK(hipMemsetAsync(zero, 0, (char *)rat_part - (char *)zero, st));
         }
 
-        for (int c0 = 0; c0 < ncol; c0 += nc_max) {
-            const int nc = (ncol - c0) < nc_max ? (ncol - c0) : nc_max;
-            Ws w;
-            ws_layout(nc, nlay, &w, d_ws);
+        return chunk_walk(ncol, nc_max, [&](int c0, int nc) -> int {
             LwArgs<R> A{};
+            ws_layout(nc, nlay, A, Carve(d_ws));
             A.ncol = nc; A.ld = ncol; A.nlay = nlay; A.dudTs = dudTs; A.iceflg = iceflg; A.liqflg = liqflg; A.doy = dyofyr;
             A.cloudLM = cloudLM; A.cloudMH = cloudMH;
-            auto P = [&](int k) { return in[k] ? (const R *)in[k] + c0 : (const R *)nullptr; };
+            auto P = [&](int k) { return colp(in[k], c0); };
             A.play = P(I_PLAY); A.plev = P(I_PLEV); A.tlay = P(I_TLAY); A.tlev = P(I_TLEV); A.tsfc = P(I_TSFC); A.emis = P(I_EMIS);
             A.h2o = P(I_H2O); A.o3 = P(I_O3); A.co2 = P(I_CO2); A.ch4 = P(I_CH4); A.n2o = P(I_N2O); A.o2 = P(I_O2);
             A.cfc11 = P(I_CFC11); A.cfc12 = P(I_CFC12); A.cfc22 = P(I_CFC22); A.ccl4 = P(I_CCL4);
             A.cldf = P(I_CLDF); A.ciwp = P(I_CIWP); A.clwp = P(I_CLWP); A.rei = P(I_REI); A.rel = P(I_REL);
             A.tauaer = P(I_TAUAER); A.zm = P(I_ZM); A.alat = P(I_ALAT);
-            A.sc = w.sc; A.scidx = w.scidx; A.pwvcm = w.pwvcm; A.colcloudy = w.colcloudy; A.perm = w.perm; A.nclear = w.nclear; A.laycloudy = w.laycloudy;
-            A.taucmc = w.taucmc; A.alpha = w.alpha; A.rcorr = w.rcorr; A.s1 = w.s1; A.s2 = w.s2; A.part = w.part;
-            A.pfcode = w.pfcode; A.pffs = w.pffs;
             A.err = d_err;
-            A.dbg_taug = dbg_taug ? (R *)dbg_taug + (size_t)c0 * NG_LW * nlay : nullptr;
-            A.dbg_pfracs = dbg_pfracs ? (R *)dbg_pfracs + (size_t)c0 * NG_LW * nlay : nullptr;
+            A.dbg_taug = colp(dbg_taug, (size_t)c0 * NG_LW * nlay);
+            A.dbg_pfracs = colp(dbg_pfracs, (size_t)c0 * NG_LW * nlay);
             A.clearCounts = clearCounts + c0;
             A.band_mask = LW_ALL_BANDS;
-
-            const dim3 blk(256);
-            const unsigned gx = (unsigned)((nc + 255) / 256);
-            span_begin(0, st); hipLaunchKernelGGL(k_validate_pwv<R>, dim3(gx), blk, 0, st, A, d_T);
-            hipLaunchKernelGGL(k_partition, dim3(1), dim3(1024), 0, st, nc, (const uint8_t *)w.colcloudy, w.perm, w.nclear); span_end(st);
-            span_begin(1, st); hipLaunchKernelGGL(k_setcoef<R>, dim3(gx, nlay), blk, 0, st, A, d_T); span_end(st);
-            // McICA + cloud optics (threads of clear columns exit at once)
-            span_begin(2, st); hipLaunchKernelGGL(k_overlap<R>, dim3(gx, nlay), blk, 0, st, nc, ncol, nlay, dyofyr, A.zm, A.alat,
-                               (const int32_t *)w.perm, (const int32_t *)w.nclear, (const LwDev<R> *)d_T, A.alpha, A.rcorr, A.laycloudy); span_end(st);
-            McArgs<R> M{};
-            M.ncol = nc; M.ld = ncol; M.nlay = nlay; M.nsubcol = NG_LW; M.doy = dyofyr; M.cloudLM = cloudLM; M.cloudMH = cloudMH;
-            M.iceflg = iceflg; M.liqflg = liqflg;
-            M.so[0] = 1; M.so[1] = 2; M.so[2] = 3; M.so[3] = 4;        // seed_order=[1,2,3,4] (rrtmg_lw_rad.F90:546)
-            M.cwp_tiny = (R)1.e-20;                                       // rrtmg_lw_rad.F90:544
-            M.play = A.play; M.cldf = A.cldf; M.ciwp = A.ciwp; M.clwp = A.clwp; M.rei = A.rei; M.rel = A.rel;
-            M.alpha = A.alpha; M.rcorr = A.rcorr; M.perm = w.perm; M.nclear = w.nclear; M.cftop = w.colcloudy;
-            M.taucmc = A.taucmc; M.laycloudy = A.laycloudy; M.clearCounts = A.clearCounts; M.err = d_err;
-            {
-                McPlan MP; int nseg = 0;
-                rc = mc_plan(0, NG_LW, nlay, MP, nseg);
-                if (rc) return rc;
-                span_begin(3, st);
-                hipLaunchKernelGGL((k_mcica<R, 0>), dim3(xcd_grid(nc, 64, nseg)), dim3(64), 0, st, M, MP, (const LwDev<R> *)d_T, (const SwDev<R> *)nullptr);
-                span_end(st);
-            }
-            auto Q = [&](int k) { return out[k] ? (R *)out[k] + c0 : (R *)nullptr; };
+            if (const int e = rrtmg_front<0>(st, A)) return e;
+            auto Q = [&](int k) { return colp(out[k], c0); };
             O.uflx = Q(O_UFLX); O.dflx = Q(O_DFLX); O.uflxc = Q(O_UFLXC); O.dflxc = Q(O_DFLXC);
             O.duflx_dTs = Q(O_DUFLX); O.duflxc_dTs = Q(O_DUFLXC);
             O.olrb = (R *)out[O_OLRB]; O.dolrb_dTs = (R *)out[O_DOLRB]; O.col0 = c0;
-            const size_t lds = lw_bands_lds_bytes<R>();
-            // band sweeps.  lw_cols: (layer, g-point) intermediates in LDS, fluxes written directly (lw_cols_kernels.hpp);
-            // lw_bands: lane = column with the parked cells (2-byte Pade indices) in HBM + the band reduction (the RATS passes need its per-band
-            // partials, so a call with RATS diagnostics takes that path throughout)
-            const bool cols = lw_cols_path && !(rats && rats->n > 0);
-            span_begin(4, st);
-            if (cols) {
-                hipError_t e = lw_cols_launch<R>(st, A, O, h_T, A.dbg_taug != nullptr);
-                if (e != hipSuccess) return fail(GEOSRAD_EHIP, std::string("lw_cols_launch: ") + hipGetErrorString(e));
-            } else if (A.dbg_taug) {
-                hipLaunchKernelGGL((k_lw_bands<R, true, true>), dim3(gx, NB_LW), blk, lds, st, A, h_T);
-            } else if (lw_split_path) {
-                hipError_t e = lw_split_launch<R>(st, A, h_T);
-                if (e != hipSuccess) return fail(GEOSRAD_EHIP, std::string("lw_split_launch: ") + hipGetErrorString(e));
-            } else {
-                // (both instantiations band-major, heaviest band first: see band_block in lw_kernels.hpp)
-                hipLaunchKernelGGL((k_lw_bands<R, false, false>), dim3(gx, NB_LW), blk, lds, st, A, h_T);
-                if constexpr (sizeof(R) == 4)      // the 768-thread cloud-free blocks: run instead of the 256-thread ones when the batch has many cloud-free columns
-                    hipLaunchKernelGGL((k_lw_bands<R, false, false, LW_WIDE_BLOCK>), dim3((unsigned)((nc + LW_WIDE_BLOCK - 1) / LW_WIDE_BLOCK), NB_LW),
-                                       dim3(LW_WIDE_BLOCK), lds, st, A, h_T);
-                hipLaunchKernelGGL((k_lw_bands<R, true, false>), dim3(gx, NB_LW), blk, lds, st, A, h_T);
-            }
-            span_end(st);
-            if (!cols) { span_begin(5, st); hipLaunchKernelGGL(k_lw_reduce<R>, dim3(gx, nlay + 1), blk, 0, st, A, O); span_end(st); }
+            if (const int e = lw_sweeps(st, A, O, nrats <= 0)) return e;
 
             // RATS diagnostics (GEOS_IrradGridComp.F90:3405-3468): the reference calls the whole of rrtmg_lw once more per listed
             // gas with that gas's mixing ratio set to zero and keeps the total-sky uflx, dflx, duflx_dTs of each call.  Nothing
@@ -1138,46 +1189,25 @@ template <typename R> struct Ctx : geosrad_ctx {
             // the gas appears in are swept again (LW_RAT_BANDS, lw_device.hpp): their partials go to a second buffer and the
             // reduction takes every other band's from the main call.  Without water vapour the precipitable water
             // (rrtmg_lw_setcoef.F90:206-272) is 0 / amttl = exactly zero.
-            for (int r = 0; rats && r < rats->n; r++) {
+            for (int r = 0; r < nrats; r++) {
+                static const R *LwArgs<R>::*const GAS[GEOSRAD_RAT_NGAS] = {&LwArgs<R>::h2o, &LwArgs<R>::o3, &LwArgs<R>::co2, &LwArgs<R>::ch4, &LwArgs<R>::n2o,
+                                                                           &LwArgs<R>::cfc11, &LwArgs<R>::cfc12, &LwArgs<R>::cfc22};      // GEOSRAD_RAT_* order
+                static_assert(GEOSRAD_RAT_H2O == 0 && GEOSRAD_RAT_N2O == 4 && GEOSRAD_RAT_HCFC22 == 7 && GEOSRAD_RAT_NGAS == 8, "GAS follows GEOSRAD_RAT_*");
                 LwArgs<R> B = A;
-                const R *z = (const R *)d_zero.p;
-                switch (rats->gas[r]) {
-                case GEOSRAD_RAT_H2O: B.h2o = z; B.pwvcm = (R *)d_zero.p; break;      // pwvcm is only read from here on
-                case GEOSRAD_RAT_O3: B.o3 = z; break;
-                case GEOSRAD_RAT_CO2: B.co2 = z; break;
-                case GEOSRAD_RAT_CH4: B.ch4 = z; break;
-                case GEOSRAD_RAT_N2O: B.n2o = z; break;
-                case GEOSRAD_RAT_CFC11: B.cfc11 = z; break;
-                case GEOSRAD_RAT_CFC12: B.cfc12 = z; break;
-                default: B.cfc22 = z; break;
-                }
+                B.*GAS[rats->gas[r]] = zero;
+                if (rats->gas[r] == GEOSRAD_RAT_H2O) B.pwvcm = zero;      // pwvcm is only read from here on
                 B.dbg_taug = nullptr; B.dbg_pfracs = nullptr;
                 B.band_mask = LW_RAT_BANDS[rats->gas[r]];
-                B.part = rat_part;
-                span_begin(1, st); hipLaunchKernelGGL(k_setcoef<R>, dim3(gx, nlay), blk, 0, st, B, d_T); span_end(st);
-                span_begin(4, st);
-                if (lw_split_path) {
-                    hipError_t e = lw_split_launch<R>(st, B, h_T);
-                    if (e != hipSuccess) return fail(GEOSRAD_EHIP, std::string("lw_split_launch: ") + hipGetErrorString(e));
-                } else {
-                hipLaunchKernelGGL((k_lw_bands<R, false, false>), dim3(gx, NB_LW), blk, lds, st, B, h_T);
-                if constexpr (sizeof(R) == 4)
-                    hipLaunchKernelGGL((k_lw_bands<R, false, false, LW_WIDE_BLOCK>), dim3((unsigned)((nc + LW_WIDE_BLOCK - 1) / LW_WIDE_BLOCK), NB_LW),
-                                       dim3(LW_WIDE_BLOCK), lds, st, B, h_T);
-                hipLaunchKernelGGL((k_lw_bands<R, true, false>), dim3(gx, NB_LW), blk, lds, st, B, h_T);
-                }
-                span_end(st);
+                span_begin(1, st); hipLaunchKernelGGL(k_setcoef<R>, dim3(grid256(nc), nlay), dim3(256), 0, st, B, d_T); span_end(st);
                 LwOut<R> OR{};
                 const size_t ro = (size_t)r * (nlay + 1) * ncol + c0;
                 OR.uflx = (R *)rats->uflx + ro; OR.dflx = (R *)rats->dflx + ro;
                 OR.duflx_dTs = rats->duflx_dTs ? (R *)rats->duflx_dTs + ro : nullptr;
                 OR.col0 = c0; OR.part_alt = rat_part; OR.alt_mask = B.band_mask;
-                B.part = A.part;
-                span_begin(5, st); hipLaunchKernelGGL(k_lw_reduce<R>, dim3(gx, nlay + 1), blk, 0, st, B, OR); span_end(st);
+                if (const int e = lw_sweeps(st, B, OR, false)) return e;
             }
-        }
-        HIPCHK(hipGetLastError());
-        return GEOSRAD_OK;
+            return GEOSRAD_OK;
+        });
     }
 
     // ---- GridComp drivers (gridcomp_kernels.hpp) ---------------------------------------------------------------------------
@@ -1198,20 +1228,20 @@ template <typename R> struct Ctx : geosrad_ctx {
             if (!in[k] && k != GEOSRAD_LWD_CO2_3D && k != GEOSRAD_LWD_TAUA && k != GEOSRAD_LWD_SSAA) return fail(GEOSRAD_EINVAL, "null input array");
         if ((in[GEOSRAD_LWD_TAUA] == nullptr) != (in[GEOSRAD_LWD_SSAA] == nullptr)) return fail(GEOSRAD_EINVAL, "TAUA and SSAA go together");
         const size_t n = (size_t)ncol, cl = n * lm, cv = n * (lm + 1);
-        size_t off = 0;
-        auto take = [&](size_t nreal) { size_t o = off; off += al(nreal * sizeof(R)); return o; };
-        size_t o_lay[18], o_lev[2], o_flux[6];
-        for (auto &o : o_lay) o = take(cl);
-        for (auto &o : o_lev) o = take(cv);
-        const size_t o_tsfc = take(n), o_alat = take(n), o_emis = take(n * 16), o_aer = take(cl * 16);
-        for (auto &o : o_flux) o = take(cv);
-        const size_t o_olrb = take(n * 16), o_dolrb = take(n * 16), o_cc = take(n * 4);
-        size_t o_rat[3] = {0, 0, 0};
-        for (auto &o : o_rat) o = take(cv * (size_t)nrats);
-        int rc = drv_reserve(0, off);
-        if (rc) return rc;
-        char *const d_ws_drv = d_ws_drvs[0];
-        auto P = [&](size_t o) { return (R *)(d_ws_drv + o); };
+        R *lay[18], *lev[2], *tsfc, *alat, *emis, *aerp, *flux[6], *olrb, *dolrb, *rat[3];
+        int32_t *cc;
+        auto carve = [&](Carve c) {
+            for (auto &q : lay) q = c.take<R>(cl);
+            for (auto &q : lev) q = c.take<R>(cv);
+            tsfc = c.take<R>(n); alat = c.take<R>(n); emis = c.take<R>(n * 16); aerp = c.take<R>(cl * 16);
+            for (auto &q : flux) q = c.take<R>(cv);
+            olrb = c.take<R>(n * 16); dolrb = c.take<R>(n * 16);
+            cc = (int32_t *)c.take<R>(n * 4);      // clearCounts (ncol, 4) int32 in 4 n reals: twice the bytes in fp64, kept so that the layout stays as it was
+            for (auto &q : rat) q = c.take<R>(cv * (size_t)nrats);
+            return c.off;
+        };
+        if (const int rc = drv_reserve(0, carve(Carve()))) return rc;
+        carve(Carve(d_ws_drvs[0]));
         LwdArgs<R> A{};
         A.ncol = ncol; A.lm = lm; A.nb = in[GEOSRAD_LWD_TAUA] ? nb : 0; A.iceflg = iceflg; A.liqflg = liqflg;
         auto I = [&](int k) { return (const R *)in[k]; };
@@ -1226,13 +1256,13 @@ template <typename R> struct Ctx : geosrad_ctx {
         A.airmw_over_h2omw = (R)consts[GEOSRAD_C_AIRMW] / (R)consts[GEOSRAD_C_H2OMW];
         A.airmw_over_o3mw = (R)consts[GEOSRAD_C_AIRMW] / (R)consts[GEOSRAD_C_O3MW];
         A.rgas = (R)consts[GEOSRAD_C_RGAS]; A.grav = (R)consts[GEOSRAD_C_GRAV];
-        A.play = P(o_lay[0]); A.tlay = P(o_lay[1]); A.h2o = P(o_lay[2]); A.o3_r = P(o_lay[3]); A.co2_r = P(o_lay[4]); A.ch4_r = P(o_lay[5]);
-        A.n2o_r = P(o_lay[6]); A.o2_r = P(o_lay[7]); A.cfc11_r = P(o_lay[8]); A.cfc12_r = P(o_lay[9]); A.cfc22_r = P(o_lay[10]);
-        A.ccl4_r = P(o_lay[11]); A.cldf = P(o_lay[12]); A.ciwp = P(o_lay[13]); A.clwp = P(o_lay[14]); A.rei = P(o_lay[15]);
-        A.rel = P(o_lay[16]); A.zm = P(o_lay[17]); A.plev = P(o_lev[0]); A.tlev = P(o_lev[1]); A.tsfc = P(o_tsfc); A.alat = P(o_alat);
-        A.emis_r = P(o_emis); A.tauaer = P(o_aer);
+        A.play = lay[0]; A.tlay = lay[1]; A.h2o = lay[2]; A.o3_r = lay[3]; A.co2_r = lay[4]; A.ch4_r = lay[5];
+        A.n2o_r = lay[6]; A.o2_r = lay[7]; A.cfc11_r = lay[8]; A.cfc12_r = lay[9]; A.cfc22_r = lay[10];
+        A.ccl4_r = lay[11]; A.cldf = lay[12]; A.ciwp = lay[13]; A.clwp = lay[14]; A.rei = lay[15];
+        A.rel = lay[16]; A.zm = lay[17]; A.plev = lev[0]; A.tlev = lev[1]; A.tsfc = tsfc; A.alat = alat;
+        A.emis_r = emis; A.tauaer = aerp;
         const dim3 blk(256);
-        const unsigned gx = (unsigned)((ncol + 255) / 256);
+        const unsigned gx = grid256(ncol);
         hipLaunchKernelGGL((k_lwd_prep<R>), dim3(gx, lm), blk, 0, st, A);
         hipLaunchKernelGGL((k_lwd_zm<R>), dim3(gx), blk, 0, st, A);
         // reverse the super-layer interface indices (IRR:3237-3239) and call the solver with Ts_derivs = .true.
@@ -1243,20 +1273,18 @@ template <typename R> struct Ctx : geosrad_ctx {
         lin[I_CFC11] = A.cfc11_r; lin[I_CFC12] = A.cfc12_r; lin[I_CFC22] = A.cfc22_r; lin[I_CCL4] = A.ccl4_r; lin[I_CLDF] = A.cldf;
         lin[I_CIWP] = A.ciwp; lin[I_CLWP] = A.clwp; lin[I_REI] = A.rei; lin[I_REL] = A.rel; lin[I_TAUAER] = A.tauaer; lin[I_ZM] = A.zm;
         lin[I_ALAT] = A.alat;
-        void *lout[O_NOUT] = {P(o_flux[0]), P(o_flux[1]), P(o_flux[2]), P(o_flux[3]), P(o_flux[4]), P(o_flux[5]),
-                              out[GEOSRAD_LWD_OLRB] ? out[GEOSRAD_LWD_OLRB] : (void *)P(o_olrb),
-                              out[GEOSRAD_LWD_DOLRB] ? out[GEOSRAD_LWD_DOLRB] : (void *)P(o_dolrb)};
-        int32_t *cc = (int32_t *)(d_ws_drv + o_cc);
+        void *lout[O_NOUT] = {flux[0], flux[1], flux[2], flux[3], flux[4], flux[5],
+                              out[GEOSRAD_LWD_OLRB] ? out[GEOSRAD_LWD_OLRB] : (void *)olrb,
+                              out[GEOSRAD_LWD_DOLRB] ? out[GEOSRAD_LWD_DOLRB] : (void *)dolrb};
         static const int32_t no_bands[16] = {0};
         LwRats RT{};
-        RT.n = nrats; RT.uflx = P(o_rat[0]); RT.dflx = P(o_rat[1]); RT.duflx_dTs = P(o_rat[2]);
+        RT.n = nrats; RT.uflx = rat[0]; RT.dflx = rat[1]; RT.duflx_dTs = rat[2];
         for (int r = 0; r < nrats; r++) RT.gas[r] = rat_gas[r];
-        rc = lw_dev(st, ncol, lm, 1, lin, iceflg, liqflg, doy, cloudLM, cloudMH, cc, lout, band_output ? band_output : no_bands, nullptr,
-                    nullptr, nrats > 0 ? &RT : nullptr);
-        if (rc) return rc;
+        if (const int rc = lw_dev(st, ncol, lm, 1, lin, iceflg, liqflg, doy, cloudLM, cloudMH, cc, lout, band_output ? band_output : no_bands,
+                                  nullptr, nullptr, nrats > 0 ? &RT : nullptr)) return rc;
         if (nrats > 0) {
             LwdRatPost<R> RP{};
-            RP.ncol = ncol; RP.lm = lm; RP.nrats = nrats; RP.uflx = P(o_rat[0]); RP.dflx = P(o_rat[1]); RP.duflx = P(o_rat[2]); RP.emis = A.emis;
+            RP.ncol = ncol; RP.lm = lm; RP.nrats = nrats; RP.uflx = rat[0]; RP.dflx = rat[1]; RP.duflx = rat[2]; RP.emis = A.emis;
             RP.flxu_rat = (R *)rat_out[GEOSRAD_LWD_FLXU_RAT]; RP.flxd_rat = (R *)rat_out[GEOSRAD_LWD_FLXD_RAT];
             RP.flx_rat = (R *)rat_out[GEOSRAD_LWD_FLX_RAT]; RP.dfdts_rat = (R *)rat_out[GEOSRAD_LWD_DFDTS_RAT];
             RP.sfcem_rat = (R *)rat_out[GEOSRAD_LWD_SFCEM_RAT];
@@ -1264,8 +1292,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         }
         LwdPost<R> Q{};
         Q.ncol = ncol; Q.lm = lm; Q.ngpt = NG_LW;
-        Q.uflx = P(o_flux[0]); Q.dflx = P(o_flux[1]); Q.uflxc = P(o_flux[2]); Q.dflxc = P(o_flux[3]); Q.duflx = P(o_flux[4]);
-        Q.duflxc = P(o_flux[5]); Q.clearCounts = cc; Q.emis = A.emis; Q.ts = A.ts;
+        Q.uflx = flux[0]; Q.dflx = flux[1]; Q.uflxc = flux[2]; Q.dflxc = flux[3]; Q.duflx = flux[4];
+        Q.duflxc = flux[5]; Q.clearCounts = cc; Q.emis = A.emis; Q.ts = A.ts;
         auto O = [&](int k) { return (R *)out[k]; };
         Q.flxu_int = O(GEOSRAD_LWD_FLXU_INT); Q.flxd_int = O(GEOSRAD_LWD_FLXD_INT); Q.flcu_int = O(GEOSRAD_LWD_FLCU_INT);
         Q.flcd_int = O(GEOSRAD_LWD_FLCD_INT); Q.dfdts = O(GEOSRAD_LWD_DFDTS); Q.dfdtsc = O(GEOSRAD_LWD_DFDTSC);
@@ -1292,25 +1320,28 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (aer && (!in[GEOSRAD_SWD_SSAA] || !in[GEOSRAD_SWD_ASYA])) return fail(GEOSRAD_EINVAL, "TAUA, SSAA and ASYA go together");
         if (aer && nb != 14) return fail(GEOSRAD_EINVAL, "RRTMG_SW aerosol arrays have 14 bands");
         const size_t n = (size_t)ncol, cl = n * lm, cv = n * (lm + 1);
-        size_t off = 0;
-        auto take = [&](size_t nreal) { size_t o = off; off += al(nreal * sizeof(R)); return o; };
         const bool want_na = out[GEOSRAD_SWD_FSWNA] || out[GEOSRAD_SWD_FSCNA] || out[GEOSRAD_SWD_FSWUNA] || out[GEOSRAD_SWD_FSCUNA] ||
                              out[GEOSRAD_SWD_FSWBANDNA];
-        size_t o_lay[13], o_lev[2], o_aer[3], o_flux[4], o_sc[6], o_cot[8], o_nflux[4], o_nsc[14];
-        for (auto &o : o_lay) o = take(cl);
-        for (auto &o : o_lev) o = take(cv);
-        for (auto &o : o_aer) o = take(cl * 14);
-        for (auto &o : o_flux) o = take(cv);
-        for (auto &o : o_sc) o = take(n);
-        for (auto &o : o_cot) o = take(n);
-        const size_t o_band = take(n * 14), o_cc = take(n * 4);
-        for (auto &o : o_nflux) o = want_na ? take(cv) : 0;
-        for (auto &o : o_nsc) o = want_na ? take(n) : 0;
-        const size_t o_nband = want_na ? take(n * 14) : 0;
-        int rc = drv_reserve(1, off);
-        if (rc) return rc;
-        char *const d_ws_drv = d_ws_drvs[1];
-        auto P = [&](size_t o) { return (R *)(d_ws_drv + o); };
+        R *lay[13], *lev[2], *aerp[3], *flux[4], *scal[6], *cot[8], *band, *nflux[4] = {}, *nsc[14] = {}, *nband = nullptr;
+        int32_t *cc;
+        auto carve = [&](Carve c) {
+            for (auto &q : lay) q = c.take<R>(cl);
+            for (auto &q : lev) q = c.take<R>(cv);
+            for (auto &q : aerp) q = c.take<R>(cl * 14);
+            for (auto &q : flux) q = c.take<R>(cv);
+            for (auto &q : scal) q = c.take<R>(n);
+            for (auto &q : cot) q = c.take<R>(n);
+            band = c.take<R>(n * 14);
+            cc = (int32_t *)c.take<R>(n * 4);      // clearCounts (ncol, 4) int32 in 4 n reals, as in lw_driver_dev
+            if (want_na) {      // the no-aerosol pass's own fluxes, surface scalars + optical thicknesses, band fluxes
+                for (auto &q : nflux) q = c.take<R>(cv);
+                for (auto &q : nsc) q = c.take<R>(n);
+                nband = c.take<R>(n * 14);
+            }
+            return c.off;
+        };
+        if (const int rc = drv_reserve(1, carve(Carve()))) return rc;
+        carve(Carve(d_ws_drvs[1]));
         auto I = [&](int k) { return (const R *)in[k]; };
         SwdArgs<R> A{};
         A.ncol = ncol; A.lm = lm; A.nb = 14; A.iceflg = iceflg; A.liqflg = liqflg;
@@ -1322,11 +1353,11 @@ template <typename R> struct Ctx : geosrad_ctx {
         A.airmw_over_h2omw = (R)consts[GEOSRAD_SWD_C_AIRMW] / (R)consts[GEOSRAD_SWD_C_H2OMW];
         A.airmw_over_o3mw = (R)consts[GEOSRAD_SWD_C_AIRMW] / (R)consts[GEOSRAD_SWD_C_O3MW];
         A.rgas = (R)consts[GEOSRAD_SWD_C_RGAS]; A.grav = (R)consts[GEOSRAD_SWD_C_GRAV];
-        A.play = P(o_lay[0]); A.tlay = P(o_lay[1]); A.h2o = P(o_lay[2]); A.o3_r = P(o_lay[3]); A.co2_r = P(o_lay[4]); A.ch4_r = P(o_lay[5]);
-        A.o2_r = P(o_lay[6]); A.cldf = P(o_lay[7]); A.ciwp = P(o_lay[8]); A.clwp = P(o_lay[9]); A.rei = P(o_lay[10]); A.rel = P(o_lay[11]);
-        A.zl = P(o_lay[12]); A.plev = P(o_lev[0]); A.tlev = P(o_lev[1]); A.tauaer = P(o_aer[0]); A.ssaaer = P(o_aer[1]); A.asmaer = P(o_aer[2]);
+        A.play = lay[0]; A.tlay = lay[1]; A.h2o = lay[2]; A.o3_r = lay[3]; A.co2_r = lay[4]; A.ch4_r = lay[5];
+        A.o2_r = lay[6]; A.cldf = lay[7]; A.ciwp = lay[8]; A.clwp = lay[9]; A.rei = lay[10]; A.rel = lay[11];
+        A.zl = lay[12]; A.plev = lev[0]; A.tlev = lev[1]; A.tauaer = aerp[0]; A.ssaaer = aerp[1]; A.asmaer = aerp[2];
         const dim3 blk(256);
-        const unsigned gx = (unsigned)((ncol + 255) / 256);
+        const unsigned gx = grid256(ncol);
         hipLaunchKernelGGL((k_swd_prep<R>), dim3(gx, lm), blk, 0, st, A);
         hipLaunchKernelGGL((k_swd_zm<R>), dim3(gx), blk, 0, st, A);
         const void *sin[S_NIN];
@@ -1336,27 +1367,25 @@ template <typename R> struct Ctx : geosrad_ctx {
         sin[S_ASMAER] = A.asmaer; sin[S_COSZEN] = in[GEOSRAD_SWD_ZT]; sin[S_ASDIR] = in[GEOSRAD_SWD_ALBVR]; sin[S_ASDIF] = in[GEOSRAD_SWD_ALBVF];
         sin[S_ALDIR] = in[GEOSRAD_SWD_ALBNR]; sin[S_ALDIF] = in[GEOSRAD_SWD_ALBNF];
         void *sout[SO_NOUT] = {};
-        for (int k = 0; k < 4; k++) sout[SO_UFLX + k] = P(o_flux[k]);
+        for (int k = 0; k < 4; k++) sout[SO_UFLX + k] = flux[k];
         const int sc_ix[6] = {GEOSRAD_SWD_NIRR, GEOSRAD_SWD_NIRF, GEOSRAD_SWD_PARR, GEOSRAD_SWD_PARF, GEOSRAD_SWD_UVRR, GEOSRAD_SWD_UVRF};
-        for (int k = 0; k < 6; k++) sout[SO_NIRR + k] = out[sc_ix[k]] ? out[sc_ix[k]] : (void *)P(o_sc[k]);
-        sout[SO_FSWBAND] = out[GEOSRAD_SWD_FSWBAND] ? out[GEOSRAD_SWD_FSWBAND] : (void *)P(o_band);
-        for (int k = 0; k < 8; k++) sout[SO_COT0 + k] = P(o_cot[k]);      // cotd t/h/m/l then cotn t/h/m/l
-        int32_t *cc = (int32_t *)(d_ws_drv + o_cc);
+        for (int k = 0; k < 6; k++) sout[SO_NIRR + k] = out[sc_ix[k]] ? out[sc_ix[k]] : (void *)scal[k];
+        sout[SO_FSWBAND] = out[GEOSRAD_SWD_FSWBAND] ? out[GEOSRAD_SWD_FSWBAND] : (void *)band;
+        for (int k = 0; k < 8; k++) sout[SO_COT0 + k] = cot[k];      // cotd t/h/m/l then cotn t/h/m/l
         // IAER = 10 always (SOL:6235; without aerosols the arrays are zero); super-layer indices flipped in the call (SOL:6341)
         void *nout[SO_NOUT] = {};
         if (want_na) {
-            for (int k = 0; k < 4; k++) nout[SO_UFLX + k] = P(o_nflux[k]);
-            for (int k = 0; k < 6; k++) nout[SO_NIRR + k] = P(o_nsc[k]);
-            for (int k = 0; k < 8; k++) nout[SO_COT0 + k] = P(o_nsc[6 + k]);
-            nout[SO_FSWBAND] = out[GEOSRAD_SWD_FSWBANDNA] ? out[GEOSRAD_SWD_FSWBANDNA] : (void *)P(o_nband);
+            for (int k = 0; k < 4; k++) nout[SO_UFLX + k] = nflux[k];
+            for (int k = 0; k < 6; k++) nout[SO_NIRR + k] = nsc[k];
+            for (int k = 0; k < 8; k++) nout[SO_COT0 + k] = nsc[6 + k];
+            nout[SO_FSWBAND] = out[GEOSRAD_SWD_FSWBANDNA] ? out[GEOSRAD_SWD_FSWBANDNA] : (void *)nband;
         }
-        rc = sw_run(st, ncol, lm, sc, dist, isolvar, sin, iceflg, liqflg, dyofyr, 10, lm - lcldlm + 1, lm - lcldmh + 1,
-                    normflx, cc, sout, 0, bndsolvar, indsolvar, nullptr, nullptr, want_na ? nout : nullptr);
-        if (rc) return rc;
+        if (const int rc = sw_run(st, ncol, lm, sc, dist, isolvar, sin, iceflg, liqflg, dyofyr, 10, lm - lcldlm + 1, lm - lcldmh + 1,
+                                  normflx, cc, sout, 0, bndsolvar, indsolvar, nullptr, nullptr, want_na ? nout : nullptr)) return rc;
         SwdPost<R> Q{};
         Q.ncol = ncol; Q.lm = lm; Q.ngpt = NG_SW; Q.aerosols = include_aerosols; Q.undef = (R)consts[GEOSRAD_SWD_C_UNDEF];
-        Q.swuflx = P(o_flux[0]); Q.swdflx = P(o_flux[1]); Q.swuflxc = P(o_flux[2]); Q.swdflxc = P(o_flux[3]); Q.clearCounts = cc;
-        for (int k = 0; k < 4; k++) { Q.cotd[k] = P(o_cot[k]); Q.cotn[k] = P(o_cot[4 + k]); Q.cot[k] = (R *)out[GEOSRAD_SWD_COTTP + k]; }
+        Q.swuflx = flux[0]; Q.swdflx = flux[1]; Q.swuflxc = flux[2]; Q.swdflxc = flux[3]; Q.clearCounts = cc;
+        for (int k = 0; k < 4; k++) { Q.cotd[k] = cot[k]; Q.cotn[k] = cot[4 + k]; Q.cot[k] = (R *)out[GEOSRAD_SWD_COTTP + k]; }
         Q.fsw = (R *)out[GEOSRAD_SWD_FSW]; Q.fsc = (R *)out[GEOSRAD_SWD_FSC]; Q.fswu = (R *)out[GEOSRAD_SWD_FSWU]; Q.fscu = (R *)out[GEOSRAD_SWD_FSCU];
         Q.cldts = (R *)out[GEOSRAD_SWD_CLDTS]; Q.cldhs = (R *)out[GEOSRAD_SWD_CLDHS]; Q.cldms = (R *)out[GEOSRAD_SWD_CLDMS];
         Q.cldls = (R *)out[GEOSRAD_SWD_CLDLS];
@@ -1364,7 +1393,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (want_na) {      // un-flip of the no-aerosol fluxes (the FS*NAN internals, SOL:4152-4159)
             SwdPost<R> N{};
             N.ncol = ncol; N.lm = lm; N.ngpt = NG_SW; N.aerosols = 0; N.undef = Q.undef;
-            N.swuflx = P(o_nflux[0]); N.swdflx = P(o_nflux[1]); N.swuflxc = P(o_nflux[2]); N.swdflxc = P(o_nflux[3]); N.clearCounts = cc;
+            N.swuflx = nflux[0]; N.swdflx = nflux[1]; N.swuflxc = nflux[2]; N.swdflxc = nflux[3]; N.clearCounts = cc;
             N.fsw = (R *)out[GEOSRAD_SWD_FSWNA]; N.fsc = (R *)out[GEOSRAD_SWD_FSCNA]; N.fswu = (R *)out[GEOSRAD_SWD_FSWUNA];
             N.fscu = (R *)out[GEOSRAD_SWD_FSCUNA];
             hipLaunchKernelGGL((k_swd_post<R>), dim3(gx, lm + 1), blk, 0, st, N);
@@ -1389,7 +1418,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (!(need(P.flx_int, P.flxd, P.flxu) && need(P.flxa_int, P.flxad, P.flxau) && need(P.flc_int, P.flcd, P.flcu) &&
               need(P.fla_int, P.flad, P.flau) && need(P.dfdtsna, P.dfdts) && need(P.ts_int, P.ts)))
             return fail(GEOSRAD_EINVAL, "an output was requested without the field it is computed from");
-        hipLaunchKernelGGL((k_lwd_chou_post<R>), dim3((unsigned)((ncol + 255) / 256), lm + 1), dim3(256), 0, st, P);
+        hipLaunchKernelGGL((k_lwd_chou_post<R>), dim3(grid256(ncol), lm + 1), dim3(256), 0, st, P);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1411,28 +1440,29 @@ template <typename R> struct Ctx : geosrad_ctx {
         for (int k = 0; k < GEOSRAD_LWK_TAUA; k++) if (!in[k]) return fail(GEOSRAD_EINVAL, "null input field");
         for (int k = 0; k <= GEOSRAD_LWK_SFCEM_INT; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null INTERNAL flux array");
         if (out[GEOSRAD_LWK_LWS0] && !out[GEOSRAD_LWK_FLX_INT]) return fail(GEOSRAD_EINVAL, "LWS0 was requested without FLX_INT, which it is computed from");
-        const size_t cell = (size_t)ncol * sizeof(R);
-        const size_t o_td = al(34 * cell), need = o_td + (out[GEOSRAD_LWK_TAUDIAG] ? 0 : al((size_t)10 * lm * cell));
-        if (d_ws_lwk.reserve(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "LW_Driver (Chou-Suarez) workspace");
         auto I = [&](int k) { return (const R *)in[k]; };
         auto O = [&](int k) { return (R *)out[k]; };
-        // 16-byte accesses (4 floats / 2 doubles per thread) when the column count and every address the two kernels touch allow
-        constexpr int VW = 16 / (int)sizeof(R);
-        bool wide = ncol % VW == 0;
-        for (int k : {GEOSRAD_LWK_PLE, GEOSRAD_LWK_T, GEOSRAD_LWK_TS, GEOSRAD_LWK_EMIS}) wide = wide && ((uintptr_t)in[k] & 15) == 0;
-        for (int k = GEOSRAD_LWK_DFDTS; k < GEOSRAD_LWK_NOUT; k++) wide = wide && ((uintptr_t)out[k] & 15) == 0;
-        R *ws = (R *)d_ws_lwk.p;               // T2M, FS, TG, TV (ncol); EG, EV, RV (ncol,10); 256-byte aligned base, ncol % VW == 0 keeps 16
+        R *ws, *taudiag = O(GEOSRAD_LWK_TAUDIAG);      // ws: T2M, FS, TG, TV (ncol); EG, EV, RV (ncol,10); 256-byte aligned base, ncol % VW == 0 keeps 16
+        auto carve = [&](Carve c) {
+            ws = c.take<R>((size_t)34 * ncol);
+            if (!out[GEOSRAD_LWK_TAUDIAG]) taudiag = c.take<R>((size_t)10 * lm * ncol);
+            return c.off;
+        };
+        if (d_ws_lwk.reserve(carve(Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "LW_Driver (Chou-Suarez) workspace");
+        carve(Carve(d_ws_lwk));
+        // the addresses the two kernels touch
+        const bool wide = wide16(ncol, {{in + GEOSRAD_LWK_PLE, 1}, {in + GEOSRAD_LWK_T, 1}, {in + GEOSRAD_LWK_TS, 1}, {in + GEOSRAD_LWK_EMIS, 1},
+                                        {out + GEOSRAD_LWK_DFDTS, GEOSRAD_LWK_NOUT - GEOSRAD_LWK_DFDTS}});
         LwkSurf<R> S{};
         S.ncol = ncol; S.lm = lm; S.mkappa = -(R)consts[GEOSRAD_LWK_C_KAPPA];
         S.ple = I(GEOSRAD_LWK_PLE); S.t = I(GEOSRAD_LWK_T); S.ts = I(GEOSRAD_LWK_TS); S.emis = I(GEOSRAD_LWK_EMIS);
         S.t2m = O(GEOSRAD_LWK_T2M) ? O(GEOSRAD_LWK_T2M) : ws;
         S.fs = ws + (size_t)ncol; S.tg = ws + (size_t)2 * ncol; S.tv = ws + (size_t)3 * ncol;
         S.eg = ws + (size_t)4 * ncol; S.ev = ws + (size_t)14 * ncol; S.rv = ws + (size_t)24 * ncol;
-        const dim3 blk(256), gw((unsigned)((ncol / VW + 255) / 256)), g1((unsigned)((ncol + 255) / 256));
+        const dim3 blk(256), gw(grid256(ncol / VW)), g1(grid256(ncol));
         if (wide) hipLaunchKernelGGL((k_lwk_surface<R, VW>), dim3(gw.x, 11), blk, 0, st, S);
         else hipLaunchKernelGGL((k_lwk_surface<R, 1>), dim3(g1.x, 11), blk, 0, st, S);
         HIPCHK(hipGetLastError());
-        R *taudiag = O(GEOSRAD_LWK_TAUDIAG) ? O(GEOSRAD_LWK_TAUDIAG) : (R *)(d_ws_lwk + o_td);
         const void *ci[C_NIN] = {};
         ci[C_PLE] = in[GEOSRAD_LWK_PLE]; ci[C_TA] = in[GEOSRAD_LWK_T]; ci[C_WA] = in[GEOSRAD_LWK_Q]; ci[C_OA] = in[GEOSRAD_LWK_O3]; ci[C_TB] = S.t2m;
         ci[C_N2O] = in[GEOSRAD_LWK_N2O]; ci[C_CH4] = in[GEOSRAD_LWK_CH4]; ci[C_CFC11] = in[GEOSRAD_LWK_CFC11]; ci[C_CFC12] = in[GEOSRAD_LWK_CFC12];
@@ -1455,8 +1485,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         void *po[GEOSRAD_LWC_NOUT];
         static_assert(GEOSRAD_LWK_TS_INT - GEOSRAD_LWK_SFCEM_INT == GEOSRAD_LWC_TS_INT - GEOSRAD_LWC_SFCEM_INT, "GEOSRAD_LWK_SFCEM_INT .. TS_INT follow GEOSRAD_LWC_*");
         for (int k = 0; k < GEOSRAD_LWC_NOUT; k++) po[k] = out[GEOSRAD_LWK_SFCEM_INT + k];
-        const int rc2 = lw_chou_post_dev(st, ncol, lm, pi, po);
-        if (rc2) return rc2;
+        if (const int rc2 = lw_chou_post_dev(st, ncol, lm, pi, po)) return rc2;
         LwkDiag<R> D{};
         D.ncol = ncol; D.lm = lm; D.taucrit = (R)consts[GEOSRAD_LWK_C_TAUCRIT] / (R)2.13; D.undef = G.undef;
         D.taudiag = taudiag; D.t = S.t; D.ple = S.ple; D.ts = S.ts; D.dfdts = O(GEOSRAD_LWK_DFDTS); D.sfcem_int = O(GEOSRAD_LWK_SFCEM_INT);
@@ -1484,20 +1513,23 @@ template <typename R> struct Ctx : geosrad_ctx {
             return fail(GEOSRAD_EINVAL, "TAUA / SSAA / ASYA: all three or none");
         for (int k = 0; k < GEOSRAD_SWC_NIN; k++)
             if (!in[k] && !(k >= GEOSRAD_SWC_TAUA && k <= GEOSRAD_SWC_ASYA)) return fail(GEOSRAD_EINVAL, "null input field");
-        const size_t cell = (size_t)ncol * sizeof(R);
-        const size_t o_plh = 0, o_o3 = o_plh + al((size_t)(lm + 1) * cell), o_qq = o_o3 + al((size_t)lm * cell), o_rr = o_qq + al((size_t)4 * lm * cell),
-                     o_zero = o_rr + al((size_t)4 * lm * cell), need = o_zero + (aer ? 0 : al((size_t)8 * lm * cell));
-        if (d_ws_swc.reserve(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "SORADCORE (Chou-Suarez) workspace");
+        const size_t cl = (size_t)lm * ncol;
         SwcPrep<R> P{};
+        R *zero = nullptr;          // TAUA = SSAA = ASYA = 0 (SOL:4543-4546): one block serves the three
+        auto carve = [&](Carve c) {
+            P.plhpa = c.take<R>(cl + ncol); P.o3 = c.take<R>(cl); P.qq3 = c.take<R>(4 * cl); P.rr3 = c.take<R>(4 * cl);
+            if (!aer) zero = c.take<R>(8 * cl);
+            return c.off;
+        };
+        if (d_ws_swc.reserve(carve(Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "SORADCORE (Chou-Suarez) workspace");
+        carve(Carve(d_ws_swc));
         P.ncol = ncol; P.lm = lm;
         P.ple = (const R *)in[GEOSRAD_SWC_PLE]; P.ox = (const R *)in[GEOSRAD_SWC_OX];
         for (int s = 0; s < 4; s++) { P.q[s] = (const R *)in[GEOSRAD_SWC_QI + s]; P.r[s] = (const R *)in[GEOSRAD_SWC_RI + s]; }
         P.o3fac = (R)consts[GEOSRAD_SWC_C_O3MW] / (R)consts[GEOSRAD_SWC_C_AIRMW]; P.undef = (R)consts[GEOSRAD_SWC_C_UNDEF];
-        P.plhpa = (R *)(d_ws_swc + o_plh); P.o3 = (R *)(d_ws_swc + o_o3); P.qq3 = (R *)(d_ws_swc + o_qq); P.rr3 = (R *)(d_ws_swc + o_rr);
-        hipLaunchKernelGGL((k_swc_prep<R>), dim3((unsigned)((ncol + 255) / 256), lm + 1), dim3(256), 0, st, P);
+        hipLaunchKernelGGL((k_swc_prep<R>), dim3(grid256(ncol), lm + 1), dim3(256), 0, st, P);
         HIPCHK(hipGetLastError());
-        const void *zero = d_ws_swc + o_zero;          // TAUA = SSAA = ASYA = 0 (SOL:4543-4546): one block serves the three
-        if (!aer) HIPCHK(hipMemsetAsync(d_ws_swc + o_zero, 0, (size_t)8 * lm * cell, st));
+        if (!aer) HIPCHK(hipMemsetAsync(zero, 0, 8 * cl * sizeof(R), st));
         const void *si[SI_NIN];
         si[SI_COSZ] = in[GEOSRAD_SWC_ZT]; si[SI_PL] = P.plhpa; si[SI_TA] = in[GEOSRAD_SWC_T]; si[SI_WA] = in[GEOSRAD_SWC_Q]; si[SI_OA] = P.o3;
         si[SI_CWC] = P.qq3; si[SI_FCLD] = in[GEOSRAD_SWC_CL]; si[SI_REFF] = P.rr3;
@@ -1535,13 +1567,9 @@ template <typename R> struct Ctx : geosrad_ctx {
         static_assert(offsetof(LwUpd<R>, cldtt) - offsetof(LwUpd<R>, flx) == (GEOSRAD_LWU_NOUT - 1) * sizeof(void *), "LwUpd export layout");
         R **o3 = &U.flx;       // the export pointers are laid out in the order of the GEOSRAD_LWU_* output enum
         for (int k = 0; k < GEOSRAD_LWU_NOUT; k++) o3[k] = (R *)out[k];
-        // 16-byte accesses (4 floats / 2 doubles per thread) when the column count and every field address allow
-        constexpr int VW = 16 / (int)sizeof(R);
-        bool wide = ncol % VW == 0;
-        for (int k = 0; k < GEOSRAD_LWU_NIN; k++) wide = wide && ((uintptr_t)in[k] & 15) == 0;
-        for (int k = 0; k < GEOSRAD_LWU_NOUT; k++) wide = wide && ((uintptr_t)out[k] & 15) == 0;
-        if (wide) hipLaunchKernelGGL((k_lw_update_flx<R, VW>), dim3((unsigned)((ncol / VW + 255) / 256), lm + 1), dim3(256), 0, st, U);
-        else hipLaunchKernelGGL((k_lw_update_flx<R, 1>), dim3((unsigned)((ncol + 255) / 256), lm + 1), dim3(256), 0, st, U);
+        const bool wide = wide16(ncol, {{in, GEOSRAD_LWU_NIN}, {out, GEOSRAD_LWU_NOUT}});
+        if (wide) hipLaunchKernelGGL((k_lw_update_flx<R, VW>), dim3(grid256(ncol / VW), lm + 1), dim3(256), 0, st, U);
+        else hipLaunchKernelGGL((k_lw_update_flx<R, 1>), dim3(grid256(ncol), lm + 1), dim3(256), 0, st, U);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1563,7 +1591,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         auto O = [&](int k) { return (R *)out[k]; };
         U.dolr = O(GEOSRAD_LWR_DOLR); U.dlws = O(GEOSRAD_LWR_DLWS); U.dflns = O(GEOSRAD_LWR_DFLNS); U.dsfcem = O(GEOSRAD_LWR_DSFCEM);
         U.nettrap = O(GEOSRAD_LWR_NETTRAP); U.coltrap = O(GEOSRAD_LWR_COLTRAP); U.flx = O(GEOSRAD_LWR_FLX); U.dfdts_out = O(GEOSRAD_LWR_DFDTS_OUT);
-        hipLaunchKernelGGL((k_lw_update_rats<R>), dim3((unsigned)((ncol + 255) / 256), lm + 1, nrats), dim3(256), 0, st, U);
+        hipLaunchKernelGGL((k_lw_update_rats<R>), dim3(grid256(ncol), lm + 1, nrats), dim3(256), 0, st, U);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1586,7 +1614,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         }
         U.tsinst = (const R *)tsinst; U.ts_int = (const R *)ts_int; U.olrb_int = (const R *)olrb_int; U.dolrb_int = (const R *)dolrb_int;
         U.olrb_exp = (R *)olrb_exp; U.tbrb_exp = (R *)tbrb_exp; U.nonzero = d_bandflags;
-        const dim3 grid((unsigned)((ncol + 255) / 256), 16);
+        const dim3 grid(grid256(ncol), 16);
         hipLaunchKernelGGL((k_lw_update_bands<R, 0>), grid, dim3(256), 0, st, U);
         if (tbrb_exp) hipLaunchKernelGGL((k_lw_update_bands<R, 1>), grid, dim3(256), 0, st, U);
         HIPCHK(hipGetLastError());
@@ -1616,12 +1644,9 @@ template <typename R> struct Ctx : geosrad_ctx {
                         need(U.osrclr, U.fscn) && need(U.rsrna, U.fswnan) && need(U.rsrsna, U.fswnan) && need(U.osrna, U.fswnan) &&
                         need(U.rscna, U.fscnan) && need(U.rscsna, U.fscnan) && need(U.osrcna, U.fscnan);
         if (!ok) return fail(GEOSRAD_EINVAL, "an export was requested without the internal field it is computed from");
-        constexpr int VW = 16 / (int)sizeof(R);
-        bool wide = ncol % VW == 0;
-        for (int k = 0; k < GEOSRAD_SWU_NIN; k++) wide = wide && ((uintptr_t)in[k] & 15) == 0;
-        for (int k = 0; k < GEOSRAD_SWU_NOUT; k++) wide = wide && ((uintptr_t)out[k] & 15) == 0;
-        if (wide) hipLaunchKernelGGL((k_sw_update_export<R, VW>), dim3((unsigned)((ncol / VW + 255) / 256), lm + 1 + nbands), dim3(256), 0, st, U);
-        else hipLaunchKernelGGL((k_sw_update_export<R, 1>), dim3((unsigned)((ncol + 255) / 256), lm + 1 + nbands), dim3(256), 0, st, U);
+        const bool wide = wide16(ncol, {{in, GEOSRAD_SWU_NIN}, {out, GEOSRAD_SWU_NOUT}});
+        if (wide) hipLaunchKernelGGL((k_sw_update_export<R, VW>), dim3(grid256(ncol / VW), lm + 1 + nbands), dim3(256), 0, st, U);
+        else hipLaunchKernelGGL((k_sw_update_export<R, 1>), dim3(grid256(ncol), lm + 1 + nbands), dim3(256), 0, st, U);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1652,7 +1677,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         for (int k = 0; k < 3; k++) U.drn[k] = O(GEOSRAD_SWS_DRNUVR + k);
         U.slrsf = O(GEOSRAD_SWS_SLRSF); U.slrsfc = O(GEOSRAD_SWS_SLRSFC); U.slrsfna = O(GEOSRAD_SWS_SLRSFNA); U.slrsfcna = O(GEOSRAD_SWS_SLRSFCNA);
         U.slrsuf = O(GEOSRAD_SWS_SLRSUF); U.slrsufc = O(GEOSRAD_SWS_SLRSUFC); U.slrsufna = O(GEOSRAD_SWS_SLRSUFNA); U.slrsufcna = O(GEOSRAD_SWS_SLRSUFCNA);
-        hipLaunchKernelGGL((k_sw_update_surface<R>), dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, st, U);
+        hipLaunchKernelGGL((k_sw_update_surface<R>), dim3(grid256(ncol)), dim3(256), 0, st, U);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1681,7 +1706,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         U.grav = (R)consts[GEOSRAD_SWK_C_GRAV]; U.undef = (R)consts[GEOSRAD_SWK_C_UNDEF]; U.taucrit = (R)taucrit;
         for (int k = 0; k < GEOSRAD_SWK_NIN; k++) U.in[k] = (const R *)in[k];
         for (int k = 0; k < GEOSRAD_SWK_NOUT; k++) U.out[k] = (R *)out[k];
-        hipLaunchKernelGGL((k_sw_update_clouds<R>), dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, st, U, (const SoradDev<R> *)d_O);
+        hipLaunchKernelGGL((k_sw_update_clouds<R>), dim3(grid256(ncol)), dim3(256), 0, st, U, (const SoradDev<R> *)d_O);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1707,7 +1732,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         HIPCHK(hipSetDevice(device));
         if (pdim <= 0 || udim <= 0 || nlev <= 0 || !idx || !nlit_dev || !unpacked || !packed) return fail(GEOSRAD_EINVAL, "lit_pack: bad arguments");
         const int nmax = pdim < udim ? pdim : udim;
-        hipLaunchKernelGGL(k_lit_pack<R>, dim3((unsigned)((nmax + 255) / 256), nlev), dim3(256), 0, st, pdim, udim, idx, nlit_dev,
+        hipLaunchKernelGGL(k_lit_pack<R>, dim3(grid256(nmax), nlev), dim3(256), 0, st, pdim, udim, idx, nlit_dev,
                            (const R *)unpacked, (R *)packed);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
@@ -1717,7 +1742,7 @@ template <typename R> struct Ctx : geosrad_ctx {
     {
         HIPCHK(hipSetDevice(device));
         if (pdim <= 0 || udim <= 0 || nlev <= 0 || !pos || !unpacked || !packed) return fail(GEOSRAD_EINVAL, "lit_unpack: bad arguments");
-        hipLaunchKernelGGL(k_lit_unpack<R>, dim3((unsigned)((udim + 255) / 256), nlev), dim3(256), 0, st, pdim, udim, pos, (const R *)packed,
+        hipLaunchKernelGGL(k_lit_unpack<R>, dim3(grid256(udim), nlev), dim3(256), 0, st, pdim, udim, pos, (const R *)packed,
                            (R *)unpacked, use_default, (R)dflt);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
@@ -1742,12 +1767,9 @@ template <typename R> struct Ctx : geosrad_ctx {
                         need(P.radswcna, P.fscna) && need(P.blw, P.dsfdts) && need(P.alw, P.sfcem, P.dsfdts, P.trd) &&
                         need(P.radsrf, P.fsw, P.flw);
         if (!ok) return fail(GEOSRAD_EINVAL, "an export was requested without the field it is computed from");
-        constexpr int VW = 16 / (int)sizeof(R);
-        bool wide = ncol % VW == 0;
-        for (int k = 0; k < GEOSRAD_RT_NIN; k++) wide = wide && ((uintptr_t)in[k] & 15) == 0;
-        for (int k = 0; k < GEOSRAD_RT_NOUT; k++) wide = wide && ((uintptr_t)out[k] & 15) == 0;
-        if (wide) hipLaunchKernelGGL((k_rad_tendencies<R, VW>), dim3((unsigned)((ncol / VW + 255) / 256), lm), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((k_rad_tendencies<R, 1>), dim3((unsigned)((ncol + 255) / 256), lm), dim3(256), 0, st, P);
+        const bool wide = wide16(ncol, {{in, GEOSRAD_RT_NIN}, {out, GEOSRAD_RT_NOUT}});
+        if (wide) hipLaunchKernelGGL((k_rad_tendencies<R, VW>), dim3(grid256(ncol / VW), lm), dim3(256), 0, st, P);
+        else hipLaunchKernelGGL((k_rad_tendencies<R, 1>), dim3(grid256(ncol), lm), dim3(256), 0, st, P);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1818,8 +1840,7 @@ template <typename R> struct Ctx : geosrad_ctx {
     {
         HIPCHK(hipSetDevice(device));
         if (ncol <= 0 || nlay <= 0) return fail(GEOSRAD_EINVAL, "bad ncol/nlay");
-        for (int k = 0; k < I_NIN; k++) if (!in[k] && k != I_TAUAER) return fail(GEOSRAD_EINVAL, "null input array");
-        for (int k = 0; k < 4; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
+        if (const int rc = lw_check_arrays(in, out)) return rc;
         bool any_bo = false;
         if (band_output) for (int b = 0; b < 16; b++) any_bo |= band_output[b] != 0;
         const size_t L = (size_t)nlay;
@@ -1918,40 +1939,36 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 
-    struct WsSw { R *sc; uint32_t *scidx; uint8_t *colcloudy, *laycloudy; int32_t *perm, *nclear; R *alpha, *rcorr, *taucmc, *ssacmc, *asmcmc, *cotsum, *cell, *part, *bsfc, *cot, *rvsum; };
-    size_t ws_layout_sw(int nc, int nlay, WsSw *w, char *base, int planes, bool radval) const
+    // the SW workspace of nc columns, straight into the kernels' arguments (+ rvsum, which is none of them): on Carve() the bytes it takes,
+    // on Carve(d_ws_sw) its planes
+    size_t ws_layout_sw(int nc, int nlay, SwArgs<R> &w, R *&rvsum, Carve c, int planes, bool radval) const
     {
-        size_t off = 0;
-        auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return base ? base + o : (char *)nullptr; };
         const size_t cl = (size_t)nlay * nc;
-        char *p;
-        p = take(SW_NFIELD * cl * sizeof(R)); if (w) w->sc = (R *)p;
-        p = take(cl * 4); if (w) w->scidx = (uint32_t *)p;
-        p = take(nc); if (w) w->colcloudy = (uint8_t *)p;
-        p = take((size_t)nc * 4); if (w) w->perm = (int32_t *)p;
-        p = take(4); if (w) w->nclear = (int32_t *)p;
-        p = take(cl); if (w) w->laycloudy = (uint8_t *)p;
-        p = take(cl * sizeof(R)); if (w) w->alpha = (R *)p;
-        p = take(cl * sizeof(R)); if (w) w->rcorr = (R *)p;
-        p = take(NG_SW * cl * sizeof(R)); if (w) w->taucmc = (R *)p;
-        p = take(NG_SW * cl * sizeof(R)); if (w) w->ssacmc = (R *)p;
-        p = take(NG_SW * cl * sizeof(R)); if (w) w->asmcmc = (R *)p;
-        p = take((size_t)3 * NG_SW * nc * sizeof(R)); if (w) w->cotsum = (R *)p;
+        w.sc = c.take<R>(SW_NFIELD * cl);
+        w.scidx = c.take<uint32_t>(cl);
+        w.colcloudy = c.take<uint8_t>(nc);
+        w.perm = c.take<int32_t>(nc);
+        w.nclear = c.take<int32_t>(1);
+        w.laycloudy = c.take<uint8_t>(cl);
+        w.alpha = c.take<R>(cl);
+        w.rcorr = c.take<R>(cl);
+        w.taucmc = c.take<R>(NG_SW * cl);
+        w.ssacmc = c.take<R>(NG_SW * cl);
+        w.asmcmc = c.take<R>(NG_SW * cl);
+        w.cotsum = c.take<R>((size_t)3 * NG_SW * nc);
         // parked planes of the band sweeps: k_sw_reform fp32 5 (gas optical depth + 2 x 2 upward reflectances), fp64 15 (no gas optical
         // depth, 2 x 5 layer properties instead); k_sw_bands 14
         // (the stage-dump instantiation is always k_sw_bands: sw_planes(true))
-        const size_t nplanes = (size_t)planes;
-        p = take(nplanes * NG_SW * nlay * (((size_t)nc + 255) & ~(size_t)255) * sizeof(R)); if (w) w->cell = (R *)p;
+        w.cell = c.take<R>((size_t)planes * NG_SW * nlay * (((size_t)nc + 255) & ~(size_t)255));
         // partial fluxes per slot: the units of k_sw_reform's mapping (23 fp32 / 32 fp64), which also cover the 14 bands of k_sw_bands (the
         // stage-dump hook always runs that kernel); 14 when GEOSRAD_SW_PATH=bands
         const size_t slots = sw_path == 2 ? (size_t)(sw_reform_nslot<R>() > NB_SW ? sw_reform_nslot<R>() : NB_SW) : (size_t)NB_SW;
-        p = take((size_t)4 * slots * (nlay + 1) * nc * sizeof(R)); if (w) w->part = (R *)p;
-        p = take((size_t)3 * slots * nc * sizeof(R)); if (w) w->bsfc = (R *)p;
-        p = take((size_t)8 * 6 * nc * sizeof(R)); if (w) w->cot = (R *)p;
+        w.part = c.take<R>((size_t)4 * slots * (nlay + 1) * nc);
+        w.bsfc = c.take<R>((size_t)3 * slots * nc);
+        w.cot = c.take<R>((size_t)8 * 6 * nc);
         // SOLAR_RADVAL layer sums of k_mcica<R, 2, true>, [3][15][20][nc]: only once a geosrad_rrtmg_sw_radval* call asked for them
-        if (w) w->rvsum = nullptr;
-        if (radval) { p = take((size_t)3 * RV_NSUM * RV_NPAR * nc * sizeof(R)); if (w) w->rvsum = (R *)p; }
-        return off;
+        rvsum = radval ? c.take<R>((size_t)3 * RV_NSUM * RV_NPAR * nc) : nullptr;
+        return c.off;
     }
     int sw_planes(bool dbg) const { return (sw_path == 2 && !dbg) ? (sizeof(R) == 4 ? 5 : 15) : 14; }
     int ensure_ws_sw(int nc, int nlay, int planes, bool radval)
@@ -1960,7 +1977,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (planes < ws_sw_planes) planes = ws_sw_planes;
         radval = radval || ws_sw_radval;
         const int want = (d_ws_sw && nlay == ws_sw_nlay && nc < ws_sw_ncol) ? ws_sw_ncol : nc;
-        const size_t need = ws_layout_sw(want, nlay, nullptr, nullptr, planes, radval);
+        SwArgs<R> w; R *rvsum;
+        const size_t need = ws_layout_sw(want, nlay, w, rvsum, Carve(), planes, radval);
         if (d_ws_sw.resize(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the SW workspace failed (" + std::to_string(need >> 20) +
                                                          " MiB); lower it with geosrad_set_chunk()");
         ws_sw_ncol = want; ws_sw_nlay = nlay; ws_sw_planes = planes; ws_sw_radval = radval;
@@ -2077,15 +2095,53 @@ template <typename R> struct Ctx : geosrad_ctx {
                       do_drfband, bndscl, indsolvar, solcycfrac, dbg, nullptr, radval);
     }
 
-    // RRTMG_SW band sweeps: k_sw_reform (lane = (column, unit of g-points); fp32 re-forms the cell optics in its second sweep and parks 12
-    // bytes per cell; in fp64 the second two-stream - IEEE divisions, double-precision exp / sqrt - costs more than the parked bytes it
-    // would save, 32.5 against 29.4 ms per 97 200 columns, so that instantiation parks the layer properties too);
-    // GEOSRAD_SW_PATH=bands selects the first mapping, k_sw_bands
+    // RRTMG_SW band sweeps of one chunk and the reduction into out (SwOutIx order, SO_NOUT entries; one that is null is not written):
+    // k_sw_reform (lane = (column, unit of g-points); fp32 re-forms the cell optics in its second sweep and parks 12 bytes per cell; in
+    // fp64 the second two-stream - IEEE divisions, double-precision exp / sqrt - costs more than the parked bytes it would save, 32.5
+    // against 29.4 ms per 97 200 columns, so that instantiation parks the layer properties too); GEOSRAD_SW_PATH=bands selects the first
+    // mapping, k_sw_bands, and the stage dumps (dbg) always run its dumping instantiation
     bool sw_reform_on() const { return sw_path == 2; }
+    int sw_sweeps(hipStream_t st, const SwArgs<R> &A, const SwSolar<R> &SV, void *const *out, int c0, bool dbg)
+    {
+        const dim3 blk(256), grid(band_grid(A.ncol, NB_SW));
+        const bool reform = sw_reform_on() && !dbg;
+        span_begin(8, st);
+        if (dbg) {
+            hipLaunchKernelGGL((k_sw_bands<R, true, true>), grid, blk, 0, st, A, h_S, SV);
+        } else if (reform) {
+            if (const int rc = hip_rc("sw_reform_launch", sw_reform_launch<R>(st, A, h_S, SV))) return rc;
+        } else {
+            hipLaunchKernelGGL((k_sw_bands<R, false, false>), grid, blk, 0, st, A, h_S, SV);
+            hipLaunchKernelGGL((k_sw_bands<R, true, false>), grid, blk, 0, st, A, h_S, SV);
+        }
+        span_end(st);
+        SwOut<R> O{};
+        auto Q = [&](int k) { return colp(out[k], c0); };
+        O.swuflx = Q(SO_UFLX); O.swdflx = Q(SO_DFLX); O.swuflxc = Q(SO_UFLXC); O.swdflxc = Q(SO_DFLXC);
+        O.nirr = Q(SO_NIRR); O.nirf = Q(SO_NIRF); O.parr = Q(SO_PARR); O.parf = Q(SO_PARF); O.uvrr = Q(SO_UVRR); O.uvrf = Q(SO_UVRF);
+        O.fswband = Q(SO_FSWBAND);
+        for (int k = 0; k < 8; k++) O.cot[k] = Q(SO_COT0 + k);
+        O.drband = Q(SO_DRBAND); O.dfband = Q(SO_DFBAND);
+        span_begin(9, st);
+        if (reform) { if (const int rc = hip_rc("sw_reform_reduce", sw_reform_reduce<R>(st, A, O))) return rc; }
+        else hipLaunchKernelGGL(k_sw_reduce<R>, dim3(grid256(A.ncol), A.nlay + 2), blk, 0, st, A, O);
+        span_end(st);
+        return GEOSRAD_OK;
+    }
 
-    // sw_na_out (SwOutIx order, all of SO_UFLX .. SO_COT0 + 7 non-null) requests an additional pass without the aerosol terms;
-    // radval ((GEOSRAD_RV_COUNT, ncol) device array) requests the SOLAR_RADVAL diagnostics: the RADVAL instantiation of k_mcica, then
-    // k_sw_radval - once per call, they do not depend on the aerosols
+    // the array checks sw_host makes before it stages anything and sw_run makes in its own order
+    int sw_check_arrays(const void *const *in, void *const *out, int iaer, int do_drfband)
+    {
+        for (int k = 0; k < S_NIN; k++)
+            if (!in[k] && !((k == S_TAUAER || k == S_SSAAER || k == S_ASMAER) && iaer != 10)) return fail(GEOSRAD_EINVAL, "null input array");
+        for (int k = 0; k < SO_DRBAND; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
+        if (do_drfband && (!out[SO_DRBAND] || !out[SO_DFBAND])) return fail(GEOSRAD_EINVAL, "do_drfband set but drband/dfband null");
+        return GEOSRAD_OK;
+    }
+
+    // sw_na_out (SwOutIx order, SO_NOUT entries, all of SO_UFLX .. SO_COT0 + 7 non-null) requests an additional pass without the aerosol
+    // terms; radval ((GEOSRAD_RV_COUNT, ncol) device array) requests the SOLAR_RADVAL diagnostics: the RADVAL instantiation of k_mcica,
+    // then k_sw_radval - once per call, they do not depend on the aerosols
     int sw_run(hipStream_t st, int ncol, int nlay, double scon, double adjes, int isolvar, const void *const *in, int iceflg, int liqflg,
                int dyofyr, int iaer, int cloudLM, int cloudMH, int normFlx, int32_t *clearCounts, void *const *out, int do_drfband,
                const void *bndscl, const void *indsolvar, const void *solcycfrac, void *const *dbg, void *const *sw_na_out,
@@ -2098,75 +2154,35 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (liqflg != 1) return fail(GEOSRAD_EINPUT, "cldprmc_sw: invalid liqflag");
         if (cloudLM == cloudMH) return fail(GEOSRAD_EINPUT, "invalid pressure super-layers!");
         if (iaer != 0 && iaer != 10) return fail(GEOSRAD_EINPUT, "iaer must be 0 or 10");
-        for (int k = 0; k < S_NIN; k++)
-            if (!in[k] && !((k == S_TAUAER || k == S_SSAAER || k == S_ASMAER) && iaer != 10)) return fail(GEOSRAD_EINVAL, "null input array");
-        for (int k = 0; k < SO_DRBAND; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
-        if (do_drfband && (!out[SO_DRBAND] || !out[SO_DFBAND])) return fail(GEOSRAD_EINVAL, "do_drfband set but drband/dfband null");
+        if (const int rc = sw_check_arrays(in, out, iaer, do_drfband)) return rc;
         if (radval && dbg) return fail(GEOSRAD_EINVAL, "the stage dumps do not produce the SOLAR_RADVAL diagnostics");
         SwSolar<R> SV;
-        int rc = sw_solar(scon, adjes, isolvar, (const R *)bndscl, (const R *)indsolvar, (const R *)solcycfrac, SV);
-        if (rc) return rc;
+        if (const int rc = sw_solar(scon, adjes, isolvar, (const R *)bndscl, (const R *)indsolvar, (const R *)solcycfrac, SV)) return rc;
 
         // one band's [layer][g<=12][column] plane must stay below 4 GiB (32-bit byte offsets)
-        const long cap = (long)(0xFFFFFFFFull / ((unsigned long long)nlay * 12ull * sizeof(R))) & ~255L;
-        int nc_max = ncol < chunk ? ncol : chunk;
-        if ((long)nc_max > cap) nc_max = (int)cap;
-        rc = ensure_ws_sw(nc_max, nlay, sw_planes(dbg != nullptr), radval != nullptr);
-        if (rc) return rc;
+        const int nc_max = chunk_cols(ncol, (long)(0xFFFFFFFFull / ((unsigned long long)nlay * 12ull * sizeof(R))) & ~255L);
+        if (const int rc = ensure_ws_sw(nc_max, nlay, sw_planes(dbg != nullptr), radval != nullptr)) return rc;
 
-        for (int c0 = 0; c0 < ncol; c0 += nc_max) {
-            const int nc = (ncol - c0) < nc_max ? (ncol - c0) : nc_max;
-            WsSw w;
-            ws_layout_sw(nc, nlay, &w, d_ws_sw, ws_sw_planes, ws_sw_radval);
+        return chunk_walk(ncol, nc_max, [&](int c0, int nc) -> int {
             SwArgs<R> A{};
+            R *rvsum;
+            ws_layout_sw(nc, nlay, A, rvsum, Carve(d_ws_sw), ws_sw_planes, ws_sw_radval);
             A.ncol = nc; A.ld = ncol; A.nlay = nlay; A.iceflg = iceflg; A.liqflg = liqflg; A.doy = dyofyr; A.cloudLM = cloudLM;
             A.cloudMH = cloudMH; A.iaer = iaer; A.normFlx = normFlx; A.do_drfband = do_drfband;
-            auto P = [&](int k) { return in[k] ? (const R *)in[k] + c0 : (const R *)nullptr; };
+            auto P = [&](int k) { return colp(in[k], c0); };
             A.play = P(S_PLAY); A.plev = P(S_PLEV); A.tlay = P(S_TLAY); A.h2o = P(S_H2O); A.o3 = P(S_O3); A.co2 = P(S_CO2);
             A.ch4 = P(S_CH4); A.o2 = P(S_O2); A.cld = P(S_CLD); A.ciwp = P(S_CIWP); A.clwp = P(S_CLWP); A.rei = P(S_REI);
             A.rel = P(S_REL); A.zm = P(S_ZM); A.alat = P(S_ALAT);
             A.tauaer = iaer == 10 ? P(S_TAUAER) : nullptr; A.ssaaer = iaer == 10 ? P(S_SSAAER) : nullptr;
             A.asmaer = iaer == 10 ? P(S_ASMAER) : nullptr;
             A.coszen = P(S_COSZEN); A.asdir = P(S_ASDIR); A.asdif = P(S_ASDIF); A.aldir = P(S_ALDIR); A.aldif = P(S_ALDIF);
-            A.sc = w.sc; A.scidx = w.scidx; A.colcloudy = w.colcloudy; A.laycloudy = w.laycloudy; A.perm = w.perm; A.nclear = w.nclear; A.alpha = w.alpha; A.rcorr = w.rcorr;
-            A.taucmc = w.taucmc; A.ssacmc = w.ssacmc; A.asmcmc = w.asmcmc; A.cotsum = w.cotsum; A.cell = w.cell; A.part = w.part;
-            A.bsfc = w.bsfc; A.cot = w.cot;
             A.err = d_err + 1;
             A.clearCounts = clearCounts + c0;
-            if (dbg) {
-                A.dbg_taug = (R *)dbg[0] + (size_t)c0 * NG_SW * nlay; A.dbg_taur = (R *)dbg[1] + (size_t)c0 * NG_SW * nlay;
-                A.dbg_ssi = (R *)dbg[2] + (size_t)c0 * NG_SW;
-            }
+            const size_t d0 = (size_t)c0 * NG_SW * nlay;      // a chunk's first record of the per-cell stage dumps
+            if (dbg) { A.dbg_taug = (R *)dbg[0] + d0; A.dbg_taur = (R *)dbg[1] + d0; A.dbg_ssi = (R *)dbg[2] + (size_t)c0 * NG_SW; }
+            if (const int e = rrtmg_front<2>(st, A, radval != nullptr, rvsum)) return e;
             const dim3 blk(256);
-            const unsigned gx = (unsigned)((nc + 255) / 256);
-            span_begin(6, st); hipLaunchKernelGGL(k_sw_validate<R>, dim3(gx), blk, 0, st, A);
-            if (iaer == 10) hipLaunchKernelGGL(k_sw_validate_aer<R>, dim3(gx, nlay), blk, 0, st, A);
-            hipLaunchKernelGGL(k_partition, dim3(1), dim3(1024), 0, st, nc, (const uint8_t *)w.colcloudy, w.perm, w.nclear); span_end(st);
-            span_begin(7, st); hipLaunchKernelGGL(k_sw_setcoef<R>, dim3(gx, nlay), blk, 0, st, A, (const SwDev<R> *)d_S); span_end(st);
-            span_begin(2, st); hipLaunchKernelGGL(k_overlap<R>, dim3(gx, nlay), blk, 0, st, nc, ncol, nlay, dyofyr, A.zm, A.alat,
-                               (const int32_t *)w.perm, (const int32_t *)w.nclear, (const LwDev<R> *)d_T, A.alpha, A.rcorr, A.laycloudy); span_end(st);
-            McArgs<R> M{};
-            M.ncol = nc; M.ld = ncol; M.nlay = nlay; M.nsubcol = NG_SW; M.doy = dyofyr; M.cloudLM = cloudLM; M.cloudMH = cloudMH;
-            M.iceflg = iceflg; M.liqflg = liqflg;
-            M.so[0] = 4; M.so[1] = 3; M.so[2] = 2; M.so[3] = 1;        // seed_order=[4,3,2,1] (SW/rrtmg_sw_rad.F90:1401)
-            M.cwp_tiny = (R)1.e-20;
-            M.play = A.play; M.cldf = A.cld; M.ciwp = A.ciwp; M.clwp = A.clwp; M.rei = A.rei; M.rel = A.rel;
-            M.alpha = A.alpha; M.rcorr = A.rcorr; M.perm = w.perm; M.nclear = w.nclear; M.cftop = w.colcloudy;
-            M.taucmc = A.taucmc; M.ssacmc = A.ssacmc; M.asmcmc = A.asmcmc; M.laycloudy = A.laycloudy; M.cotsum = A.cotsum; M.clearCounts = A.clearCounts; M.err = d_err + 1;
-            {
-                McPlan MP; int nseg = 0;
-                rc = mc_plan(2, NG_SW, nlay, MP, nseg);
-                if (rc) return rc;
-                span_begin(3, st);
-                M.rvsum = w.rvsum;
-                if (radval)
-                    hipLaunchKernelGGL((k_mcica<R, 2, true>), dim3(xcd_grid(nc, 64, nseg)), dim3(64), 0, st, M, MP, (const LwDev<R> *)d_T,
-                                       (const SwDev<R> *)d_S);
-                else
-                    hipLaunchKernelGGL((k_mcica<R, 2>), dim3(xcd_grid(nc, 64, nseg)), dim3(64), 0, st, M, MP, (const LwDev<R> *)d_T,
-                                       (const SwDev<R> *)d_S);
-                span_end(st);
-            }
+            const unsigned gx = grid256(nc);
             if (radval) {
                 // the sub-columns are summed in the groups of the band sweeps' own cotd?? / cotn?? family (sw_radval_kernels.hpp)
                 SwRvGroups G{};
@@ -2175,61 +2191,20 @@ template <typename R> struct Ctx : geosrad_ctx {
                     G.n = sw_reform_par_units<R>(sz);
                     for (int k = 0, e = 0; k < G.n; k++) { e += sz[k]; G.end[k] = e; }
                 } else { G.n = 3; G.end[0] = 8; G.end[1] = 14; G.end[2] = 20; }
-                hipLaunchKernelGGL(k_sw_radval<R>, dim3(gx, 4), blk, 0, st, A, h_S, SV, G, (const R *)w.rvsum, (R *)radval + c0);
+                hipLaunchKernelGGL(k_sw_radval<R>, dim3(gx, 4), blk, 0, st, A, h_S, SV, G, (const R *)rvsum, (R *)radval + c0);
             }
             if (dbg && dbg[3])       // cldprmc_sw stage dump (6-entry dbg of geosrad_rrtmg_sw_cldprmc)
-                hipLaunchKernelGGL(k_sw_dump_cldprmc<R>, dim3(gx, nlay), blk, 0, st, A, (R *)dbg[3] + (size_t)c0 * NG_SW * nlay,
-                                   (R *)dbg[4] + (size_t)c0 * NG_SW * nlay, (R *)dbg[5] + (size_t)c0 * NG_SW * nlay);
-            span_begin(8, st);
-            if (dbg) {
-                hipLaunchKernelGGL((k_sw_bands<R, true, true>), dim3(band_grid(nc, NB_SW)), blk, 0, st, A, h_S, SV);
-            } else if (sw_reform_on()) {
-                hipError_t e = sw_reform_launch<R>(st, A, h_S, SV);
-                if (e != hipSuccess) return fail(GEOSRAD_EHIP, std::string("sw_reform_launch: ") + hipGetErrorString(e));
-            } else {
-                hipLaunchKernelGGL((k_sw_bands<R, false, false>), dim3(band_grid(nc, NB_SW)), blk, 0, st, A, h_S, SV);
-                hipLaunchKernelGGL((k_sw_bands<R, true, false>), dim3(band_grid(nc, NB_SW)), blk, 0, st, A, h_S, SV);
-            }
-            span_end(st);
-            SwOut<R> O{};
-            auto Q = [&](int k) { return out[k] ? (R *)out[k] + c0 : (R *)nullptr; };
-            O.swuflx = Q(SO_UFLX); O.swdflx = Q(SO_DFLX); O.swuflxc = Q(SO_UFLXC); O.swdflxc = Q(SO_DFLXC);
-            O.nirr = Q(SO_NIRR); O.nirf = Q(SO_NIRF); O.parr = Q(SO_PARR); O.parf = Q(SO_PARF); O.uvrr = Q(SO_UVRR); O.uvrf = Q(SO_UVRF);
-            O.fswband = Q(SO_FSWBAND);
-            for (int k = 0; k < 8; k++) O.cot[k] = Q(SO_COT0 + k);
-            O.drband = Q(SO_DRBAND); O.dfband = Q(SO_DFBAND);
-            span_begin(9, st);
-            if (sw_reform_on() && !dbg) { hipError_t e = sw_reform_reduce<R>(st, A, O); if (e != hipSuccess) return fail(GEOSRAD_EHIP, std::string("sw_reform_reduce: ") + hipGetErrorString(e)); }
-            else hipLaunchKernelGGL(k_sw_reduce<R>, dim3(gx, nlay + 2), blk, 0, st, A, O);
-            span_end(st);
+                hipLaunchKernelGGL(k_sw_dump_cldprmc<R>, dim3(gx, nlay), blk, 0, st, A, (R *)dbg[3] + d0, (R *)dbg[4] + d0, (R *)dbg[5] + d0);
+            if (const int e = sw_sweeps(st, A, SV, out, c0, dbg != nullptr)) return e;
             if (sw_na_out && !dbg) {
                 // the GridComp's "no-aerosol" diagnostics (GEOS_SolarGridComp.F90:3249-3259 calls the whole of SORADCORE a second
                 // time): same columns, same clouds (McICA is seeded by the pressures), same gas optical depths - only the band
                 // sweeps and the reduction are repeated, without the aerosol terms; validation, setcoef and McICA are shared
                 A.iaer = 0; A.do_drfband = 0;
-                span_begin(8, st);
-                if (sw_reform_on()) {
-                    hipError_t e = sw_reform_launch<R>(st, A, h_S, SV);
-                    if (e != hipSuccess) return fail(GEOSRAD_EHIP, std::string("sw_reform_launch: ") + hipGetErrorString(e));
-                } else {
-                    hipLaunchKernelGGL((k_sw_bands<R, false, false>), dim3(band_grid(nc, NB_SW)), blk, 0, st, A, h_S, SV);
-                    hipLaunchKernelGGL((k_sw_bands<R, true, false>), dim3(band_grid(nc, NB_SW)), blk, 0, st, A, h_S, SV);
-                }
-                span_end(st);
-                SwOut<R> N{};
-                auto QN = [&](int k) { return (R *)sw_na_out[k] + c0; };
-                N.swuflx = QN(SO_UFLX); N.swdflx = QN(SO_DFLX); N.swuflxc = QN(SO_UFLXC); N.swdflxc = QN(SO_DFLXC);
-                N.nirr = QN(SO_NIRR); N.nirf = QN(SO_NIRF); N.parr = QN(SO_PARR); N.parf = QN(SO_PARF); N.uvrr = QN(SO_UVRR); N.uvrf = QN(SO_UVRF);
-                N.fswband = QN(SO_FSWBAND);
-                for (int k = 0; k < 8; k++) N.cot[k] = QN(SO_COT0 + k);
-                span_begin(9, st);
-                if (sw_reform_on()) { hipError_t e = sw_reform_reduce<R>(st, A, N); if (e != hipSuccess) return fail(GEOSRAD_EHIP, std::string("sw_reform_reduce: ") + hipGetErrorString(e)); }
-                else hipLaunchKernelGGL(k_sw_reduce<R>, dim3(gx, nlay + 2), blk, 0, st, A, N);
-                span_end(st);
+                return sw_sweeps(st, A, SV, sw_na_out, c0, false);
             }
-        }
-        HIPCHK(hipGetLastError());
-        return GEOSRAD_OK;
+            return GEOSRAD_OK;
+        });
     }
 
     // ---- RRTMG_SW, host pointers ---------------------------------------------------------------------------
@@ -2240,10 +2215,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         HIPCHK(hipSetDevice(device));
         if (ncol <= 0 || nlay <= 0) return fail(GEOSRAD_EINVAL, "bad ncol/nlay");
         if (radval && dbg) return fail(GEOSRAD_EINVAL, "the stage dumps do not produce the SOLAR_RADVAL diagnostics");
+        if (const int rc = sw_check_arrays(in, out, iaer, do_drfband)) return rc;
         auto aer = [](int k) { return k == S_TAUAER || k == S_SSAAER || k == S_ASMAER; };
-        for (int k = 0; k < S_NIN; k++) if (!in[k] && !(aer(k) && iaer != 10)) return fail(GEOSRAD_EINVAL, "null input array");
-        for (int k = 0; k < SO_DRBAND; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
-        if (do_drfband && (!out[SO_DRBAND] || !out[SO_DFBAND])) return fail(GEOSRAD_EINVAL, "do_drfband set but drband/dfband null");
         const size_t L = (size_t)nlay;
         HostArrs H(sizeof(R));
         const void *din[S_NIN] = {};
@@ -2317,9 +2290,15 @@ template <typename R> struct Ctx : geosrad_ctx {
         for (int k = 0; k < CO_NOUT; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
         if (na > 0 && (!aer[0] || !aer[1] || !aer[2])) return fail(GEOSRAD_EINVAL, "na > 0 but taua/ssaa/asya null");
         const int K1 = np + 1, K2 = np + 2;
-        const int nc_max = m < chunk ? m : chunk;
-        const size_t need = al((size_t)nc_max * CF_NFIELD * K1 * sizeof(R)) + al((size_t)nc_max * CH_NB * CH_NKIND * K2 * sizeof(R));
-        if (d_ws_ch.reserve(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the irrad workspace failed");
+        const int nc_max = chunk_cols(m);
+        R *rec, *part;
+        auto carve = [&](Carve c) {
+            rec = c.take<R>((size_t)nc_max * CF_NFIELD * K1);
+            part = c.take<R>((size_t)nc_max * CH_NB * CH_NKIND * K2);
+            return c.off;
+        };
+        if (d_ws_ch.reserve(carve(Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the irrad workspace failed");
+        carve(Carve(d_ws_ch));
         const int nband = trace ? 10 : 9;      // irrad.F90:478 (band 10 only with trace gases)
 #ifndef GEOSRAD_EXP_LDS_PAD
 #define GEOSRAD_EXP_LDS_PAD 0
@@ -2330,20 +2309,19 @@ template <typename R> struct Ctx : geosrad_ctx {
             if (hipFuncSetAttribute(kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
                 return fail(GEOSRAD_EINVAL, "np too large for the LDS-resident band state");
         }
-        for (int c0 = 0; c0 < m; c0 += nc_max) {
-            const int nc = (m - c0) < nc_max ? (m - c0) : nc_max;
+        return chunk_walk(m, nc_max, [&](int c0, int nc) -> int {
             ChouArgs<R> A{};
             A.m = nc; A.ld = m; A.np = np; A.trace = trace; A.ict = ict; A.icb = icb; A.ns = ns; A.na = na; A.nb = nb; A.co2 = (R)co2;
-            auto P = [&](int k) { return (const R *)in[k] + c0; };
+            auto P = [&](int k) { return colp(in[k], c0); };
             A.ple = P(C_PLE); A.ta = P(C_TA); A.wa = P(C_WA); A.oa = P(C_OA); A.tb = P(C_TB); A.n2o = P(C_N2O); A.ch4 = P(C_CH4);
             A.cfc11 = P(C_CFC11); A.cfc12 = P(C_CFC12); A.cfc22 = P(C_CFC22); A.fcld = P(C_FCLD);
             ChouGeos<R> G{};
             if (geos) { G = *geos; for (int l = 0; l < 4; l++) { G.q[l] += c0; G.r[l] += c0; } }
             else { A.cwc = P(C_CWC); A.reff = P(C_REFF); }
             A.fs = P(C_FS); A.tg = P(C_TG); A.eg = P(C_EG); A.tv = P(C_TV); A.ev = P(C_EV); A.rv = P(C_RV);
-            A.taua = aer[0] ? (R *)aer[0] + c0 : nullptr; A.ssaa = aer[1] ? (R *)aer[1] + c0 : nullptr; A.asya = aer[2] ? (R *)aer[2] + c0 : nullptr;
+            A.taua = colp(aer[0], c0); A.ssaa = colp(aer[1], c0); A.asya = colp(aer[2], c0);
             A.taudiag = (R *)out[CO_TAUDIAG] + c0;
-            A.rec = (R *)d_ws_ch.p; A.part = (R *)(d_ws_ch + al((size_t)nc_max * CF_NFIELD * K1 * sizeof(R)));
+            A.rec = rec; A.part = part;
             A.err = d_err + 2;
             span_begin(10, st);
             const dim3 gp((unsigned)((nc + 63) / 64), (unsigned)chou_prep_tiles<R>(np));
@@ -2355,16 +2333,15 @@ template <typename R> struct Ctx : geosrad_ctx {
             else hipLaunchKernelGGL(k_chou_bands<R>, dim3((unsigned)((nc + CH_CPW - 1) / CH_CPW), nband), dim3(64), lds, st, A, (const ChouDev<R> *)d_C);
             span_end(st);
             ChouOut<R> O{};
-            auto Q = [&](int k) { return (R *)out[k] + c0; };
+            auto Q = [&](int k) { return colp(out[k], c0); };
             O.flxu = Q(CO_FLXU); O.flcu = Q(CO_FLCU); O.flau = Q(CO_FLAU); O.flxau = Q(CO_FLXAU); O.flxd = Q(CO_FLXD); O.flcd = Q(CO_FLCD);
             O.flad = Q(CO_FLAD); O.flxad = Q(CO_FLXAD); O.dfdts = Q(CO_DFDTS); O.sfcem = Q(CO_SFCEM);
             hipLaunchKernelGGL(k_chou_reduce<R>, dim3((unsigned)((nc + 63) / 64), 9), dim3(256), 0, st, A, O, nband);
             if (!trace)      // band 10 of taudiag stays zero (the reference zeroes the array and never reaches band 10)
                 for (int k = 0; k < np; k++)
                     HIPCHK(hipMemsetAsync((R *)out[CO_TAUDIAG] + ((size_t)9 * np + k) * m + c0, 0, (size_t)nc * sizeof(R), st));
-        }
-        HIPCHK(hipGetLastError());
-        return GEOSRAD_OK;
+            return GEOSRAD_OK;
+        });
     }
 
     int irrad_host(int m, int np, const void *const *in, double co2, int trace, int ict, int icb, int ns, int na, int nb, void *const *aer,
@@ -2430,18 +2407,23 @@ template <typename R> struct Ctx : geosrad_ctx {
         for (int k = 0; k < SOO_DRBAND; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
         if (do_drfband && (!out[SOO_DRBAND] || !out[SOO_DFBAND])) return fail(GEOSRAD_EINVAL, "do_drfband set but drband/dfband null");
         const int K2 = np + 2;
-        const int nc_max = m < chunk ? m : chunk;
-        const size_t per = (size_t)nc_max * sizeof(R);
+        const int nc_max = chunk_cols(m);
+        const size_t per = (size_t)nc_max;
         // passes: k_sorad_pass (lane = column, the per-level arrays of every pass in HBM scratch planes, 30 x K2 reals per (column, pass))
         // or k_sorad_col (one block per column, everything on chip, no scratch; GEOSRAD_SORAD_PATH=col)
         // (a layer count whose on-chip arrays exceed the LDS takes the scratch-plane path; so does OVERCAST: k_sorad_col has no OVERCAST
         // variant, the OVERCAST passes are k_sorad_pass_oc whatever GEOSRAD_SORAD_PATH says)
         const bool col_path = !oc && sorad_col_path && K2 <= 256 && sorad_col_lds_reals<R>(np) * sizeof(R) <= (size_t)160 * 1024;
-        const size_t o_lay = 0, o_swh = o_lay + al(4 * K2 * per), o_colv = o_swh + al(K2 * per), o_cld = o_colv + al(8 * per),
-                     o_psum = o_cld + al((size_t)SO_NGRP * 4 * K2 * per), o_aer = o_psum + al((size_t)SO_NPASS * 3 * per),
-                     o_perm = o_aer + (col_path || oc ? 0 : al((size_t)3 * SO_NGATHER * np * per)), o_cls = o_perm + al((size_t)nc_max * sizeof(int32_t)),
-                     o_off = o_cls + al((size_t)nc_max), o_scr = o_off + al(16 * sizeof(int32_t)),
-                     need = o_scr + (col_path ? 0 : al((size_t)SO_NPASS * SO_NPLANE * K2 * per));
+        SoradArgs<R> W{};      // the workspace planes, the same for every chunk; the gathered aerosol planes and the scratch planes only on the paths that use them
+        auto carve = [&](Carve c) {
+            W.lay = c.take<R>(4 * K2 * per); W.swh = c.take<R>(K2 * per); W.colv = c.take<R>(8 * per); W.cld = c.take<R>((size_t)SO_NGRP * 4 * K2 * per);
+            W.psum = c.take<R>((size_t)SO_NPASS * 3 * per);
+            W.aer = col_path || oc ? nullptr : c.take<R>((size_t)3 * SO_NGATHER * np * per);
+            W.perm = c.take<int32_t>(per); W.cls = c.take<uint8_t>(per); W.cls_off = c.take<int32_t>(16);
+            W.scr = col_path ? nullptr : c.take<R>((size_t)SO_NPASS * SO_NPLANE * K2 * per);
+            return c.off;
+        };
+        const size_t need = carve(Carve());
         const size_t so_lds = sorad_col_lds_reals<R>(np) * sizeof(R);
         if (col_path) {
             if (so_lds > so_lds_set) {
@@ -2451,22 +2433,18 @@ template <typename R> struct Ctx : geosrad_ctx {
         }
         if (d_ws_so.reserve(need) != hipSuccess)
             return fail(GEOSRAD_ENOMEM, "hipMalloc of the sorad workspace failed (" + std::to_string(need >> 20) + " MiB); lower it with geosrad_set_chunk()");
-        for (int c0 = 0; c0 < m; c0 += nc_max) {
-            const int nc = (m - c0) < nc_max ? (m - c0) : nc_max;
-            SoradArgs<R> A{};
+        carve(Carve(d_ws_so));
+        return chunk_walk(m, nc_max, [&](int c0, int nc) -> int {
+            SoradArgs<R> A = W;
             A.m = nc; A.ld = m; A.np = np; A.ict = ict; A.icb = icb; A.do_drfband = do_drfband; A.co2 = (R)co2;
             for (int p = 0; p < 5; p++) A.hk[p] = ((const R *)hk_uv)[p];
             for (int ib = 0; ib < 3; ib++) for (int ik = 0; ik < 10; ik++) A.hk[5 + ib * 10 + ik] = ((const R *)hk_ir)[ik * 3 + ib];   // hk_ir(3,10)
-            auto P = [&](int k) { return (const R *)in[k] + c0; };
+            auto P = [&](int k) { return colp(in[k], c0); };
             A.cosz = P(SI_COSZ); A.pl = P(SI_PL); A.ta = P(SI_TA); A.wa = P(SI_WA); A.oa = P(SI_OA); A.cwc = P(SI_CWC); A.fcld = P(SI_FCLD);
             A.reff = P(SI_REFF); A.taua = P(SI_TAUA); A.ssaa = P(SI_SSAA); A.asya = P(SI_ASYA); A.rsuvbm = P(SI_RSUVBM);
             A.rsuvdf = P(SI_RSUVDF); A.rsirbm = P(SI_RSIRBM); A.rsirdf = P(SI_RSIRDF);
-            A.lay = (R *)(d_ws_so + o_lay); A.swh = (R *)(d_ws_so + o_swh); A.colv = (R *)(d_ws_so + o_colv); A.cld = (R *)(d_ws_so + o_cld);
-            A.psum = (R *)(d_ws_so + o_psum); A.scr = col_path ? nullptr : (R *)(d_ws_so + o_scr);
-            A.aer = col_path || oc ? nullptr : (R *)(d_ws_so + o_aer); A.perm = (int32_t *)(d_ws_so + o_perm); A.cls = (uint8_t *)(d_ws_so + o_cls);
-            A.cls_off = (int32_t *)(d_ws_so + o_off);
             const dim3 blk(256);
-            const unsigned gx = (unsigned)((nc + 255) / 256);
+            const unsigned gx = grid256(nc);
             span_begin(12, st);
             if (oc) {          // OVERCAST: one class, positions are columns
                 hipLaunchKernelGGL(k_sorad_ident<R>, dim3(gx), blk, 0, st, A);
@@ -2483,7 +2461,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             }
             span_end(st);
             SoradOut<R> O{};
-            auto Q = [&](int k) { return out[k] ? (R *)out[k] + c0 : (R *)nullptr; };
+            auto Q = [&](int k) { return colp(out[k], c0); };
             O.flx = Q(SOO_FLX); O.flc = Q(SOO_FLC); O.fdiruv = Q(SOO_FDIRUV); O.fdifuv = Q(SOO_FDIFUV); O.fdirpar = Q(SOO_FDIRPAR);
             O.fdifpar = Q(SOO_FDIFPAR); O.fdirir = Q(SOO_FDIRIR); O.fdifir = Q(SOO_FDIFIR); O.flxu = Q(SOO_FLXU); O.flcu = Q(SOO_FLCU);
             O.flx_sfc_band = Q(SOO_SFCBAND); O.drband = Q(SOO_DRBAND); O.dfband = Q(SOO_DFBAND);
@@ -2513,9 +2491,8 @@ template <typename R> struct Ctx : geosrad_ctx {
             span_end(st);               // the slot times k_sorad_pass alone (= its average duration in a rocprofv3 kernel trace)
             if (!col_path) hipLaunchKernelGGL(k_sorad_sum<R>, dim3(gx, np + 1), blk, 0, st, A, O);
             hipLaunchKernelGGL(k_sorad_reduce<R>, dim3(gx), blk, 0, st, A, (const SoradDev<R> *)d_O, O);
-        }
-        HIPCHK(hipGetLastError());
-        return GEOSRAD_OK;
+            return GEOSRAD_OK;
+        });
     }
 
     int sorad_host(int m, int np, int nb, const void *const *in, double co2, int ict, int icb, const void *hk_uv, const void *hk_ir,
@@ -2557,10 +2534,11 @@ template <typename R> struct Ctx : geosrad_ctx {
             }
         }
         const size_t cl = (size_t)ncol * nlay;
-        const size_t need = 2 * al(cl * sizeof(R));
-        if (d_mc.reserve(need) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the McICA scratch failed");
-        R *d_alpha = (R *)d_mc.p, *d_rcorr = (R *)(d_mc + al(cl * sizeof(R)));
-        const unsigned gx = (unsigned)((ncol + 255) / 256);
+        R *d_alpha, *d_rcorr;
+        auto carve = [&](Carve c) { d_alpha = c.take<R>(cl); d_rcorr = c.take<R>(cl); return c.off; };
+        if (d_mc.reserve(carve(Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the McICA scratch failed");
+        carve(Carve(d_mc));
+        const unsigned gx = grid256(ncol);
         span_begin(2, st);
         hipLaunchKernelGGL(k_overlap<R>, dim3(gx, nlay), dim3(256), 0, st, ncol, ncol, nlay, doy, (const R *)zmid, (const R *)alat,
                            (const int32_t *)nullptr, (const int32_t *)nullptr, (const LwDev<R> *)d_T, d_alpha, d_rcorr, (uint8_t *)nullptr);
@@ -2573,8 +2551,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         M.alpha = d_alpha; M.rcorr = d_rcorr;
         M.cldy = cldy; M.ciwp_s = (R *)ciwp_s; M.clwp_s = (R *)clwp_s;
         McPlan MP; int nseg = 0;
-        int rc = mc_plan(1, nsubcol, nlay, MP, nseg);
-        if (rc) return rc;
+        if (const int rc = mc_plan(1, nsubcol, nlay, MP, nseg)) return rc;
         const size_t lds = mc_sa_lds_reals(nlay, nsubcol) * sizeof(R);
         const long nblk = ((long)ncol * nsubcol + 64 * MC_SA_K - 1) / (64 * MC_SA_K);
         span_begin(3, st);
@@ -2613,22 +2590,22 @@ template <typename R> struct Ctx : geosrad_ctx {
         HIPCHK(hipSetDevice(device));
         if (ncol <= 0 || nlay < 4 || nsubcol <= 0) return fail(GEOSRAD_EINVAL, "bad ncol/nlay/nsubcol");
         const size_t cl = (size_t)ncol * nlay, co = cl * nsubcol;
-        size_t off = 0;
-        auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-        const size_t o_z = take(cl * sizeof(R)), o_p = take(cl * sizeof(R)), o_f = take(cl * sizeof(R)), o_i = take(cl * sizeof(R)),
-                     o_l = take(cl * sizeof(R)), o_a = take((size_t)ncol * sizeof(R)), o_cy = take(co * 4), o_ci = take(co * sizeof(R)),
-                     o_cl = take(co * sizeof(R));
-        if (d_io.reserve(off) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the host-API staging buffer failed");
+        R *d[6], *d_ci, *d_cl;      // zmid, play, cldfrac, ciwp, clwp (nlay, ncol), alat (ncol); the generator's three outputs behind them
+        int32_t *d_cy;
+        auto carve = [&](Carve c) {
+            for (int k = 0; k < 6; k++) d[k] = c.take<R>(k == 5 ? (size_t)ncol : cl);
+            d_cy = c.take<int32_t>(co); d_ci = c.take<R>(co); d_cl = c.take<R>(co);
+            return c.off;
+        };
+        if (d_io.reserve(carve(Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the host-API staging buffer failed");
+        carve(Carve(d_io));
         const void *src[6] = {zmid, play, cldfrac, ciwp, clwp, alat};
-        const size_t dst[6] = {o_z, o_p, o_f, o_i, o_l, o_a};
         for (int k = 0; k < 6; k++)
-            HIPCHK(hipMemcpyAsync(d_io + dst[k], src[k], (k == 5 ? (size_t)ncol : cl) * sizeof(R), hipMemcpyHostToDevice, stream));
-        const int rc = mcica_dev(stream, ncol, nsubcol, nlay, d_io + o_z, d_io + o_a, doy, d_io + o_p, d_io + o_f, d_io + o_i, d_io + o_l, cwp_tiny, so,
-                       (int32_t *)(d_io + o_cy), d_io + o_ci, d_io + o_cl);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(cldy, d_io + o_cy, co * 4, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(ciwp_s, d_io + o_ci, co * sizeof(R), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(clwp_s, d_io + o_cl, co * sizeof(R), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(d[k], src[k], (k == 5 ? (size_t)ncol : cl) * sizeof(R), hipMemcpyHostToDevice, stream));
+        if (const int rc = mcica_dev(stream, ncol, nsubcol, nlay, d[0], d[5], doy, d[1], d[2], d[3], d[4], cwp_tiny, so, d_cy, d_ci, d_cl)) return rc;
+        HIPCHK(hipMemcpyAsync(cldy, d_cy, co * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(ciwp_s, d_ci, co * sizeof(R), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(clwp_s, d_cl, co * sizeof(R), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         return GEOSRAD_OK;
     }

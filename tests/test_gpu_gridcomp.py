@@ -235,6 +235,67 @@ def test_sw_driver_no_aerosol_flavour_shares_the_cloud_generator(gpu_ctx, rk):
     assert np.abs(tout["FSC"].cpu().numpy() - tout["FSCNA"].cpu().numpy()).max() > 1e-3
 
 
+@pytest.fixture(scope="module")
+def sw_bands_ctx():
+    """contexts whose RRTMG_SW band sweeps are k_sw_bands (GEOSRAD_SW_PATH=bands, read when the context is created)"""
+    import os
+    from geosradiation_gridcomp_amd.api import Context
+    old = os.environ.get("GEOSRAD_SW_PATH")
+    os.environ["GEOSRAD_SW_PATH"] = "bands"
+    try:
+        ctxs = {4: Context(4), 8: Context(8)}
+    finally:
+        if old is None:
+            del os.environ["GEOSRAD_SW_PATH"]
+        else:
+            os.environ["GEOSRAD_SW_PATH"] = old
+    yield ctxs
+    for c in ctxs.values():
+        c.close()
+
+
+@pytest.mark.parametrize("path", ["reform", "bands"])
+@pytest.mark.parametrize("rk", [4, 8])
+def test_sw_driver_no_aerosol_pass_through_ragged_chunks(gpu_ctx, sw_bands_ctx, rk, path):
+    """the no-aerosol pass of geosrad_sw_driver_rrtmg_dev on 150 columns in chunks of 64 + 64 + 22: every output, both flavours, has the
+    bits of the unchunked call, under either mapping of the band sweeps; and FSWBANDNA is FSWBAND of a call without aerosols"""
+    ctx = (gpu_ctx if path == "reform" else sw_bands_ctx)[rk]; dt = ctx.dtype
+    ncol, lm = 150, 72
+    inp = synth.make_columns(ncol, lm, start=2718, cloudy_frac=0.6, aerosol=True)
+    f = synth.geos_sw_fields(inp)
+    consts = G.swd_consts()
+    shapes = {k: (ncol,) for k in G.SWD_OUT}
+    shapes.update({k: (lm + 1, ncol) for k in ("FSW", "FSC", "FSWU", "FSCU", "FSWNA", "FSCNA", "FSWUNA", "FSCUNA")})
+    shapes["FSWBAND"] = (14, ncol); shapes["FSWBANDNA"] = (14, ncol)
+    args = (3, 1, 1361.0, 1.0, 0, int(inp["dyofyr"]))
+
+    def run(fields, names, chunk, aerosols):
+        tin, ptr = _dev(fields, dt)          # the driver normalises the aerosol triplet in place: fresh copies for every call
+        tout, pout = _zeros({k: shapes[k] for k in names}, dt)
+        ptr.update(pout)
+        ctx.set_chunk(chunk)
+        try:
+            ctx.sw_driver_rrtmg_dev(_stream(), ncol, lm, 14 if aerosols else 0, ptr, consts, *args, aerosols, f["LCLDLM"], f["LCLDMH"], 1)
+            ctx.check(_stream())
+        finally:
+            ctx.set_chunk(131072)
+        return {k: v.cpu().numpy() for k, v in tout.items()}
+
+    ctx.set_inhomogeneity(1)
+    try:
+        whole = run(f, list(shapes), 131072, True)
+        chunked = run(f, list(shapes), 64, True)
+        f0 = dict(f); f0["TAUA"] = None; f0["SSAA"] = None; f0["ASYA"] = None
+        bare = run(f0, ["FSW", "FSC", "FSWU", "FSCU", "FSWBAND"], 131072, False)
+    finally:
+        ctx.set_inhomogeneity(0)
+    for k in shapes:
+        assert np.array_equal(chunked[k], whole[k]), k
+    assert np.array_equal(whole["FSWBANDNA"], bare["FSWBAND"])
+    assert np.abs(whole["FSWBAND"] - whole["FSWBANDNA"]).max() > 1e-3          # the aerosols do matter in the regular flavour
+    assert not (whole["FSWNA"] == -7.0).any() and not (whole["FSCUNA"] == -7.0).any()
+
+
 def test_lw_driver_137_layers_single_column_and_chunked_batches(gpu_ctx):
     """edge sizes: BASELINE configs[4] layer count, one column, and a batch the solver splits into several chunks -- every column
     must come out the same whatever the batching (bitwise)"""

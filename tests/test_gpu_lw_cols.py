@@ -100,3 +100,22 @@ def test_cols_equals_default_path_and_batching_is_invisible(cols_ctx, gpu_ctx, r
         assert np.abs(a[k].astype(np.float64) - d[k]).max() <= 0.1 * tol, k
         assert np.abs(a[k][:, :48].astype(np.float64) - r[k]).max() <= tol, k
     np.testing.assert_array_equal(a["clearCounts"], d["clearCounts"])
+
+
+@pytest.mark.parametrize("rk", [8, 4])
+def test_cols_context_takes_the_bands_path_for_a_rats_call(cols_ctx, gpu_ctx, rk):
+    """the RATS passes need the band partials of the reduction, so a call with RATS takes the lw_bands path throughout whatever
+    GEOSRAD_LW_PATH says: the same bits as the default context, chunked (64 + 64 + 22) and at once"""
+    from tests.test_gpu_lw import rats_dev, ragged_columns, RATS_GASES, RATS_OUT
+    inp = ragged_columns()
+    for ctx in (cols_ctx[rk], gpu_ctx[rk]):
+        ctx.set_inhomogeneity(1)
+    try:
+        want = rats_dev(gpu_ctx[rk], inp, RATS_GASES, 131072)
+        got = {chunk: rats_dev(cols_ctx[rk], inp, RATS_GASES, chunk) for chunk in (131072, 64)}
+    finally:
+        for ctx in (cols_ctx[rk], gpu_ctx[rk]):
+            ctx.set_inhomogeneity(0)
+    for chunk, g in got.items():
+        for k in RATS_OUT:
+            assert np.array_equal(g[k], want[k]), (chunk, k)

@@ -58,3 +58,22 @@ def test_split_fluxes_match_reference_golden(split_ctx, name, rk):
     for k in FLUX:
         tol = (2e-5 if rk == 4 else 1e-8) if "dTs" in k else (2e-3 if rk == 4 else 1e-6)
         assert np.abs(o[k].astype(np.float64) - g[f"{kind}_{k}"].astype(np.float64)).max() <= tol, k
+
+
+@pytest.mark.parametrize("rk", [8, 4])
+def test_split_rats_through_ragged_chunks(split_ctx, rk):
+    """the RATS passes of the split path (k_lw_cells + k_lw_sweep over each gas's bands): chunks of 64 + 64 + 22 columns give the bits
+    of the split context's own one-chunk call"""
+    from tests.test_gpu_lw import rats_dev, ragged_columns, RATS_GASES, RATS_OUT
+    ctx = split_ctx[rk]
+    inp = ragged_columns()
+    ctx.set_inhomogeneity(1)
+    try:
+        whole = rats_dev(ctx, inp, RATS_GASES, 131072)
+        chunked = rats_dev(ctx, inp, RATS_GASES, 64)
+    finally:
+        ctx.set_inhomogeneity(0)
+    for k in RATS_OUT:
+        assert np.array_equal(chunked[k], whole[k]), k
+    for r in range(len(RATS_GASES)):
+        assert not np.array_equal(whole["uflx_rat"][r], whole["uflx"]), RATS_GASES[r]
