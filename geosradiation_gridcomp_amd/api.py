@@ -493,6 +493,17 @@ class Context:
                                                        ctypes.c_double(taucrit), cs, self._ptr_array(G.SWK_IN, ptr),
                                                        self._ptr_array(G.SWK_OUT, ptr)))
 
+    def sw_update_cldhb_dev(self, stream, ncol, lm, lcldmh, lcldlm, doy, ptr, consts=None):
+        """heartbeat McICA cloud fractions CLD??SWHB of UPDATE_EXPORT (GEOS_SolarGridComp.F90:7060-7223, SOLAR_RADVAL): `ptr` name -> device
+        address for gridcomp.SWHB_IN / SWHB_OUT (a missing export = not associated); lcldmh / lcldlm in model ordering; doy = day of the
+        year (the correlation lengths); consts in gridcomp.SWHB_CONST order (default: the library's MAPL_GRAV and MAPL_RGAS).  The context's
+        set_inhomogeneity / initialize_cloud_subcol_gen settings apply, as for generate_stochastic_clouds_dev."""
+        from . import gridcomp as G
+        ci = ctypes.c_int
+        cs = None if consts is None else (ctypes.c_double * len(G.SWHB_CONST))(*consts)
+        self._chk(self.L.geosrad_sw_update_cldhb_dev(self.h, ctypes.c_void_p(stream), ci(ncol), ci(lm), ci(int(lcldmh)), ci(int(lcldlm)),
+                                                      ci(int(doy)), cs, self._ptr_array(G.SWHB_IN, ptr), self._ptr_array(G.SWHB_OUT, ptr)))
+
     def sw_driver_rrtmg_dev(self, stream, ncol, lm, nb_aer, ptr, consts, iceflg, liqflg, sc, dist, isolvar, dyofyr, include_aerosols,
                             lcldlm, lcldmh, normflx=1, bndsolvar=None, indsolvar=None):
         """RRTMG branch of SORADCORE on the packed daytime columns (GEOS_SolarGridComp.F90:6113-6450)."""

@@ -611,6 +611,8 @@ struct geosrad_ctx {
     virtual int sw_update_surface_dev(hipStream_t st, int ncol, int lm, double undef, const void *const *in, void *const *out) = 0;
     virtual int sw_update_clouds_dev(hipStream_t st, int ncol, int lm, int lcldmh, int lcldlm, double taucrit, const double *consts,
                                      const void *const *in, void *const *out) = 0;
+    virtual int sw_update_cldhb_dev(hipStream_t st, int ncol, int lm, int lcldmh, int lcldlm, int doy, const double *consts,
+                                    const void *const *in, void *const *out) = 0;
     virtual int rad_tendencies_dev(hipStream_t st, int ncol, int lm, double grav, double cp, const void *const *in,
                                    void *const *out) = 0;
     virtual int sw_host(int ncol, int nlay, double scon, double adjes, int isolvar, const void *const *in, int iceflg, int liqflg,
@@ -738,6 +740,7 @@ template <typename R> struct Ctx : geosrad_ctx {
     DevBuf<> d_ws_ch;
     DevBuf<> d_ws_lwk;      // lw_driver_chou_dev: irrad's per-column surface arguments (+ TAUDIAG when not exported)
     DevBuf<> d_ws_drvs[2];      // RRTMG-side arrays of the LW / SW GridComp drivers (separate: the two may run on two streams)
+    DevBuf<> d_ws_hb;           // sw_update_cldhb_dev: overlap correlation planes, cloud-layer range, partition and counts of one chunk
     // McICA segment plans (jump-ahead constants), cached per (mode, nsubcol, nlay, inhomogeneous?)
     struct PlanEntry { DevBuf<McSegDev> d_seg; int nseg; KissJump jsub, jhalf; };
     std::map<std::tuple<int, int, int, int>, PlanEntry> plans;
@@ -924,10 +927,11 @@ template <typename R> struct Ctx : geosrad_ctx {
     }
 
     // not counted: d_ws_swc, d_mc, d_zero, d_xcw, d_tab_so, the fixed-size structs and McICA plans, the pipeline slots
+    // (d_ws_hb is counted: like the solvers' workspaces it is sized by the chunk, two real planes of nlay x chunk columns)
     size_t workspace_bytes() const override
     {
         size_t t = 0;
-        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
+        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_ws_hb, &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
             t += b->bytes;
         return t;
     }
@@ -1709,6 +1713,57 @@ template <typename R> struct Ctx : geosrad_ctx {
         hipLaunchKernelGGL((k_sw_update_clouds<R>), dim3(grid256(ncol)), dim3(256), 0, st, U, (const SoradDev<R> *)d_O);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
+    }
+
+    // CLD??SWHB of UPDATE_EXPORT (mcica_kernels.hpp: k_swhb_prep, k_swhb_count, k_swhb_export), chunk by chunk
+    int sw_update_cldhb_dev(hipStream_t st, int ncol, int lm, int lcldmh, int lcldlm, int doy, const double *consts,
+                            const void *const *in, void *const *out) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (ncol < 1) return fail(GEOSRAD_EINVAL, "bad ncol");
+        if (lm < 4 || lm > 0xFFFE) return fail(GEOSRAD_EINVAL, "the generator's seeds need four layers (and lm < 65535)");
+        if (!(1 < lcldmh && lcldmh < lcldlm && lcldlm <= lm)) return fail(GEOSRAD_EINVAL, "super-layer levels must satisfy 1 < lcldmh < lcldlm <= lm");
+        bool any = false;
+        for (int k = 0; k < GEOSRAD_SWHB_NOUT; k++) any = any || out[k];
+        if (!any) return GEOSRAD_OK;
+        for (int k = 0; k < GEOSRAD_SWHB_NIN; k++)
+            if (!in[k]) return fail(GEOSRAD_EINVAL, "null input field");
+        HbArgs<R> H{};
+        H.lm = lm; H.ld = ncol; H.doy = doy; H.lcldmh = lcldmh; H.lcldlm = lcldlm;
+        // MAPL_GRAV, MAPL_RGAS = MAPL_RUNIV / MAPL_AIRMW (MAPL_Constants)
+        H.grav = (R)(consts ? consts[GEOSRAD_SWHB_C_GRAV] : 9.80665); H.rgas = (R)(consts ? consts[GEOSRAD_SWHB_C_RGAS] : 8314.47 / 28.965);
+        H.cwp_tiny = (R)1.e-20;                                       // (:7177)
+        const int nc_max = chunk_cols(ncol);
+        const char *ab = getenv("GEOSRAD_SWHB_COMPACT");              // A/B of the compaction only (profiles/r08_sw_cldhb.md)
+        const bool compact = ab ? atoi(ab) != 0 : SWHB_COMPACT;
+        int32_t *perm, *nclear;
+        auto carve = [&](Carve c) {
+            const size_t cl = (size_t)lm * nc_max;
+            H.alpha = c.take<R>(cl); H.rcorr = c.take<R>(cl);
+            H.cf0 = c.take<uint16_t>(nc_max); H.cf1 = c.take<uint16_t>(nc_max); H.cloudy = c.take<uint8_t>(nc_max);
+            perm = c.take<int32_t>(compact ? nc_max : 0); nclear = c.take<int32_t>(compact ? 1 : 0);
+            H.cnt = c.take<int32_t>((size_t)4 * nc_max);
+            return c.off;
+        };
+        const size_t need = carve(Carve());
+        if (d_ws_hb.reserve(need) != hipSuccess)
+            return fail(GEOSRAD_ENOMEM, "hipMalloc of the CLD??SWHB workspace failed (" + std::to_string(need >> 20) + " MiB); lower it with geosrad_set_chunk()");
+        carve(Carve(d_ws_hb));
+        if (compact) { H.perm = perm; H.nclear = nclear; }
+        McPlan MP; int nseg = 0;
+        if (const int rc = mc_plan(1, HB_NSUB, lm, MP, nseg)) return rc;
+        const LwDev<R> *dT = d_T;
+        return chunk_walk(ncol, nc_max, [&](int c0, int nc) {
+            H.ncol = nc;
+            H.fcld = colp(in[GEOSRAD_SWHB_FCLD], c0); H.ple = colp(in[GEOSRAD_SWHB_PLE], c0); H.t = colp(in[GEOSRAD_SWHB_T], c0);
+            H.qi = colp(in[GEOSRAD_SWHB_QI], c0); H.ql = colp(in[GEOSRAD_SWHB_QL], c0); H.lats = colp(in[GEOSRAD_SWHB_LATS], c0);
+            for (int k = 0; k < GEOSRAD_SWHB_NOUT; k++) H.out[k] = colp(out[k], c0);
+            hipLaunchKernelGGL((k_swhb_prep<R>), dim3(grid256(nc)), dim3(256), 0, st, H, dT);
+            if (compact) hipLaunchKernelGGL(k_partition, dim3(1), dim3(1024), 0, st, nc, (const uint8_t *)H.cloudy, perm, nclear);
+            hipLaunchKernelGGL((k_swhb_count<R>), dim3(xcd_grid(nc, 64, nseg)), dim3(64), 0, st, H, MP, dT);
+            hipLaunchKernelGGL((k_swhb_export<R>), dim3(grid256(nc)), dim3(256), 0, st, H);
+            return GEOSRAD_OK;
+        });
     }
 
     // ---- lit-column compaction (GEOS_SolarGridComp.F90:3686, PackIt / UnPackIt :7753-7799) --------------------------------------
@@ -2746,6 +2801,7 @@ struct MultiCtx final : geosrad_ctx {
     int sw_update_export_dev(hipStream_t, int, int, int, const void *const *, void *const *) override { return nodev("geosrad_sw_update_export_dev"); }
     int sw_update_surface_dev(hipStream_t, int, int, double, const void *const *, void *const *) override { return nodev("geosrad_sw_update_surface_dev"); }
     int sw_update_clouds_dev(hipStream_t, int, int, int, int, double, const double *, const void *const *, void *const *) override { return nodev("geosrad_sw_update_clouds_dev"); }
+    int sw_update_cldhb_dev(hipStream_t, int, int, int, int, int, const double *, const void *const *, void *const *) override { return nodev("geosrad_sw_update_cldhb_dev"); }
     int rad_tendencies_dev(hipStream_t, int, int, double, double, const void *const *, void *const *) override { return nodev("geosrad_rad_tendencies_dev"); }
     int lit_index_dev(hipStream_t, int, const void *, int32_t *, int32_t *, int32_t *, int *) override { return nodev("geosrad_lit_index_dev"); }
     int lit_pack_dev(hipStream_t, int, int, int, const int32_t *, const int32_t *, const void *, void *) override { return nodev("geosrad_lit_pack_dev"); }
@@ -3242,6 +3298,13 @@ int geosrad_sw_update_clouds_dev(geosrad_ctx *c, void *stream, int ncol, int lm,
 {
     if (!c || !in || !out) return GEOSRAD_EINVAL;
     return c->sw_update_clouds_dev((hipStream_t)stream, ncol, lm, lcldmh, lcldlm, taucrit, consts, in, out);
+}
+
+int geosrad_sw_update_cldhb_dev(geosrad_ctx *c, void *stream, int ncol, int lm, int lcldmh, int lcldlm, int doy, const double *consts,
+                                const void *const *in, void *const *out)
+{
+    if (!c || !in || !out) return GEOSRAD_EINVAL;
+    return c->sw_update_cldhb_dev((hipStream_t)stream, ncol, lm, lcldmh, lcldlm, doy, consts, in, out);
 }
 
 int geosrad_rad_tendencies_dev(geosrad_ctx *c, void *stream, int ncol, int lm, double grav, double cp, const void *const *in,

@@ -151,16 +151,13 @@ template <typename R> GR_DEV R zcw_combine(const ZcwReq<R> &q)
     return nf_add(nf_add(nf_add(t1, t2), t3), t4);
 }
 
-// KISS seeds from the fractional part of the four lowest-layer pressures (cloud_subcol_gen.F90:375-400)
-template <typename R> GR_DEV Kiss kiss_seed(const R *__restrict__ play, int ld, int nlay, int col, bool surface_at_one,
-                                            const int *so)
+// KISS seeds from the fractional part of the four lowest-layer pressures (cloud_subcol_gen.F90:375-400); pl: their play [hPa], the
+// lowest layer first
+template <typename R> GR_DEV Kiss kiss_seed(const R (&pl)[4], const int *so)
 {
     R pseed[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int lay = surface_at_one ? k : nlay - 1 - k;
-        pseed[k] = nf_mul(play[(size_t)lay * ld + col], (R)100.);
-    }
+    for (int k = 0; k < 4; k++) pseed[k] = nf_mul(pl[k], (R)100.);
     uint32_t sd[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -172,6 +169,15 @@ template <typename R> GR_DEV Kiss kiss_seed(const R *__restrict__ play, int ld, 
     }
     Kiss k; k.s1 = sd[0]; k.s2 = sd[1]; k.s3 = sd[2]; k.s4 = sd[3];
     return k;
+}
+// the same from a play array (nlay, ld) in either vertical ordering
+template <typename R> GR_DEV Kiss kiss_seed(const R *__restrict__ play, int ld, int nlay, int col, bool surface_at_one,
+                                            const int *so)
+{
+    R pl[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) pl[k] = play[(size_t)(surface_at_one ? k : nlay - 1 - k) * ld + col];
+    return kiss_seed<R>(pl, so);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -841,6 +847,208 @@ static __global__ void __launch_bounds__(64) k_clearcounts(int ncol, int nsubcol
         c0 += !a; c1 += !h; c2 += !m; c3 += !l;
     }
     cnt[4 * col] = c0; cnt[4 * col + 1] = c1; cnt[4 * col + 2] = c2; cnt[4 * col + 3] = c3;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The heartbeat McICA cloud fractions of the Solar GridComp, CLD??SWHB (GEOS_SolarGridComp.F90:7060-7223, SOLAR_RADVAL): every model
+// step, on every column with cloud fraction, the generator inputs from the imports (:7133-7161), generate_stochastic_clouds with the
+// 112 g-points of RRTMG_SW as sub-columns and seed_order = [4,3,2,1] in the MODEL's vertical ordering (TOA first, :7125-7131),
+// clearCounts_threeBand, and 1 - count / 112.  Only the four counts of a column leave the generator, so no mask and no water path
+// is materialised (k_mcica_sa is bound by exactly those writes); the generator's bound here is its integer arithmetic.
+//   k_swhb_prep   : lane = column, one walk from the bottom carrying zmid: the two overlap correlation planes (as k_overlap forms them
+//                   from zmid: the ACCUMULATED heights are differenced, not the increment reused - the two round differently), the
+//                   column's first and last layer with cloud fraction, its counts zeroed
+//   k_swhb_count  : thread = (column, <= MC_S sub-columns) on k_mcica's grid and MODE 1's plan, one walk down the layers with all its
+//                   streams; per sub-column four "seen a cloudy cell" bits; integer atomics into the column's four counts (any order of
+//                   integer adds gives the same counts)
+//   k_swhb_export : lane = column, counts -> the requested exports; columns without cloud fraction get 0 (:7077-7080)
+// play, ciwp and clwp have no planes: one rounded operation each from PLE, QI, QL where the walk needs them.  The statements are the
+// reference's, operation by operation, in R.
+// ---------------------------------------------------------------------------------------------------
+constexpr int HB_NSUB = 112;      // ngptsw
+// cloudy columns compacted to the front with k_partition before the count, so that no wave carries idle lanes for its cloud-free columns
+constexpr bool SWHB_COMPACT = true;
+template <typename R> struct HbArgs {
+    int ncol, ld, lm, doy, lcldmh, lcldlm;      // ncol columns (of this chunk) of fields whose leading dimension is ld
+    R grav, rgas, cwp_tiny;
+    const R *fcld, *ple, *t, *qi, *ql, *lats;   // GEOS layout: (ld,LM), PLE (ld,0:LM) in Pa, LATS (ld) in radians
+    R *alpha, *rcorr;                           // [lm][ncol], by column
+    uint16_t *cf0, *cf1;                        // [ncol] first / last layer with cloud fraction, 1-based; 0: the column has none
+    uint8_t *cloudy;                            // [ncol] k_partition's flag
+    const int32_t *perm, *nclear;               // k_partition's compaction (null: identity, all columns)
+    int32_t *cnt;                               // [4][ncol] clear counts: whole column, high, middle, low
+    R *out[4];                                  // CLDTT, CLDHI, CLDMD, CLDLO (ncol); null = not associated
+};
+
+// maximum of v (0 <= v < 2^16) over the wave's active lanes, bit by bit (ballots only see active lanes)
+GR_DEV int wave_max16(int v)
+{
+    int m = 0;
+#pragma unroll
+    for (int b = 15; b >= 0; b--)
+        if (__ballot(v >= (m | (1 << b))) != 0) m |= 1 << b;
+    return m;
+}
+
+template <typename R> __global__ void __launch_bounds__(256) k_swhb_prep(HbArgs<R> H, const LwDev<R> *__restrict__ T)
+{
+#pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
+    const int col = blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= H.ncol) return;
+    const int n = H.ncol, ld = H.ld, lm = H.lm;
+    const R *__restrict__ ple = H.ple, *__restrict__ tt = H.t, *__restrict__ fc = H.fcld;
+    const bool inhomo = T->xcw != nullptr;
+    const R lat = H.lats[col];
+    const R adl = corr_length<R>(T->aam, H.doy, lat);
+    const R rdl = inhomo ? corr_length<R>(T->ram, H.doy, lat) : (R)1;
+    const R c102 = (R)1.02 * (R)100;
+    // layer k + 1 of the pair (k, k + 1) the loop is at, starting with the lowest layer: zmid(LM) = 0 (:7154)
+    R pu = ple[(size_t)(lm - 1) * ld + col];
+    const R pb = ple[(size_t)lm * ld + col];
+    R plm1 = (R)0.5 * (pu + pb), fa1 = c102 * (pb - pu), t1 = tt[(size_t)(lm - 1) * ld + col], z1 = 0;
+    int first = 0, last = 0;
+    if (fc[(size_t)(lm - 1) * ld + col] > 0) first = last = lm;
+    for (int k = lm - 2; k >= 0; k--) {
+        const size_t a = (size_t)k * ld + col;
+        const R pk1 = pu;                       // PLE(k+1): the interface between the two layers
+        pu = ple[a];
+        const R plm0 = (R)0.5 * (pu + pk1);                                   // plmid (:7133)
+        const R fa0 = c102 * (pk1 - pu);                                      // cfac (:7138)
+        const R t0 = tt[a];
+        const R tlev = (t0 * fa1 + t1 * fa0) / (fa1 + fa0);                   // (:7147)
+        const R z0 = z1 + (((H.rgas * tlev) / H.grav) * (plm1 - plm0)) / pk1; // zmid (:7159)
+        const R dz = fabs(z1 - z0);                                           // k_overlap (cloud_subcol_gen.F90:310-321)
+        const size_t w = (size_t)(k + 1) * n + col;
+        H.alpha[w] = gr_exp<R>(-dz / adl);
+        if (inhomo) H.rcorr[w] = gr_exp<R>(-dz / rdl);
+        if (fc[a] > 0) { first = k + 1; if (!last) last = k + 1; }
+        plm1 = plm0; fa1 = fa0; t1 = t0; z1 = z0;
+    }
+    H.alpha[col] = 0;
+    if (inhomo) H.rcorr[col] = 0;
+    H.cf0[col] = (uint16_t)first; H.cf1[col] = (uint16_t)last;
+    H.cloudy[col] = last != 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) H.cnt[(size_t)q * n + col] = 0;
+}
+
+template <typename R>
+__global__ void __launch_bounds__(64) k_swhb_count(HbArgs<R> H, McPlan P, const LwDev<R> *__restrict__ Tp)
+{
+#pragma clang fp contract(off)
+    int bstart, bseg;
+    if (!band_block(H.ncol, P.nseg, bstart, bseg)) return;
+    const int col = bstart + threadIdx.x;
+    if (col >= H.ncol) return;
+    if (H.nclear && col < *H.nclear) return;
+    const int pc = H.perm ? H.perm[col] : col;
+    const int last = H.cf1[pc];
+    if (last == 0) return;                      // no cloud fraction: nothing is drawn; a wave of such lanes is gone here
+    const int n = H.ncol, ld = H.ld, lm = H.lm;
+    // The walk ends below the wave's lowest layer with cloud fraction: the layers under it are clear whatever is drawn.  It starts at
+    // layer 1 all the same: `cdf1(k) = cdf1(k-1)` where cdf2(k) < alpha(k), and the condensate chain likewise, carry the draws of
+    // the leading cloud-free layers down.  Those layers are drawn and chained; their cloud fraction is not read.
+    const int lend = wave_max16(last);
+    const int lfirst = lm + 1 - wave_max16(lm + 1 - (int)H.cf0[pc]);
+    const LwDev<R> &T = *Tp;
+    const McSegDev &SG = P.seg[bseg];
+    const int s0 = SG.start, ns = SG.count;     // uniform over the block
+    const bool inhomo = T.xcw != nullptr;
+    const R *__restrict__ ple = H.ple;
+
+    // seeds: play = plmid / 100 (:7134) of the four lowest layers, LM first (TOA is at layer 1: surface_at_one is false)
+    R pl4[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const size_t a = (size_t)(lm - 1 - k) * ld + pc;
+        pl4[k] = ((R)0.5 * (ple[a] + ple[a + ld])) / (R)100.;
+    }
+    const int so[4] = {4, 3, 2, 1};             // seed_order (:7179)
+    // stream positions of the segment's sub-columns as in k_mcica: k1 = presence pass, k2 = condensate pass
+    Kiss k1[MC_S], k2[MC_S];
+    k1[0] = kiss_seed<R>(pl4, so);
+    if (s0 > 0) kiss_jump(k1[0], SG.j);
+#pragma unroll
+    for (int s = 1; s < MC_S; s++) { k1[s] = k1[s - 1]; if (s < ns) kiss_jump(k1[s], P.jsub); }
+#pragma unroll
+    for (int s = 0; s < MC_S; s++) { k2[s] = k1[s]; if (inhomo && s < ns) kiss_jump(k2[s], P.jhalf); }
+
+    R cprev[MC_S], c3prev[MC_S];
+#pragma unroll
+    for (int s = 0; s < MC_S; s++) { cprev[s] = 0; c3prev[s] = 0; }
+    uint32_t any_all = 0, any_hi = 0, any_mid = 0, any_lo = 0;      // bit s: sub-column s has a cloudy cell (in the super-layer)
+    const R c102 = (R)1.02 * (R)100;
+    // clearCounts_threeBand's "TOA at level 1" branch (cloud_subcol_gen.F90:625-632), 0-based: high il < hi_end, middle il < mid_end
+    const int hi_end = H.lcldmh - 1, mid_end = H.lcldlm - 1;
+    // the next layer's inputs are requested a layer ahead: the layer's own integer work covers their latency
+    R al_n = 0, rc_n = 0, cf_n = lfirst <= 1 ? H.fcld[pc] : (R)0;
+    for (int il = 0; il < lend; il++) {
+        const R al = al_n, rc = rc_n, cf = cf_n;
+        if (il + 1 < lend) {
+            const size_t w = (size_t)(il + 1) * n + pc;
+            al_n = H.alpha[w];
+            if (inhomo) rc_n = H.rcorr[w];
+            cf_n = il + 2 >= lfirst ? H.fcld[(size_t)(il + 1) * ld + pc] : (R)0;
+        }
+        const R thr = (R)1. - cf;
+        const R sigma = cf > (R)0.99 ? (R)0.5 : (cf > (R)0.9 ? (R)0.71 : (R)1.0);
+        bool cldy[MC_S];
+        bool anyc = false;
+#pragma unroll
+        for (int s = 0; s < MC_S; s++) {
+            cldy[s] = false;
+            if (s >= ns) continue;
+            // cloud presence with exponential overlap (cloud_subcol_gen.F90:406-414)
+            R cdf1 = kiss_next<R>(k1[s]);
+            const R cdf2 = kiss_next<R>(k1[s]);
+            if (il > 0 && cdf2 < al) cdf1 = cprev[s];
+            cprev[s] = cdf1;
+            cldy[s] = cdf1 >= thr;
+            anyc = anyc || cldy[s];
+            if (inhomo) {
+                // condensate with exponential overlap (:416-466); the stream is consumed for every layer
+                const R c2 = kiss_next<R>(k2[s]);
+                R cdf3 = kiss_next<R>(k2[s]);
+                if (il > 0 && c2 < rc) cdf3 = c3prev[s];
+                c3prev[s] = cdf3;
+            }
+        }
+        if (__ballot(anyc) == 0) continue;
+        // some sub-column of the wave is cloudy here: the layer's water paths (:7138-7140) and the condensate scaling factors of all
+        // the segment's sub-columns together.  A cell whose scaled water paths are both <= cwp_tiny is reset to clear (:468-480), so
+        // the factor decides cells with tiny condensate.
+        const size_t a = (size_t)il * ld + pc;
+        const R cfac = c102 * (ple[a + ld] - ple[a]);
+        const R ciw = cfac * H.qi[a], clw = cfac * H.ql[a];
+        R zcws[MC_S];
+#pragma unroll
+        for (int s = 0; s < MC_S; s++) zcws[s] = (inhomo && s < ns) ? zcw_lookup<R>(T.xcw, c3prev[s], sigma) : (R)1;
+        uint32_t m = 0;
+#pragma unroll
+        for (int s = 0; s < MC_S; s++) {
+            if (!cldy[s]) continue;
+            const R ci = inhomo ? ciw * zcws[s] : ciw, cl = inhomo ? clw * zcws[s] : clw;
+            if (!(ci <= H.cwp_tiny && cl <= H.cwp_tiny)) m |= 1u << s;
+        }
+        any_all |= m;
+        if (il < hi_end) any_hi |= m; else if (il < mid_end) any_mid |= m; else any_lo |= m;
+    }
+    const uint32_t act = (1u << ns) - 1u;
+    atomicAdd(&H.cnt[(size_t)0 * n + pc], __popc(~any_all & act));
+    atomicAdd(&H.cnt[(size_t)1 * n + pc], __popc(~any_hi & act));
+    atomicAdd(&H.cnt[(size_t)2 * n + pc], __popc(~any_mid & act));
+    atomicAdd(&H.cnt[(size_t)3 * n + pc], __popc(~any_lo & act));
+}
+
+template <typename R> __global__ void __launch_bounds__(256) k_swhb_export(HbArgs<R> H)
+{
+#pragma clang fp contract(off)
+    const int col = blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= H.ncol) return;
+    const bool cloudy = H.cf1[col] != 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++)      // 1. - clearCounts(q,n)/float(ngptsw) (:7187-7206)
+        if (H.out[q]) H.out[q][col] = cloudy ? (R)1. - (R)H.cnt[(size_t)q * H.ncol + col] / (R)HB_NSUB : (R)0;
 }
 
 }  // namespace geosrad

@@ -8,7 +8,7 @@ module geosrad_gridcomp
    use geosrad_c, only : geosrad_ctx_handle, geosrad_fail, geosrad_data_path, geosrad_load_tables_chou_sw, geosrad_load_tables_chou_lw
    implicit none
    private
-   public :: lw_driver_rrtmg, lw_driver_rrtmg_rats, lw_update_rats, lw_update_bands, sw_update_surface, sw_update_clouds, sw_driver_rrtmg, sw_driver_chou, lw_driver_chou, lw_chou_post, lw_update_flx, sw_update_export, rad_tendencies
+   public :: lw_driver_rrtmg, lw_driver_rrtmg_rats, lw_update_rats, lw_update_bands, sw_update_surface, sw_update_clouds, sw_update_cldhb, sw_driver_rrtmg, sw_driver_chou, lw_driver_chou, lw_chou_post, lw_update_flx, sw_update_export, rad_tendencies
    public :: lit_index, lit_pack, lit_unpack
    public :: dev_alloc, dev_free, dev_put, dev_get, dev_sync
 
@@ -35,6 +35,10 @@ module geosrad_gridcomp
       SWK_CLDHI = 8, SWK_CLDTT = 9, SWK_COTDENLO = 10, SWK_COTDENMD = 11, SWK_COTDENHI = 12, SWK_COTDENTT = 13, SWK_TAULO = 14, SWK_TAUMD = 15, &
       SWK_TAUHI = 16, SWK_TAUTT = 17, SWK_TAUTX = 18, SWK_COTLO = 19, SWK_COTMD = 20, SWK_COTHI = 21, SWK_COTTT = 22, SWK_COTNUMLO = 23, &
       SWK_COTNUMMD = 24, SWK_COTNUMHI = 25, SWK_COTNUMTT = 26, SWK_CLDTMP = 27, SWK_CLDPRS = 28, SWK_NOUT = 28
+   ! ---- GEOSRAD_SWHB_* (heartbeat McICA cloud fractions of UPDATE_EXPORT) ----
+   integer, parameter, public :: SWHB_FCLD = 1, SWHB_PLE = 2, SWHB_T = 3, SWHB_QI = 4, SWHB_QL = 5, SWHB_LATS = 6, SWHB_NIN = 6
+   integer, parameter, public :: SWHB_C_GRAV = 1, SWHB_C_RGAS = 2, SWHB_NCONST = 2
+   integer, parameter, public :: SWHB_CLDTT = 1, SWHB_CLDHI = 2, SWHB_CLDMD = 3, SWHB_CLDLO = 4, SWHB_NOUT = 4
    ! ---- GEOSRAD_LWR_* (RATS exports of Update_Flx) ----
    integer, parameter, public :: LWR_FLX_INT = 1, LWR_SFCEM_INT = 2, LWR_DFDTS = 3, LWR_FLX_RAT = 4, LWR_SFCEM_RAT = 5, LWR_DFDTS_RAT = 6, LWR_NIN = 6
    integer, parameter, public :: LWR_DOLR = 1, LWR_DLWS = 2, LWR_DFLNS = 3, LWR_DSFCEM = 4, LWR_NETTRAP = 5, LWR_COLTRAP = 6, LWR_FLX = 7, &
@@ -141,6 +145,14 @@ module geosrad_gridcomp
          type(c_ptr), value :: ctx, stream
          integer(c_int), value :: ncol, lm, lcldmh, lcldlm
          real(c_double), value :: taucrit
+         real(c_double), intent(in) :: consts(*)
+         type(c_ptr), intent(in) :: fin(*), fout(*)
+      end function
+      integer(c_int) function geosrad_sw_update_cldhb_dev(ctx, stream, ncol, lm, lcldmh, lcldlm, doy, consts, fin, fout) &
+            bind(C, name='geosrad_sw_update_cldhb_dev')
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: ctx, stream
+         integer(c_int), value :: ncol, lm, lcldmh, lcldlm, doy
          real(c_double), intent(in) :: consts(*)
          type(c_ptr), intent(in) :: fin(*), fout(*)
       end function
@@ -364,6 +376,20 @@ contains
       consts(SWK_C_GRAV) = real(grav, c_double); consts(SWK_C_UNDEF) = real(undef, c_double)
       if (geosrad_sw_update_clouds_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(lm,c_int), int(lcldmh,c_int), &
             int(lcldlm,c_int), real(taucrit,c_double), consts, fin, fout) /= 0) call geosrad_fail('UPDATE_EXPORT (clouds)')
+   end subroutine
+
+   ! heartbeat McICA cloud fractions of UPDATE_EXPORT (GEOS_SolarGridComp.F90:7060-7223, SOLAR_RADVAL): CLDTTSWHB, CLDHISWHB, CLDMDSWHB,
+   ! CLDLOSWHB on all columns from FCLD, PLE, T, QI, QL and LATS; doy = the day of the year the generator's correlation lengths take.
+   ! The condensate inhomogeneity and correlation lengths are those of set_inhomogeneity / initialize_cloud_subcol_gen.
+   ! MAPL_GRAV = 9.80665, MAPL_RGAS = MAPL_RUNIV / MAPL_AIRMW = 8314.47 / 28.965 (MAPL_Constants).
+   subroutine sw_update_cldhb(ncol, lm, lcldmh, lcldlm, doy, fin, fout)
+      integer, intent(in) :: ncol, lm, lcldmh, lcldlm, doy
+      type(c_ptr), intent(in) :: fin(SWHB_NIN), fout(SWHB_NOUT)
+      real, parameter :: grav = 9.80665, rgas = 8314.47 / 28.965
+      real(c_double) :: consts(SWHB_NCONST)
+      consts(SWHB_C_GRAV) = real(grav, c_double); consts(SWHB_C_RGAS) = real(rgas, c_double)
+      if (geosrad_sw_update_cldhb_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(lm,c_int), int(lcldmh,c_int), &
+            int(lcldlm,c_int), int(doy,c_int), consts, fin, fout) /= 0) call geosrad_fail('UPDATE_EXPORT (CLD??SWHB)')
    end subroutine
 
    ! RRTMG branch of SORADCORE (GEOS_SolarGridComp.F90:6113-6450) on the packed daytime columns

@@ -71,6 +71,11 @@ SWK_OUT_2D = ["CLDLO", "CLDMD", "CLDHI", "CLDTT", "COTDENLO", "COTDENMD", "COTDE
               "COTLO", "COTMD", "COTHI", "COTTT", "COTNUMLO", "COTNUMMD", "COTNUMHI", "COTNUMTT", "CLDTMP", "CLDPRS"]
 SWK_OUT = SWK_OUT_3D + SWK_OUT_2D
 
+# heartbeat McICA cloud fractions of UPDATE_EXPORT, CLD??SWHB (SOL:7060-7223), GEOSRAD_SWHB_*
+SWHB_IN = ["FCLD", "PLE", "T", "QI", "QL", "LATS"]
+SWHB_CONST = ["GRAV", "RGAS"]
+SWHB_OUT = ["CLDTT", "CLDHI", "CLDMD", "CLDLO"]
+
 # MAPL_Constants (not in the reference repository): defaults only
 MAPL = {"AIRMW": 28.965, "H2OMW": 18.015, "O3MW": 47.9982, "RUNIV": 8314.47, "GRAV": 9.80665, "CP": 1004.6830, "UNDEF": 1.0e15}
 MAPL["RGAS"] = MAPL["RUNIV"] / MAPL["AIRMW"]
@@ -96,6 +101,12 @@ def swk_consts(**over):
     d = dict(GRAV=MAPL["GRAV"], UNDEF=MAPL["UNDEF"])
     d.update(over)
     return [float(d[k]) for k in SWK_CONST]
+
+
+def swhb_consts(**over):
+    d = dict(GRAV=MAPL["GRAV"], RGAS=MAPL["RGAS"])
+    d.update(over)
+    return [float(d[k]) for k in SWHB_CONST]
 
 
 def lwd_consts(**over):

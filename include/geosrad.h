@@ -586,6 +586,26 @@ enum { GEOSRAD_SWK_FCLD_X /*(ncol,LM)*/, GEOSRAD_SWK_TAUCLI, GEOSRAD_SWK_TAUCLW,
 int geosrad_sw_update_clouds_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm, int lcldmh, int lcldlm, double taucrit,
                                  const double *consts /*GRAV, UNDEF*/, const void *const *in, void *const *out);
 
+/* geosrad_sw_update_cldhb_dev: the heartbeat McICA cloud fractions CLD??SWHB of UPDATE_EXPORT (GEOS_SolarGridComp.F90:7060-7223, inside
+ * #ifdef SOLAR_RADVAL), every model step over all columns.  For every column with any FCLD > 0: the generator inputs from the imports
+ * (:7133-7161: plmid = 0.5 (PLE(k-1) + PLE(k)), play = plmid / 100, cfac = 1.02 * 100 * (PLE(k) - PLE(k-1)), ciwp / clwp = cfac QI / QL,
+ * interior interface temperatures weighted by cfac, zmid from the hydrostatic equation with zmid(LM) = 0), generate_stochastic_clouds
+ * with the 112 g-points of RRTMG_SW as sub-columns, cwp_tiny = 1e-20 and seed_order = [4,3,2,1] in the MODEL's vertical ordering (TOA at
+ * layer 1: the levels are not reversed, :7125-7131), clearCounts_threeBand(cloudLM = lcldlm, cloudMH = lcldmh) (high = layers
+ * 1..lcldmh-1, middle = lcldmh..lcldlm-1, low = lcldlm..LM) and CLD?? = 1 - count / 112 (:7187-7206); columns without cloud fraction
+ * get 0 (:7077-7080).  No sub-column array is materialised.  The context's condensate inhomogeneity (geosrad_set_inhomogeneity) and
+ * correlation lengths (geosrad_set_corr_lengths) apply, as in geosrad_mcica_dev; no solver tables are needed.  Fields (ncol,LM), PLE
+ * (ncol,0:LM) in Pa, LATS (ncol) in radians, the exports (ncol).  consts NULL: MAPL_GRAV = 9.80665, MAPL_RGAS = 8314.47 / 28.965.
+ * A NULL output is "not associated" and left untouched; with all four NULL nothing is launched and the call returns GEOSRAD_OK.
+ * GEOSRAD_EINVAL, nothing launched: an input is NULL while an output is requested, ncol < 1, lm < 4 (the seeds need four layers), or
+ * not 1 < lcldmh < lcldlm <= lm (SOL:3036-3062). */
+enum { GEOSRAD_SWHB_FCLD /*(ncol,LM)*/, GEOSRAD_SWHB_PLE /*(ncol,0:LM) Pa*/, GEOSRAD_SWHB_T, GEOSRAD_SWHB_QI, GEOSRAD_SWHB_QL,
+       GEOSRAD_SWHB_LATS /*(ncol) radians*/, GEOSRAD_SWHB_NIN };
+enum { GEOSRAD_SWHB_C_GRAV, GEOSRAD_SWHB_C_RGAS, GEOSRAD_SWHB_NCONST };
+enum { GEOSRAD_SWHB_CLDTT /*(ncol)*/, GEOSRAD_SWHB_CLDHI, GEOSRAD_SWHB_CLDMD, GEOSRAD_SWHB_CLDLO, GEOSRAD_SWHB_NOUT };
+int geosrad_sw_update_cldhb_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm, int lcldmh, int lcldlm, int doy,
+                                const double *consts /*GRAV, RGAS; NULL: MAPL's values*/, const void *const *in, void *const *out);
+
 /* geosrad_rad_tendencies_dev: the parent's heating rates (GEOS_RadiationGridComp.F90:798-819). */
 enum { GEOSRAD_RT_PLE, GEOSRAD_RT_FLW, GEOSRAD_RT_FSW, GEOSRAD_RT_FLWCLR, GEOSRAD_RT_FSWCLR, GEOSRAD_RT_FSWNA, GEOSRAD_RT_FLA,
        GEOSRAD_RT_FSCNA, GEOSRAD_RT_DSFDTS, GEOSRAD_RT_SFCEM, GEOSRAD_RT_TRD, GEOSRAD_RT_NIN };
