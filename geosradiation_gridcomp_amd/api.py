@@ -90,7 +90,9 @@ class Context:
     def _chk(self, rc):
         if rc:
             msg = self.L.geosrad_last_error(self.h).decode()
-            raise (GeosradInputError if rc == 5 else GeosradError)(msg)
+            err = (GeosradInputError if rc == 5 else GeosradError)(msg)
+            err.rc = rc                     # the GEOSRAD_E* code of include/geosrad.h
+            raise err
 
     def _kind(self):
         return "r4" if self.real_kind == 4 else "r8"
@@ -531,6 +533,47 @@ class Context:
         self._chk(self.L.geosrad_sw_driver_chou_dev(self.h, ctypes.c_void_p(stream), ci(ncol), ci(lm), self._ptr_array(G.SWC_IN, ptr), cs,
                                                     ci(int(lcldmh)), ci(int(lcldlm)), _p(hu), _p(hi), ci(1 if do_drfband else 0),
                                                     self._ptr_array(G.SWC_OUT, ptr)))
+
+    @staticmethod
+    def _lit_args(names, lit_index, lit_pos, dark, keep):
+        """lit_index / lit_pos: device addresses (None / 0 = NULL); dark: name -> UnPackIt's DEFAULT of that output (missing = 0.0), or None
+        = NULL; keep: names of the outputs whose dark columns keep their values"""
+        dk = None if dark is None else (ctypes.c_double * len(names))(*[float(dark.get(k, 0.0)) for k in names])
+        mask = 0
+        for k in keep:
+            mask |= 1 << names.index(k)
+        return ctypes.c_void_p(lit_index or None), ctypes.c_void_p(lit_pos or None), dk, ctypes.c_uint64(mask)
+
+    def sw_driver_rrtmg_lit_dev(self, stream, ncol, nlit, lit_index, lit_pos, lm, nb_aer, ptr, consts, iceflg, liqflg, sc, dist, isolvar,
+                                dyofyr, include_aerosols, lcldlm, lcldmh, normflx=1, bndsolvar=None, indsolvar=None, dark=None, keep=()):
+        """sw_driver_rrtmg_dev on the un-packed tile of ncol columns, nlit of them lit (GEOS_SolarGridComp.F90:3686, PackIt :3839-3894,
+        UnPackIt :6520-6580): `ptr` holds tile-wide fields, lit_index / lit_pos / nlit are what lit_index_dev gave; dark / keep as in
+        _lit_args, by gridcomp.SWD_OUT name.  TAUA / SSAA / ASYA are only read."""
+        from . import gridcomp as G
+        ci = ctypes.c_int
+        cs = (ctypes.c_double * len(G.SWD_CONST))(*consts)
+        bs = None if bndsolvar is None else np.ascontiguousarray(bndsolvar, dtype=self.dtype)
+        ins = None if indsolvar is None else np.ascontiguousarray(indsolvar, dtype=self.dtype)
+        li, lp, dk, mask = self._lit_args(G.SWD_OUT, lit_index, lit_pos, dark, keep)
+        self._chk(self.L.geosrad_sw_driver_rrtmg_lit_dev(
+            self.h, ctypes.c_void_p(stream), ci(ncol), ci(nlit), li, lp, ci(lm), ci(nb_aer), self._ptr_array(G.SWD_IN, ptr), cs, ci(iceflg),
+            ci(liqflg), ctypes.c_double(sc), ctypes.c_double(dist), ci(isolvar), ci(int(dyofyr)), ci(1 if include_aerosols else 0),
+            ci(int(lcldlm)), ci(int(lcldmh)), ci(normflx), None if bs is None else _p(bs), None if ins is None else _p(ins), dk, mask,
+            self._ptr_array(G.SWD_OUT, ptr)))
+
+    def sw_driver_chou_lit_dev(self, stream, ncol, nlit, lit_index, lit_pos, lm, ptr, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband=False,
+                               dark=None, keep=()):
+        """sw_driver_chou_dev on the un-packed tile of ncol columns, nlit of them lit: see sw_driver_rrtmg_lit_dev; dark / keep by
+        gridcomp.SWC_OUT name."""
+        from . import gridcomp as G
+        ci = ctypes.c_int
+        cs = (ctypes.c_double * len(G.SWC_CONST))(*consts)
+        hu = None if hk_uv is None else np.ascontiguousarray(hk_uv, dtype=self.dtype)
+        hi = None if hk_ir is None else np.ascontiguousarray(hk_ir, dtype=self.dtype)
+        li, lp, dk, mask = self._lit_args(G.SWC_OUT, lit_index, lit_pos, dark, keep)
+        self._chk(self.L.geosrad_sw_driver_chou_lit_dev(self.h, ctypes.c_void_p(stream), ci(ncol), ci(nlit), li, lp, ci(lm),
+                                                        self._ptr_array(G.SWC_IN, ptr), cs, ci(int(lcldmh)), ci(int(lcldlm)), _p(hu), _p(hi),
+                                                        ci(1 if do_drfband else 0), dk, mask, self._ptr_array(G.SWC_OUT, ptr)))
 
     def lw_driver_chou_dev(self, stream, ncol, lm, ptr, consts, trace, lcldmh, lcldlm, binary_clouds=False):
         """Chou-Suarez branch of LW_Driver in one call (GEOS_IrradGridComp.F90:1781-1785, :1876-1912, :2093-2108, :3604-3663): `ptr` holds

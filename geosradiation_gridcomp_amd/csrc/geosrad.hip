@@ -319,6 +319,15 @@ static int default_host_threads()
     return (int)(n < 1 ? 1 : (n > 8 ? 8 : n));
 }
 
+// the un-packed tile of the lit-aware SW drivers (geosrad_sw_driver_*_lit_dev): its columns, geosrad_lit_index_dev's two index arrays
+// (device), UnPackIt's DEFAULT of every output (host) and the outputs whose dark columns keep their values
+struct LitTile {
+    int tile;
+    const int32_t *idx, *pos;
+    const double *dark;
+    uint64_t keep;
+};
+
 // ---------------------------------------------------------------------------------------------------
 struct geosrad_ctx {
     int device = 0, real_kind = 4, chunk = 131072;
@@ -593,14 +602,16 @@ struct geosrad_ctx {
     virtual int lw_driver_dev(hipStream_t st, int ncol, int lm, int nb, const void *const *in, const double *consts, int iceflg,
                               int liqflg, int doy, int lcldlm, int lcldmh, const int32_t *band_output, void *const *out, int nrats,
                               const int32_t *rat_gas, void *const *rat_out) = 0;
+    // lit != nullptr (both SW drivers): `in` / `out` are the un-packed tile's and ncol is NumLit (geosrad_sw_driver_*_lit_dev)
     virtual int sw_driver_dev(hipStream_t st, int ncol, int lm, int nb, const void *const *in, const double *consts, int iceflg,
                               int liqflg, double sc, double dist, int isolvar, int dyofyr, int include_aerosols, int lcldlm,
-                              int lcldmh, int normflx, const void *bndsolvar, const void *indsolvar, void *const *out) = 0;
+                              int lcldmh, int normflx, const void *bndsolvar, const void *indsolvar, void *const *out,
+                              const LitTile *lit) = 0;
     virtual int lw_chou_post_dev(hipStream_t st, int ncol, int lm, const void *const *in, void *const *out) = 0;
     virtual int lw_driver_chou_dev(hipStream_t st, int ncol, int lm, const void *const *in, const double *consts, int trace, int lcldmh,
                                    int lcldlm, int binary_clouds, void *const *out) = 0;
     virtual int sw_driver_chou_dev(hipStream_t st, int ncol, int lm, const void *const *in, const double *consts, int lcldmh, int lcldlm,
-                                   const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out) = 0;
+                                   const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out, const LitTile *lit) = 0;
     virtual int lw_update_flx_dev(hipStream_t st, int ncol, int lm, int rrtmg, int lev_mid_high, int lev_low_mid, double undef,
                                   const void *const *in, void *const *out) = 0;
     virtual int lw_update_rats_dev(hipStream_t st, int ncol, int lm, int nrats, const void *const *in, void *const *out) = 0;
@@ -1221,6 +1232,36 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 
+    // the lit-aware SW drivers: the arguments that describe the tile
+    int lit_check(const LitTile &t, int nlit, void *const *out, int nout)
+    {
+        if (nlit < 0 || nlit > t.tile) return fail(GEOSRAD_EINVAL, "nlit must lie in 0 .. ncol");
+        if (nlit > 0 && (!t.idx || !t.pos)) return fail(GEOSRAD_EINVAL, "lit_index / lit_pos null");
+        bool fill = false;
+        for (int k = 0; k < nout; k++) fill = fill || (out[k] && !(t.keep >> k & 1));
+        if (fill && (!t.pos || !t.dark)) return fail(GEOSRAD_EINVAL, "an output whose keep bit is clear needs lit_pos and dark");
+        return GEOSRAD_OK;
+    }
+    // one k_lit_scatter over the listed outputs the caller requested: output k from its packed plane of `rows` rows (nullptr with nlit == 0)
+    struct LitField { int k; const R *src; int rows; };
+    using LitFields = std::vector<LitField>;
+    int lit_scatter(hipStream_t st, const LitTile &t, int nlit, void *const *out, const LitFields &fields)
+    {
+        LitScatter<R> S{};
+        S.tile = t.tile; S.nlit = nlit; S.pos = t.pos;
+        for (const LitField &f : fields) {
+            const int keep = (int)(t.keep >> f.k & 1);
+            if (!out[f.k] || (nlit == 0 && keep)) continue;
+            if (S.nf == LIT_NFIELD) return fail(GEOSRAD_EINVAL, "lit_scatter: too many fields");
+            S.f[S.nf].src = f.src; S.f[S.nf].dst = (R *)out[f.k]; S.f[S.nf].row0 = S.rows; S.f[S.nf].keep = keep;
+            S.f[S.nf].dark = t.dark ? (R)t.dark[f.k] : (R)0;
+            S.nf++; S.rows += f.rows;
+        }
+        if (S.nf) hipLaunchKernelGGL((k_lit_scatter<R>), dim3(grid256(t.tile), S.rows), dim3(256), 0, st, S);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+
     int lw_driver_dev(hipStream_t st, int ncol, int lm, int nb, const void *const *in, const double *consts, int iceflg, int liqflg,
                       int doy, int lcldlm, int lcldmh, const int32_t *band_output, void *const *out, int nrats, const int32_t *rat_gas,
                       void *const *rat_out) override
@@ -1312,10 +1353,11 @@ template <typename R> struct Ctx : geosrad_ctx {
 
     int sw_driver_dev(hipStream_t st, int ncol, int lm, int nb, const void *const *in, const double *consts, int iceflg, int liqflg,
                       double sc, double dist, int isolvar, int dyofyr, int include_aerosols, int lcldlm, int lcldmh, int normflx,
-                      const void *bndsolvar, const void *indsolvar, void *const *out) override
+                      const void *bndsolvar, const void *indsolvar, void *const *out, const LitTile *lit) override
     {
         HIPCHK(hipSetDevice(device));
-        if (ncol <= 0 || lm < 4 || nb < 0 || nb > 14) return fail(GEOSRAD_EINVAL, "bad ncol/lm/nb_aer");
+        if ((lit ? lit->tile : ncol) <= 0 || lm < 4 || nb < 0 || nb > 14) return fail(GEOSRAD_EINVAL, "bad ncol/lm/nb_aer");
+        if (lit) if (const int rc = lit_check(*lit, ncol, out, GEOSRAD_SWD_NOUT)) return rc;
         // SORADCORE asserts the solar-variability options it supports before the call (GEOS_SolarGridComp.F90:6286-6292): no isolvar 1
         if (isolvar == 1) return fail(GEOSRAD_EINPUT, "SORADCORE: ISOLVAR == 1 is not supported by the GridComp (the solver entry point rrtmg_sw accepts it)");
         for (int k = 0; k < GEOSRAD_SWD_NIN; k++)
@@ -1323,10 +1365,24 @@ template <typename R> struct Ctx : geosrad_ctx {
         const bool aer = in[GEOSRAD_SWD_TAUA] != nullptr;
         if (aer && (!in[GEOSRAD_SWD_SSAA] || !in[GEOSRAD_SWD_ASYA])) return fail(GEOSRAD_EINVAL, "TAUA, SSAA and ASYA go together");
         if (aer && nb != 14) return fail(GEOSRAD_EINVAL, "RRTMG_SW aerosol arrays have 14 bands");
+        auto rows = [lm](int k) {      // of output k
+            return k <= GEOSRAD_SWD_FSCU || (k >= GEOSRAD_SWD_FSWNA && k <= GEOSRAD_SWD_FSCUNA) ? lm + 1
+                   : (k == GEOSRAD_SWD_FSWBAND || k == GEOSRAD_SWD_FSWBANDNA ? 14 : 1);
+        };
+        if (lit) {      // what rrtmg_sw would reject, before anything is launched
+            if (const int rc = sw_check_options(1, lm, iceflg, liqflg, lm - lcldlm + 1, lm - lcldmh + 1, 10)) return rc;
+            SwSolar<R> SV;
+            if (const int rc = sw_solar(sc, dist, isolvar, (const R *)bndsolvar, (const R *)indsolvar, nullptr, SV)) return rc;
+        }
+        if (lit && ncol == 0) {        // no daytime column: the dark fill alone
+            LitFields F;
+            for (int k = 0; k < GEOSRAD_SWD_NOUT; k++) F.push_back({k, nullptr, rows(k)});
+            return lit_scatter(st, *lit, 0, out, F);
+        }
         const size_t n = (size_t)ncol, cl = n * lm, cv = n * (lm + 1);
         const bool want_na = out[GEOSRAD_SWD_FSWNA] || out[GEOSRAD_SWD_FSCNA] || out[GEOSRAD_SWD_FSWUNA] || out[GEOSRAD_SWD_FSCUNA] ||
                              out[GEOSRAD_SWD_FSWBANDNA];
-        R *lay[13], *lev[2], *aerp[3], *flux[4], *scal[6], *cot[8], *band, *nflux[4] = {}, *nsc[14] = {}, *nband = nullptr;
+        R *lay[13], *lev[2], *aerp[3], *flux[4], *scal[6], *cot[8], *band, *nflux[4] = {}, *nsc[14] = {}, *nband = nullptr, *col[6] = {};
         int32_t *cc;
         auto carve = [&](Carve c) {
             for (auto &q : lay) q = c.take<R>(cl);
@@ -1342,12 +1398,14 @@ template <typename R> struct Ctx : geosrad_ctx {
                 for (auto &q : nsc) q = c.take<R>(n);
                 nband = c.take<R>(n * 14);
             }
+            if (lit) for (auto &q : col) q = c.take<R>(n);      // the packed per-column imports the solver reads as they are
             return c.off;
         };
         if (const int rc = drv_reserve(1, carve(Carve()))) return rc;
         carve(Carve(d_ws_drvs[1]));
         auto I = [&](int k) { return (const R *)in[k]; };
-        SwdArgs<R> A{};
+        SwdLit<R> AL{};
+        SwdArgs<R> &A = AL;
         A.ncol = ncol; A.lm = lm; A.nb = 14; A.iceflg = iceflg; A.liqflg = liqflg;
         A.ple = I(GEOSRAD_SWD_PLE); A.pl = I(GEOSRAD_SWD_PL); A.t = I(GEOSRAD_SWD_T); A.q = I(GEOSRAD_SWD_Q); A.o3 = I(GEOSRAD_SWD_O3);
         A.ch4 = I(GEOSRAD_SWD_CH4); A.cl = I(GEOSRAD_SWD_CL); A.ts = I(GEOSRAD_SWD_TS); A.qq_ice = I(GEOSRAD_SWD_QQ_ICE);
@@ -1362,19 +1420,29 @@ template <typename R> struct Ctx : geosrad_ctx {
         A.zl = lay[12]; A.plev = lev[0]; A.tlev = lev[1]; A.tauaer = aerp[0]; A.ssaaer = aerp[1]; A.asmaer = aerp[2];
         const dim3 blk(256);
         const unsigned gx = grid256(ncol);
-        hipLaunchKernelGGL((k_swd_prep<R>), dim3(gx, lm), blk, 0, st, A);
+        // ZT ALAT ALBVR ALBVF ALBNR ALBNF: the caller's packed arrays, or the tile's gathered by the prep kernel
+        static const int col_ix[6] = {GEOSRAD_SWD_ZT, GEOSRAD_SWD_ALAT, GEOSRAD_SWD_ALBVR, GEOSRAD_SWD_ALBVF, GEOSRAD_SWD_ALBNR, GEOSRAD_SWD_ALBNF};
+        const void *cin[6];
+        for (int k = 0; k < 6; k++) cin[k] = lit ? col[k] : in[col_ix[k]];
+        if (lit) {
+            AL.tile = lit->tile; AL.lit = lit->idx;
+            for (int k = 0; k < 6; k++) { AL.col_in[k] = I(col_ix[k]); AL.col_out[k] = col[k]; }
+            hipLaunchKernelGGL((k_swd_prep<R, true>), dim3(gx, lm), blk, 0, st, AL);
+        } else hipLaunchKernelGGL((k_swd_prep<R>), dim3(gx, lm), blk, 0, st, A);
         hipLaunchKernelGGL((k_swd_zm<R>), dim3(gx), blk, 0, st, A);
         const void *sin[S_NIN];
         sin[S_PLAY] = A.play; sin[S_PLEV] = A.plev; sin[S_TLAY] = A.tlay; sin[S_H2O] = A.h2o; sin[S_O3] = A.o3_r; sin[S_CO2] = A.co2_r;
         sin[S_CH4] = A.ch4_r; sin[S_O2] = A.o2_r; sin[S_CLD] = A.cldf; sin[S_CIWP] = A.ciwp; sin[S_CLWP] = A.clwp; sin[S_REI] = A.rei;
-        sin[S_REL] = A.rel; sin[S_ZM] = A.zl; sin[S_ALAT] = in[GEOSRAD_SWD_ALAT]; sin[S_TAUAER] = A.tauaer; sin[S_SSAAER] = A.ssaaer;
-        sin[S_ASMAER] = A.asmaer; sin[S_COSZEN] = in[GEOSRAD_SWD_ZT]; sin[S_ASDIR] = in[GEOSRAD_SWD_ALBVR]; sin[S_ASDIF] = in[GEOSRAD_SWD_ALBVF];
-        sin[S_ALDIR] = in[GEOSRAD_SWD_ALBNR]; sin[S_ALDIF] = in[GEOSRAD_SWD_ALBNF];
+        sin[S_REL] = A.rel; sin[S_ZM] = A.zl; sin[S_ALAT] = cin[1]; sin[S_TAUAER] = A.tauaer; sin[S_SSAAER] = A.ssaaer;
+        sin[S_ASMAER] = A.asmaer; sin[S_COSZEN] = cin[0]; sin[S_ASDIR] = cin[2]; sin[S_ASDIF] = cin[3];
+        sin[S_ALDIR] = cin[4]; sin[S_ALDIF] = cin[5];
         void *sout[SO_NOUT] = {};
         for (int k = 0; k < 4; k++) sout[SO_UFLX + k] = flux[k];
         const int sc_ix[6] = {GEOSRAD_SWD_NIRR, GEOSRAD_SWD_NIRF, GEOSRAD_SWD_PARR, GEOSRAD_SWD_PARF, GEOSRAD_SWD_UVRR, GEOSRAD_SWD_UVRF};
-        for (int k = 0; k < 6; k++) sout[SO_NIRR + k] = out[sc_ix[k]] ? out[sc_ix[k]] : (void *)scal[k];
-        sout[SO_FSWBAND] = out[GEOSRAD_SWD_FSWBAND] ? out[GEOSRAD_SWD_FSWBAND] : (void *)band;
+        // what the solver writes as the driver returns it goes straight to the caller's packed arrays; a tile's takes the workspace planes
+        auto direct = [&](int k, R *plane) { return out[k] && !lit ? out[k] : (void *)plane; };
+        for (int k = 0; k < 6; k++) sout[SO_NIRR + k] = direct(sc_ix[k], scal[k]);
+        sout[SO_FSWBAND] = direct(GEOSRAD_SWD_FSWBAND, band);
         for (int k = 0; k < 8; k++) sout[SO_COT0 + k] = cot[k];      // cotd t/h/m/l then cotn t/h/m/l
         // IAER = 10 always (SOL:6235; without aerosols the arrays are zero); super-layer indices flipped in the call (SOL:6341)
         void *nout[SO_NOUT] = {};
@@ -1382,25 +1450,47 @@ template <typename R> struct Ctx : geosrad_ctx {
             for (int k = 0; k < 4; k++) nout[SO_UFLX + k] = nflux[k];
             for (int k = 0; k < 6; k++) nout[SO_NIRR + k] = nsc[k];
             for (int k = 0; k < 8; k++) nout[SO_COT0 + k] = nsc[6 + k];
-            nout[SO_FSWBAND] = out[GEOSRAD_SWD_FSWBANDNA] ? out[GEOSRAD_SWD_FSWBANDNA] : (void *)nband;
+            nout[SO_FSWBAND] = direct(GEOSRAD_SWD_FSWBANDNA, nband);
         }
         if (const int rc = sw_run(st, ncol, lm, sc, dist, isolvar, sin, iceflg, liqflg, dyofyr, 10, lm - lcldlm + 1, lm - lcldmh + 1,
                                   normflx, cc, sout, 0, bndsolvar, indsolvar, nullptr, nullptr, want_na ? nout : nullptr)) return rc;
-        SwdPost<R> Q{};
+        SwdPostLit<R> QL{};
+        SwdPost<R> &Q = QL;
         Q.ncol = ncol; Q.lm = lm; Q.ngpt = NG_SW; Q.aerosols = include_aerosols; Q.undef = (R)consts[GEOSRAD_SWD_C_UNDEF];
         Q.swuflx = flux[0]; Q.swdflx = flux[1]; Q.swuflxc = flux[2]; Q.swdflxc = flux[3]; Q.clearCounts = cc;
         for (int k = 0; k < 4; k++) { Q.cotd[k] = cot[k]; Q.cotn[k] = cot[4 + k]; Q.cot[k] = (R *)out[GEOSRAD_SWD_COTTP + k]; }
         Q.fsw = (R *)out[GEOSRAD_SWD_FSW]; Q.fsc = (R *)out[GEOSRAD_SWD_FSC]; Q.fswu = (R *)out[GEOSRAD_SWD_FSWU]; Q.fscu = (R *)out[GEOSRAD_SWD_FSCU];
         Q.cldts = (R *)out[GEOSRAD_SWD_CLDTS]; Q.cldhs = (R *)out[GEOSRAD_SWD_CLDHS]; Q.cldms = (R *)out[GEOSRAD_SWD_CLDMS];
         Q.cldls = (R *)out[GEOSRAD_SWD_CLDLS];
-        hipLaunchKernelGGL((k_swd_post<R>), dim3(gx, lm + 1), blk, 0, st, Q);
+        // k_swd_post_lit's dark values and keep bits, from the outputs its slots stand for (-1: none)
+        auto post_lit = [&](SwdPostLit<R> &P, std::initializer_list<int> ix) {
+            P.tile = lit->tile; P.pos = lit->pos; P.keep = 0;
+            int s = 0;
+            for (const int k : ix) {
+                if (k >= 0 && (lit->keep >> k & 1)) P.keep |= 1u << s;
+                P.dark[s++] = k >= 0 && lit->dark ? (R)lit->dark[k] : (R)0;
+            }
+            hipLaunchKernelGGL((k_swd_post_lit<R>), dim3(grid256(lit->tile), lm + 1), blk, 0, st, P);
+        };
+        if (lit) post_lit(QL, {GEOSRAD_SWD_FSW, GEOSRAD_SWD_FSC, GEOSRAD_SWD_FSWU, GEOSRAD_SWD_FSCU, GEOSRAD_SWD_CLDTS, GEOSRAD_SWD_CLDHS,
+                               GEOSRAD_SWD_CLDMS, GEOSRAD_SWD_CLDLS, GEOSRAD_SWD_COTTP, GEOSRAD_SWD_COTHP, GEOSRAD_SWD_COTMP, GEOSRAD_SWD_COTLP});
+        else hipLaunchKernelGGL((k_swd_post<R>), dim3(gx, lm + 1), blk, 0, st, Q);
         if (want_na) {      // un-flip of the no-aerosol fluxes (the FS*NAN internals, SOL:4152-4159)
-            SwdPost<R> N{};
+            SwdPostLit<R> NL{};
+            SwdPost<R> &N = NL;
             N.ncol = ncol; N.lm = lm; N.ngpt = NG_SW; N.aerosols = 0; N.undef = Q.undef;
             N.swuflx = nflux[0]; N.swdflx = nflux[1]; N.swuflxc = nflux[2]; N.swdflxc = nflux[3]; N.clearCounts = cc;
             N.fsw = (R *)out[GEOSRAD_SWD_FSWNA]; N.fsc = (R *)out[GEOSRAD_SWD_FSCNA]; N.fswu = (R *)out[GEOSRAD_SWD_FSWUNA];
             N.fscu = (R *)out[GEOSRAD_SWD_FSCUNA];
-            hipLaunchKernelGGL((k_swd_post<R>), dim3(gx, lm + 1), blk, 0, st, N);
+            if (lit) post_lit(NL, {GEOSRAD_SWD_FSWNA, GEOSRAD_SWD_FSCNA, GEOSRAD_SWD_FSWUNA, GEOSRAD_SWD_FSCUNA, -1, -1, -1, -1, -1, -1, -1, -1});
+            else hipLaunchKernelGGL((k_swd_post<R>), dim3(gx, lm + 1), blk, 0, st, N);
+        }
+        if (lit) {      // the results the solver wrote as the driver returns them
+            LitFields F;
+            for (int k = 0; k < 6; k++) F.push_back({sc_ix[k], scal[k], 1});
+            F.push_back({GEOSRAD_SWD_FSWBAND, band, 14});
+            if (want_na) F.push_back({GEOSRAD_SWD_FSWBANDNA, nband, 14});
+            if (const int rc = lit_scatter(st, *lit, ncol, out, F)) return rc;
         }
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
@@ -1505,24 +1595,45 @@ template <typename R> struct Ctx : geosrad_ctx {
     }
 
     // Chou-Suarez branch of SORADCORE: k_swc_prep + sorad_dev.  The prepared arrays live in a buffer of their own (sorad_dev's scratch is
-    // sized per chunk, these per call).
+    // sized per chunk, these per call).  On a tile (lit) that buffer also holds, NumLit wide, the imports sorad reads as they are and all its
+    // results, which one k_lit_scatter takes to the tile.
     int sw_driver_chou_dev(hipStream_t st, int ncol, int lm, const void *const *in, const double *consts, int lcldmh, int lcldlm,
-                           const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out) override
+                           const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out, const LitTile *lit) override
     {
         HIPCHK(hipSetDevice(device));
-        if (ncol <= 0 || lm < 4) return fail(GEOSRAD_EINVAL, "bad ncol/lm");
+        if ((lit ? lit->tile : ncol) <= 0 || lm < 4) return fail(GEOSRAD_EINVAL, "bad ncol/lm");
         if (!consts) return fail(GEOSRAD_EINVAL, "consts null");
         const bool aer = in[GEOSRAD_SWC_TAUA] != nullptr;
         if (aer != (in[GEOSRAD_SWC_SSAA] != nullptr) || aer != (in[GEOSRAD_SWC_ASYA] != nullptr))
             return fail(GEOSRAD_EINVAL, "TAUA / SSAA / ASYA: all three or none");
         for (int k = 0; k < GEOSRAD_SWC_NIN; k++)
             if (!in[k] && !(k >= GEOSRAD_SWC_TAUA && k <= GEOSRAD_SWC_ASYA)) return fail(GEOSRAD_EINVAL, "null input field");
-        const size_t cl = (size_t)lm * ncol;
-        SwcPrep<R> P{};
+        const int nres = do_drfband ? GEOSRAD_SWC_NOUT : GEOSRAD_SWC_DRBAND;      // results sorad writes
+        if (lit) if (const int rc = lit_check(*lit, ncol, out, nres)) return rc;
+        auto rows = [lm](int k) { return k <= GEOSRAD_SWC_FSCU ? lm + 1 : (k >= GEOSRAD_SWC_FSWBAND ? 8 : 1); };
+        if (lit) {      // what sorad_dev would reject, before anything is launched
+            if (const int rc = sorad_check_options(1, lm, 8, lcldmh, lcldlm, hk_uv, hk_ir)) return rc;
+            for (int k = 0; k < nres; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
+            if (ncol == 0) {
+                LitFields F;
+                for (int k = 0; k < nres; k++) F.push_back({k, nullptr, rows(k)});
+                return lit_scatter(st, *lit, 0, out, F);
+            }
+        }
+        const size_t n = (size_t)ncol, cl = (size_t)lm * ncol;
+        SwcLit<R> PL{};
+        SwcPrep<R> &P = PL;
         R *zero = nullptr;          // TAUA = SSAA = ASYA = 0 (SOL:4543-4546): one block serves the three
+        R *res[GEOSRAD_SWC_NOUT] = {};
         auto carve = [&](Carve c) {
             P.plhpa = c.take<R>(cl + ncol); P.o3 = c.take<R>(cl); P.qq3 = c.take<R>(4 * cl); P.rr3 = c.take<R>(4 * cl);
             if (!aer) zero = c.take<R>(8 * cl);
+            if (lit) {
+                for (auto &q : PL.lay_out) q = c.take<R>(cl);
+                if (aer) for (auto &q : PL.aer_out) q = c.take<R>(8 * cl);
+                for (auto &q : PL.col_out) q = c.take<R>(n);
+                for (int k = 0; k < nres; k++) res[k] = c.take<R>(n * rows(k));
+            }
             return c.off;
         };
         if (d_ws_swc.reserve(carve(Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "SORADCORE (Chou-Suarez) workspace");
@@ -1531,20 +1642,36 @@ template <typename R> struct Ctx : geosrad_ctx {
         P.ple = (const R *)in[GEOSRAD_SWC_PLE]; P.ox = (const R *)in[GEOSRAD_SWC_OX];
         for (int s = 0; s < 4; s++) { P.q[s] = (const R *)in[GEOSRAD_SWC_QI + s]; P.r[s] = (const R *)in[GEOSRAD_SWC_RI + s]; }
         P.o3fac = (R)consts[GEOSRAD_SWC_C_O3MW] / (R)consts[GEOSRAD_SWC_C_AIRMW]; P.undef = (R)consts[GEOSRAD_SWC_C_UNDEF];
-        hipLaunchKernelGGL((k_swc_prep<R>), dim3(grid256(ncol), lm + 1), dim3(256), 0, st, P);
+        // T Q CL, TAUA SSAA ASYA, ZT ALBVR ALBVF ALBNR ALBNF: the caller's packed arrays, or the tile's gathered by the prep kernel
+        static const int lay_ix[3] = {GEOSRAD_SWC_T, GEOSRAD_SWC_Q, GEOSRAD_SWC_CL}, aer_ix[3] = {GEOSRAD_SWC_TAUA, GEOSRAD_SWC_SSAA, GEOSRAD_SWC_ASYA},
+                         col_ix[5] = {GEOSRAD_SWC_ZT, GEOSRAD_SWC_ALBVR, GEOSRAD_SWC_ALBVF, GEOSRAD_SWC_ALBNR, GEOSRAD_SWC_ALBNF};
+        const void *lay[3], *aerp[3], *col[5];
+        for (int k = 0; k < 3; k++) { lay[k] = lit ? PL.lay_out[k] : in[lay_ix[k]]; aerp[k] = !aer ? zero : (lit ? PL.aer_out[k] : in[aer_ix[k]]); }
+        for (int k = 0; k < 5; k++) col[k] = lit ? PL.col_out[k] : in[col_ix[k]];
+        if (lit) {
+            PL.tile = lit->tile; PL.lit = lit->idx;
+            for (int k = 0; k < 3; k++) { PL.lay_in[k] = (const R *)in[lay_ix[k]]; PL.aer_in[k] = (const R *)in[aer_ix[k]]; }
+            for (int k = 0; k < 5; k++) PL.col_in[k] = (const R *)in[col_ix[k]];
+            hipLaunchKernelGGL((k_swc_prep<R, true>), dim3(grid256(ncol), lm + 1), dim3(256), 0, st, PL);
+        } else hipLaunchKernelGGL((k_swc_prep<R>), dim3(grid256(ncol), lm + 1), dim3(256), 0, st, P);
         HIPCHK(hipGetLastError());
         if (!aer) HIPCHK(hipMemsetAsync(zero, 0, 8 * cl * sizeof(R), st));
         const void *si[SI_NIN];
-        si[SI_COSZ] = in[GEOSRAD_SWC_ZT]; si[SI_PL] = P.plhpa; si[SI_TA] = in[GEOSRAD_SWC_T]; si[SI_WA] = in[GEOSRAD_SWC_Q]; si[SI_OA] = P.o3;
-        si[SI_CWC] = P.qq3; si[SI_FCLD] = in[GEOSRAD_SWC_CL]; si[SI_REFF] = P.rr3;
-        si[SI_TAUA] = aer ? in[GEOSRAD_SWC_TAUA] : zero; si[SI_SSAA] = aer ? in[GEOSRAD_SWC_SSAA] : zero; si[SI_ASYA] = aer ? in[GEOSRAD_SWC_ASYA] : zero;
-        si[SI_RSUVBM] = in[GEOSRAD_SWC_ALBVR]; si[SI_RSUVDF] = in[GEOSRAD_SWC_ALBVF]; si[SI_RSIRBM] = in[GEOSRAD_SWC_ALBNR]; si[SI_RSIRDF] = in[GEOSRAD_SWC_ALBNF];
+        si[SI_COSZ] = col[0]; si[SI_PL] = P.plhpa; si[SI_TA] = lay[0]; si[SI_WA] = lay[1]; si[SI_OA] = P.o3;
+        si[SI_CWC] = P.qq3; si[SI_FCLD] = lay[2]; si[SI_REFF] = P.rr3;
+        si[SI_TAUA] = aerp[0]; si[SI_SSAA] = aerp[1]; si[SI_ASYA] = aerp[2];
+        si[SI_RSUVBM] = col[1]; si[SI_RSUVDF] = col[2]; si[SI_RSIRBM] = col[3]; si[SI_RSIRDF] = col[4];
+        auto O = [&](int k) { return lit ? (void *)res[k] : out[k]; };
         void *so[SOO_NOUT];
-        so[SOO_FLX] = out[GEOSRAD_SWC_FSW]; so[SOO_FLC] = out[GEOSRAD_SWC_FSC]; so[SOO_FLXU] = out[GEOSRAD_SWC_FSWU]; so[SOO_FLCU] = out[GEOSRAD_SWC_FSCU];
-        so[SOO_FDIRIR] = out[GEOSRAD_SWC_NIRR]; so[SOO_FDIFIR] = out[GEOSRAD_SWC_NIRF]; so[SOO_FDIRPAR] = out[GEOSRAD_SWC_PARR];
-        so[SOO_FDIFPAR] = out[GEOSRAD_SWC_PARF]; so[SOO_FDIRUV] = out[GEOSRAD_SWC_UVRR]; so[SOO_FDIFUV] = out[GEOSRAD_SWC_UVRF];
-        so[SOO_SFCBAND] = out[GEOSRAD_SWC_FSWBAND]; so[SOO_DRBAND] = out[GEOSRAD_SWC_DRBAND]; so[SOO_DFBAND] = out[GEOSRAD_SWC_DFBAND];
-        return sorad_dev(st, ncol, lm, 8, si, consts[GEOSRAD_SWC_C_CO2], lcldmh, lcldlm, hk_uv, hk_ir, so, do_drfband);
+        so[SOO_FLX] = O(GEOSRAD_SWC_FSW); so[SOO_FLC] = O(GEOSRAD_SWC_FSC); so[SOO_FLXU] = O(GEOSRAD_SWC_FSWU); so[SOO_FLCU] = O(GEOSRAD_SWC_FSCU);
+        so[SOO_FDIRIR] = O(GEOSRAD_SWC_NIRR); so[SOO_FDIFIR] = O(GEOSRAD_SWC_NIRF); so[SOO_FDIRPAR] = O(GEOSRAD_SWC_PARR);
+        so[SOO_FDIFPAR] = O(GEOSRAD_SWC_PARF); so[SOO_FDIRUV] = O(GEOSRAD_SWC_UVRR); so[SOO_FDIFUV] = O(GEOSRAD_SWC_UVRF);
+        so[SOO_SFCBAND] = O(GEOSRAD_SWC_FSWBAND); so[SOO_DRBAND] = O(GEOSRAD_SWC_DRBAND); so[SOO_DFBAND] = O(GEOSRAD_SWC_DFBAND);
+        if (const int rc = sorad_dev(st, ncol, lm, 8, si, consts[GEOSRAD_SWC_C_CO2], lcldmh, lcldlm, hk_uv, hk_ir, so, do_drfband)) return rc;
+        if (!lit) return GEOSRAD_OK;
+        LitFields F;
+        for (int k = 0; k < nres; k++) F.push_back({k, res[k], rows(k)});
+        return lit_scatter(st, *lit, ncol, out, F);
     }
 
     int lw_update_flx_dev(hipStream_t st, int ncol, int lm, int rrtmg, int lev_mid_high, int lev_low_mid, double undef,
@@ -2185,6 +2312,16 @@ template <typename R> struct Ctx : geosrad_ctx {
     }
 
     // the array checks sw_host makes before it stages anything and sw_run makes in its own order
+    int sw_check_options(int ncol, int nlay, int iceflg, int liqflg, int cloudLM, int cloudMH, int iaer)
+    {
+        if (!have_sw) return fail(GEOSRAD_EINVAL, "RRTMG_SW tables not set: call geosrad_set_tables_sw first (rrtmg_sw_ini)");
+        if (ncol <= 0 || nlay < 4 || nlay > 203) return fail(GEOSRAD_EINVAL, "bad ncol/nlay (4 <= nlay <= mxlay = 203)");
+        if (iceflg < 1 || iceflg > 4) return fail(GEOSRAD_EINPUT, "cldprmc_sw: invalid iceflag");
+        if (liqflg != 1) return fail(GEOSRAD_EINPUT, "cldprmc_sw: invalid liqflag");
+        if (cloudLM == cloudMH) return fail(GEOSRAD_EINPUT, "invalid pressure super-layers!");
+        if (iaer != 0 && iaer != 10) return fail(GEOSRAD_EINPUT, "iaer must be 0 or 10");
+        return GEOSRAD_OK;
+    }
     int sw_check_arrays(const void *const *in, void *const *out, int iaer, int do_drfband)
     {
         for (int k = 0; k < S_NIN; k++)
@@ -2203,12 +2340,7 @@ template <typename R> struct Ctx : geosrad_ctx {
                void *radval = nullptr)
     {
         HIPCHK(hipSetDevice(device));
-        if (!have_sw) return fail(GEOSRAD_EINVAL, "RRTMG_SW tables not set: call geosrad_set_tables_sw first (rrtmg_sw_ini)");
-        if (ncol <= 0 || nlay < 4 || nlay > 203) return fail(GEOSRAD_EINVAL, "bad ncol/nlay (4 <= nlay <= mxlay = 203)");
-        if (iceflg < 1 || iceflg > 4) return fail(GEOSRAD_EINPUT, "cldprmc_sw: invalid iceflag");
-        if (liqflg != 1) return fail(GEOSRAD_EINPUT, "cldprmc_sw: invalid liqflag");
-        if (cloudLM == cloudMH) return fail(GEOSRAD_EINPUT, "invalid pressure super-layers!");
-        if (iaer != 0 && iaer != 10) return fail(GEOSRAD_EINPUT, "iaer must be 0 or 10");
+        if (const int rc = sw_check_options(ncol, nlay, iceflg, liqflg, cloudLM, cloudMH, iaer)) return rc;
         if (const int rc = sw_check_arrays(in, out, iaer, do_drfband)) return rc;
         if (radval && dbg) return fail(GEOSRAD_EINVAL, "the stage dumps do not produce the SOLAR_RADVAL diagnostics");
         SwSolar<R> SV;
@@ -2448,16 +2580,22 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 
-    int sorad_dev(hipStream_t st, int m, int np, int nb, const void *const *in, double co2, int ict, int icb, const void *hk_uv,
-                  const void *hk_ir, void *const *out, int do_drfband) override
+    int sorad_check_options(int m, int np, int nb, int ict, int icb, const void *hk_uv, const void *hk_ir)
     {
-        HIPCHK(hipSetDevice(device));
         if (!have_sorad) return fail(GEOSRAD_EINVAL, "Chou-Suarez SW tables not set: call geosrad_load_tables_chou_sw first");
         if (m <= 0 || np < 4 || np > 400) return fail(GEOSRAD_EINVAL, "bad m/np");
         if (nb < 8) return fail(GEOSRAD_EINVAL, "nb (bands of the aerosol arrays) must be 8");
         const bool oc = (overcast & GEOSRAD_OVERCAST_SORAD) != 0;      // -DOVERCAST reads neither ict nor icb
         if (!oc && !(ict >= 1 && ict < icb && icb <= np)) return fail(GEOSRAD_EINPUT, "ict / icb must satisfy 1 <= ict < icb < np + 1");
         if (!hk_uv || !hk_ir) return fail(GEOSRAD_EINVAL, "hk_uv / hk_ir null");
+        return GEOSRAD_OK;
+    }
+    int sorad_dev(hipStream_t st, int m, int np, int nb, const void *const *in, double co2, int ict, int icb, const void *hk_uv,
+                  const void *hk_ir, void *const *out, int do_drfband) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = sorad_check_options(m, np, nb, ict, icb, hk_uv, hk_ir)) return rc;
+        const bool oc = (overcast & GEOSRAD_OVERCAST_SORAD) != 0;      // -DOVERCAST reads neither ict nor icb
         for (int k = 0; k < SI_NIN; k++) if (!in[k]) return fail(GEOSRAD_EINVAL, "null input array");
         for (int k = 0; k < SOO_DRBAND; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
         if (do_drfband && (!out[SOO_DRBAND] || !out[SOO_DFBAND])) return fail(GEOSRAD_EINVAL, "do_drfband set but drband/dfband null");
@@ -2789,11 +2927,12 @@ struct MultiCtx final : geosrad_ctx {
     int lw_driver_dev(hipStream_t, int, int, int, const void *const *, const double *, int, int, int, int, int, const int32_t *, void *const *, int,
                       const int32_t *, void *const *) override { return nodev("geosrad_lw_driver_rrtmg_dev"); }
     int sw_driver_dev(hipStream_t, int, int, int, const void *const *, const double *, int, int, double, double, int, int, int, int, int, int,
-                      const void *, const void *, void *const *) override { return nodev("geosrad_sw_driver_rrtmg_dev"); }
+                      const void *, const void *, void *const *, const LitTile *lit) override
+    { return nodev(lit ? "geosrad_sw_driver_rrtmg_lit_dev" : "geosrad_sw_driver_rrtmg_dev"); }
     int lw_chou_post_dev(hipStream_t, int, int, const void *const *, void *const *) override { return nodev("geosrad_lw_chou_post_dev"); }
     int lw_driver_chou_dev(hipStream_t, int, int, const void *const *, const double *, int, int, int, int, void *const *) override { return nodev("geosrad_lw_driver_chou_dev"); }
     int sw_driver_chou_dev(hipStream_t, int, int, const void *const *, const double *, int, int, const void *, const void *, int,
-                           void *const *) override { return nodev("geosrad_sw_driver_chou_dev"); }
+                           void *const *, const LitTile *lit) override { return nodev(lit ? "geosrad_sw_driver_chou_lit_dev" : "geosrad_sw_driver_chou_dev"); }
     int lw_update_flx_dev(hipStream_t, int, int, int, int, int, double, const void *const *, void *const *) override { return nodev("geosrad_lw_update_flx_dev"); }
     int lw_update_rats_dev(hipStream_t, int, int, int, const void *const *, void *const *) override { return nodev("geosrad_lw_update_rats_dev"); }
     int lw_update_bands_dev(hipStream_t, int, const int32_t *, const double *, const double *, double, const void *, const void *, const void *,
@@ -3236,14 +3375,34 @@ int geosrad_sw_driver_rrtmg_dev(geosrad_ctx *c, void *stream, int ncol, int lm, 
 {
     if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
     return c->sw_driver_dev((hipStream_t)stream, ncol, lm, nb_aer, in, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr,
-                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out);
+                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, nullptr);
+}
+
+int geosrad_sw_driver_rrtmg_lit_dev(geosrad_ctx *c, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos, int lm,
+                                    int nb_aer, const void *const *in, const double *consts, int iceflgsw, int liqflgsw, double sc, double dist,
+                                    int isolvar, int dyofyr, int include_aerosols, int lcldlm, int lcldmh, int normflx, const void *bndsolvar,
+                                    const void *indsolvar, const double *dark, uint64_t keep_mask, void *const *out)
+{
+    if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
+    const LitTile lit{ncol, lit_index, lit_pos, dark, keep_mask};
+    return c->sw_driver_dev((hipStream_t)stream, nlit, lm, nb_aer, in, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr,
+                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, &lit);
 }
 
 int geosrad_sw_driver_chou_dev(geosrad_ctx *c, void *stream, int ncol, int lm, const void *const *in, const double *consts, int lcldmh,
                                int lcldlm, const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out)
 {
     if (!c || !in || !out) return GEOSRAD_EINVAL;
-    return c->sw_driver_chou_dev((hipStream_t)stream, ncol, lm, in, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, out);
+    return c->sw_driver_chou_dev((hipStream_t)stream, ncol, lm, in, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, out, nullptr);
+}
+
+int geosrad_sw_driver_chou_lit_dev(geosrad_ctx *c, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos, int lm,
+                                   const void *const *in, const double *consts, int lcldmh, int lcldlm, const void *hk_uv, const void *hk_ir,
+                                   int do_drfband, const double *dark, uint64_t keep_mask, void *const *out)
+{
+    if (!c || !in || !out) return GEOSRAD_EINVAL;
+    const LitTile lit{ncol, lit_index, lit_pos, dark, keep_mask};
+    return c->sw_driver_chou_dev((hipStream_t)stream, nlit, lm, in, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, out, &lit);
 }
 
 int geosrad_lw_driver_chou_dev(geosrad_ctx *c, void *stream, int ncol, int lm, const void *const *in, const double *consts, int trace,

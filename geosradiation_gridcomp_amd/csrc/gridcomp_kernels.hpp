@@ -6,6 +6,9 @@
 //                                        conventions, SFCEM, net fluxes, super-layer cloud fractions
 //   k_swd_prep / k_swd_zm / k_swd_post   the same for SORADCORE's RRTMG branch (GEOSsolar_GridComp/GEOS_SolarGridComp.F90:6113-6219,
 //                                        :6395-6454)
+//   k_swd_prep<R, true> / k_swc_prep<R, true> / k_swd_post_lit / k_lit_scatter
+//                                        the same on the un-packed tile: PackIt (SOL:3839-3894) inside the prep kernels, UnPackIt with
+//                                        its DEFAULT (SOL:6520-6580) inside the post kernel and one scatter over the remaining results
 //   k_lw_update_flx                      Update_Flx (IRR:3861-3999): the heartbeat linearisation of the LW fluxes in the surface
 //                                        temperature, every model step between two full calculations
 //   k_sw_update_export                   the 3-D / TOA / surface flux part of UPDATE_EXPORT (SOL:7540-7579): normalised fluxes x SLR
@@ -14,6 +17,7 @@
 // blockIdx.y = level): all accesses are coalesced, nothing is transposed, the vertical flip is an index calculation.
 // A null output pointer = Fortran "not associated" (export not requested).
 #pragma once
+#include <type_traits>
 #include "../../include/geosrad.h"
 #include "lw_device.hpp"
 #include "chou_kernels.hpp"      // gr_log10
@@ -322,18 +326,46 @@ template <typename R> struct SwcPrep {
     R o3fac, undef;                       // MAPL_O3MW / MAPL_AIRMW
     R *plhpa, *o3, *qq3, *rr3;            // (ncol, LM+1), (ncol, LM), (ncol, LM, 4) x 2
 };
-template <typename R> __global__ void __launch_bounds__(256) k_swc_prep(SwcPrep<R> P)
+// LIT: the imports are the un-packed tile's (leading dimension `tile`), read at column lit[m] of packed position m = the lane (PackIt,
+// SOL:3839-3894); every store goes to the packed workspace as before.  What `sorad` reads as it is travels along: T, Q, CL (row k < LM),
+// the aerosol arrays (rows (band, k)), cos zenith and the four albedos (row LM).
+template <typename R> struct SwcLit : SwcPrep<R> {
+    int tile;
+    const int32_t *lit;
+    const R *lay_in[3], *aer_in[3], *col_in[5];      // T Q CL; TAUA SSAA ASYA (all three or none); ZT ALBVR ALBVF ALBNR ALBNF
+    R *lay_out[3], *aer_out[3], *col_out[5];
+};
+template <typename R, bool LIT> using SwcPrepOf = std::conditional_t<LIT, SwcLit<R>, SwcPrep<R>>;
+template <typename R, bool LIT = false> __global__ void __launch_bounds__(256) k_swc_prep(SwcPrepOf<R, LIT> P)
 {
 #pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
     const int ij = blockIdx.x * blockDim.x + threadIdx.x;
     if (ij >= P.ncol) return;
     const int k = blockIdx.y;                                      // 0 .. LM
     const size_t o = (size_t)k * P.ncol + ij;
-    const R pe = P.ple[o];
+    size_t g = o, gn = P.ncol;                                     // the same cell of the imports
+    if constexpr (LIT) { gn = P.tile; g = (size_t)k * gn + P.lit[ij]; }
+    const R pe = P.ple[g];
     P.plhpa[o] = pe * (R)0.01;                                     // SOL:4490
+    if constexpr (LIT) {
+        if (k == P.lm) {
+            const size_t c = g - (size_t)k * gn;
+#pragma unroll
+            for (int s = 0; s < 5; s++) P.col_out[s][ij] = P.col_in[s][c];
+        } else {
+#pragma unroll
+            for (int s = 0; s < 3; s++) P.lay_out[s][o] = P.lay_in[s][g];
+            if (P.aer_in[0])
+                for (int b = 0; b < 8; b++) {
+                    const size_t bo = (size_t)b * P.lm * P.ncol + o, bg = (size_t)b * P.lm * gn + g;
+#pragma unroll
+                    for (int s = 0; s < 3; s++) P.aer_out[s][bo] = P.aer_in[s][bg];
+                }
+        }
+    }
     if (k == P.lm) return;
-    const R pl = (R)0.5 * (pe + P.ple[o + P.ncol]);                // SOL:4488
-    R o3 = P.ox[o];                                                // SOL:4523-4533
+    const R pl = (R)0.5 * (pe + P.ple[g + gn]);                    // SOL:4488
+    R o3 = P.ox[g];                                                // SOL:4523-4533
     if (pl < (R)100.) {
         const R x = gr_log10<R>(pl) - (R)2.;
         o3 = o3 * gr_exp<R>((R)-1.5 * (x * x));
@@ -344,8 +376,8 @@ template <typename R> __global__ void __launch_bounds__(256) k_swc_prep(SwcPrep<
     const size_t sp = (size_t)P.lm * P.ncol;
 #pragma unroll
     for (int s = 0; s < 4; s++) {
-        P.qq3[s * sp + o] = P.q[s][o];                             // SOL:4502-4505
-        R r = P.r[s][o];
+        P.qq3[s * sp + o] = P.q[s][g];                             // SOL:4502-4505
+        R r = P.r[s][g];
         if (r == P.undef) r = dflt[s];
         P.rr3[s * sp + o] = r * (R)1.e6;                           // SOL:4512-4515
     }
@@ -560,10 +592,22 @@ template <typename R> struct SwdArgs {
     R *play, *plev, *tlay, *tlev, *h2o, *o3_r, *co2_r, *ch4_r, *o2_r, *cldf, *ciwp, *clwp, *rei, *rel, *zl, *tauaer, *ssaaer, *asmaer;
 };
 
-template <typename R> GR_DEV R swd_tlev(const SwdArgs<R> &A, int k, int ij)      // TLEV(1..LM+1), SOL:6172-6176
+// LIT: the imports are the un-packed tile's (leading dimension `tile`), read at column lit[m] of packed position m = the lane (PackIt,
+// SOL:3839-3894); every store goes to the packed workspace as before, and the aerosol imports are only read (the reference normalises its
+// packed buffer, SOL:6116-6125 on BufInp, never the import).  The per-column imports the solver reads as they are travel along (row K = 1).
+template <typename R> struct SwdLit : SwdArgs<R> {
+    int tile;
+    const int32_t *lit;
+    const R *col_in[6];      // ZT ALAT ALBVR ALBVF ALBNR ALBNF
+    R *col_out[6];
+};
+template <typename R, bool LIT> using SwdArgsOf = std::conditional_t<LIT, SwdLit<R>, SwdArgs<R>>;
+
+// ij, n: the column of the imports and their leading dimension
+template <typename R> GR_DEV R swd_tlev(const SwdArgs<R> &A, int k, int ij, int n)      // TLEV(1..LM+1), SOL:6172-6176
 {
 #pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
-    const int n = A.ncol, lm = A.lm;
+    const int lm = A.lm;
     if (k == lm + 1) return A.ts[ij];
     if (k == 1) k = 2;
     auto PLE = [&](int l) { return A.ple[(size_t)(l - 1) * n + ij]; };
@@ -572,14 +616,16 @@ template <typename R> GR_DEV R swd_tlev(const SwdArgs<R> &A, int k, int ij)     
     return (T(k - 1) * dpk + T(k) * dpm) / (dpm + dpk);
 }
 
-template <typename R> __global__ void __launch_bounds__(256) k_swd_prep(SwdArgs<R> A)
+template <typename R, bool LIT = false> __global__ void __launch_bounds__(256) k_swd_prep(SwdArgsOf<R, LIT> A)
 {
 #pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
-    const int ij = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ij >= A.ncol) return;
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;                               // packed position
+    if (m >= A.ncol) return;
     const int n = A.ncol, lm = A.lm, K = blockIdx.y + 1, LV = lm - K + 1;
-    const size_t o = (size_t)(K - 1) * n + ij, g = (size_t)(LV - 1) * n + ij;
-    const R dpr = A.ple[(size_t)LV * n + ij] - A.ple[(size_t)(LV - 1) * n + ij];      // DPR(LV) = PLE(LV+1) - PLE(LV)
+    int ij = m, gn = n;                                                                // column and leading dimension of the imports
+    if constexpr (LIT) { ij = A.lit[m]; gn = A.tile; }
+    const size_t o = (size_t)(K - 1) * n + m, g = (size_t)(LV - 1) * gn + ij;
+    const R dpr = A.ple[(size_t)LV * gn + ij] - A.ple[(size_t)(LV - 1) * gn + ij];    // DPR(LV) = PLE(LV+1) - PLE(LV)
     const R xx = (R)1.02 * (R)100 * dpr;
     A.ciwp[o] = xx * A.qq_ice[g];
     A.clwp[o] = xx * A.qq_liq[g];
@@ -594,11 +640,11 @@ template <typename R> __global__ void __launch_bounds__(256) k_swd_prep(SwdArgs<
     else if (A.iceflg == 4) reice = clampr<R>(reice * (R)2., (R)1., (R)200.);
     A.rei[o] = reice; A.rel[o] = reliq;
     // PLE_R(1:LM+1) = PLE(LM+1:1)/100, TLEV_R likewise (SOL:6180-6181)
-    A.plev[o] = A.ple[(size_t)LV * n + ij] / (R)100.;      // PLE(LV+1)
-    A.tlev[o] = swd_tlev<R>(A, LV + 1, ij);
+    A.plev[o] = A.ple[(size_t)LV * gn + ij] / (R)100.;     // PLE(LV+1)
+    A.tlev[o] = swd_tlev<R>(A, LV + 1, ij, gn);
     if (K == lm) {
-        A.plev[(size_t)lm * n + ij] = A.ple[ij] / (R)100.;
-        A.tlev[(size_t)lm * n + ij] = swd_tlev<R>(A, 1, ij);
+        A.plev[(size_t)lm * n + m] = A.ple[ij] / (R)100.;
+        A.tlev[(size_t)lm * n + m] = swd_tlev<R>(A, 1, ij, gn);
     }
     auto pos = [](R x) { return x < 0 ? (R)0 : x; };
     A.play[o] = A.pl[g] / (R)100.;
@@ -614,18 +660,23 @@ template <typename R> __global__ void __launch_bounds__(256) k_swd_prep(SwdArgs<
     for (int b = 0; b < A.nb; b++) {
         R ta = 0, ss = 0, as = 0;
         if (A.taua) {
-            const size_t ga = ((size_t)b * lm + (LV - 1)) * n + ij;
+            const size_t ga = ((size_t)b * lm + (LV - 1)) * gn + ij;
             ta = A.taua[ga]; ss = A.ssaa[ga]; as = A.asya[ga];
             if (ta > 0 && ss > 0) { as = as / ss; ss = ss / ta; }
             else { ta = 0; ss = 0; as = 0; }
-            A.taua[ga] = ta; A.ssaa[ga] = ss; A.asya[ga] = as;
+            if constexpr (!LIT) { A.taua[ga] = ta; A.ssaa[ga] = ss; A.asya[ga] = as; }
         }
-        const size_t oa = ((size_t)b * lm + (K - 1)) * n + ij;
+        const size_t oa = ((size_t)b * lm + (K - 1)) * n + m;
         A.tauaer[oa] = ta; A.ssaaer[oa] = ss; A.asmaer[oa] = as;
+    }
+    if constexpr (LIT) {
+        if (K == 1)
+#pragma unroll
+            for (int s = 0; s < 6; s++) A.col_out[s][m] = A.col_in[s][ij];
     }
 }
 
-// ZL_R (SOL:6200-6207): note the level index differs from LW (levels are 1-based here)
+// ZL_R (SOL:6200-6207): note the level index differs from LW (levels are 1-based here).  Reads the workspace only: packed either way.
 template <typename R> __global__ void __launch_bounds__(256) k_swd_zm(SwdArgs<R> A)
 {
 #pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
@@ -653,13 +704,13 @@ template <typename R> struct SwdPost {
     R *cldts, *cldhs, *cldms, *cldls, *cot[4];
 };
 
-template <typename R> __global__ void __launch_bounds__(256) k_swd_post(SwdPost<R> P)
+// the statements of the post step for one (column, level L = model level 0..LM of the un-flipped arrays): the solver's results are read
+// at column ij of n, the outputs written at column c of ld
+template <typename R> GR_DEV void swd_post_cell(const SwdPost<R> &P, int L, int ij, int n, int c, int ld)
 {
 #pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
-    const int ij = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ij >= P.ncol) return;
-    const int n = P.ncol, lm = P.lm, L = blockIdx.y;      // model level index 0..LM of the un-flipped arrays
-    const size_t s = (size_t)(lm - L) * n + ij, o = (size_t)L * n + ij;
+    const int lm = P.lm;
+    const size_t s = (size_t)(lm - L) * n + ij, o = (size_t)L * ld + c;
     const R u = P.swuflx[s], d = P.swdflx[s], uc = P.swuflxc[s], dcl = P.swdflxc[s];
     if (P.fsw) P.fsw[o] = d - u;                          // SOL:6447-6450
     if (P.fsc) P.fsc[o] = dcl - uc;
@@ -668,17 +719,72 @@ template <typename R> __global__ void __launch_bounds__(256) k_swd_post(SwdPost<
     if (L == 0) {
         const R ng = (R)P.ngpt;
         if (P.aerosols) {                                  // SOL:6405-6410
-            if (P.cldts) P.cldts[ij] = (R)1. - (R)P.clearCounts[(size_t)0 * n + ij] / ng;
-            if (P.cldhs) P.cldhs[ij] = (R)1. - (R)P.clearCounts[(size_t)1 * n + ij] / ng;
-            if (P.cldms) P.cldms[ij] = (R)1. - (R)P.clearCounts[(size_t)2 * n + ij] / ng;
-            if (P.cldls) P.cldls[ij] = (R)1. - (R)P.clearCounts[(size_t)3 * n + ij] / ng;
+            if (P.cldts) P.cldts[c] = (R)1. - (R)P.clearCounts[(size_t)0 * n + ij] / ng;
+            if (P.cldhs) P.cldhs[c] = (R)1. - (R)P.clearCounts[(size_t)1 * n + ij] / ng;
+            if (P.cldms) P.cldms[c] = (R)1. - (R)P.clearCounts[(size_t)2 * n + ij] / ng;
+            if (P.cldls) P.cldls[c] = (R)1. - (R)P.clearCounts[(size_t)3 * n + ij] / ng;
         }
         for (int k = 0; k < 4; k++)                        // SOL:6416-6438
             if (P.cot[k]) {
                 const R a = P.cotn[k][ij], b = P.cotd[k][ij];
-                P.cot[k][ij] = (a > 0 && b > 0) ? a / b : P.undef;
+                P.cot[k][c] = (a > 0 && b > 0) ? a / b : P.undef;
             }
     }
+}
+
+template <typename R> __global__ void __launch_bounds__(256) k_swd_post(SwdPost<R> P)
+{
+    const int ij = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ij >= P.ncol) return;
+    swd_post_cell<R>(P, blockIdx.y, ij, P.ncol, ij, P.ncol);
+}
+
+// k_swd_post on the un-packed tile: one thread per (TILE column, model level).  A lit column (pos >= 0) reads the solver's packed result
+// at its position; a dark one receives UnPackIt's DEFAULT (SOL:6534) unless the output's keep bit is set (an InOut internal,
+// SOL:6523-6524).  dark[] / keep bits in the order fsw fsc fswu fscu cldts cldhs cldms cldls cot[0..3].
+template <typename R> struct SwdPostLit : SwdPost<R> {
+    int tile;
+    const int32_t *pos;
+    R dark[12];
+    uint32_t keep;
+};
+template <typename R> __global__ void __launch_bounds__(256) k_swd_post_lit(SwdPostLit<R> P)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= P.tile) return;
+    const int n = P.ncol, L = blockIdx.y;                 // n = NumLit, the leading dimension of the solver's arrays
+    const int ij = P.pos[c];
+    if (ij >= 0 && ij < n) swd_post_cell<R>(P, L, ij, n, c, P.tile);
+    else {
+        const size_t o = (size_t)L * P.tile + c;
+        auto fill = [&](R *q, int k, size_t at) { if (q && !(P.keep >> k & 1u)) q[at] = P.dark[k]; };
+        fill(P.fsw, 0, o); fill(P.fsc, 1, o); fill(P.fswu, 2, o); fill(P.fscu, 3, o);
+        if (L == 0) {
+            fill(P.cldts, 4, c); fill(P.cldhs, 5, c); fill(P.cldms, 6, c); fill(P.cldls, 7, c);
+            for (int k = 0; k < 4; k++) fill(P.cot[k], 8 + k, c);
+        }
+    }
+}
+
+// UnPackIt (SOL:7776-7799) of every result a solver leaves as it is, in one launch: field k holds the rows f[k].row0 .. f[k + 1].row0 - 1 of
+// blockIdx.y; UnPacked(c, l) = Packed(pos[c], l) on a lit column, `dark` on a dark one unless `keep`.  One thread per (tile column, row).
+constexpr int LIT_NFIELD = 24;
+template <typename R> struct LitScatter {
+    int tile, nlit, nf;
+    const int32_t *pos;
+    struct { const R *src; R *dst; int row0, keep; R dark; } f[LIT_NFIELD];
+    int rows;                                             // row0 of the field after the last
+};
+template <typename R> __global__ void __launch_bounds__(256) k_lit_scatter(LitScatter<R> S)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x, row = blockIdx.y;
+    if (c >= S.tile) return;
+    int k = 0;
+    while (k + 1 < S.nf && S.f[k + 1].row0 <= row) k++;
+    const size_t l = (size_t)(row - S.f[k].row0);
+    const int m = S.pos[c];
+    if (m >= 0 && m < S.nlit) S.f[k].dst[l * S.tile + c] = S.f[k].src[l * S.nlit + m];
+    else if (!S.f[k].keep) S.f[k].dst[l * S.tile + c] = S.f[k].dark;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@ module geosrad_gridcomp
    implicit none
    private
    public :: lw_driver_rrtmg, lw_driver_rrtmg_rats, lw_update_rats, lw_update_bands, sw_update_surface, sw_update_clouds, sw_update_cldhb, sw_driver_rrtmg, sw_driver_chou, lw_driver_chou, lw_chou_post, lw_update_flx, sw_update_export, rad_tendencies
-   public :: lit_index, lit_pack, lit_unpack
+   public :: lit_index, lit_pack, lit_unpack, sw_driver_rrtmg_lit, sw_driver_chou_lit
    public :: dev_alloc, dev_free, dev_put, dev_get, dev_sync
 
    ! ---- GEOSRAD_LWD_* ----
@@ -173,6 +173,27 @@ module geosrad_gridcomp
          type(c_ptr), intent(in) :: fin(*), fout(*)
          real(c_double), intent(in) :: consts(*)
          real, intent(in) :: hk_uv(*), hk_ir(*)
+      end function
+      integer(c_int) function geosrad_sw_driver_rrtmg_lit_dev(ctx, stream, ncol, nlit, lit_index, lit_pos, lm, nb_aer, fin, consts, iceflgsw, &
+            liqflgsw, sc, dist, isolvar, dyofyr, include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, dark, keep_mask, fout) &
+            bind(C, name='geosrad_sw_driver_rrtmg_lit_dev')
+         import :: c_int, c_ptr, c_double, c_int64_t
+         type(c_ptr), value :: ctx, stream, lit_index, lit_pos, bndsolvar, indsolvar
+         integer(c_int), value :: ncol, nlit, lm, nb_aer, iceflgsw, liqflgsw, isolvar, dyofyr, include_aerosols, lcldlm, lcldmh, normflx
+         real(c_double), value :: sc, dist
+         type(c_ptr), intent(in) :: fin(*), fout(*)
+         real(c_double), intent(in) :: consts(*), dark(*)
+         integer(c_int64_t), value :: keep_mask
+      end function
+      integer(c_int) function geosrad_sw_driver_chou_lit_dev(ctx, stream, ncol, nlit, lit_index, lit_pos, lm, fin, consts, lcldmh, lcldlm, &
+            hk_uv, hk_ir, do_drfband, dark, keep_mask, fout) bind(C, name='geosrad_sw_driver_chou_lit_dev')
+         import :: c_int, c_ptr, c_double, c_int64_t
+         type(c_ptr), value :: ctx, stream, lit_index, lit_pos
+         integer(c_int), value :: ncol, nlit, lm, lcldmh, lcldlm, do_drfband
+         type(c_ptr), intent(in) :: fin(*), fout(*)
+         real(c_double), intent(in) :: consts(*), dark(*)
+         real, intent(in) :: hk_uv(*), hk_ir(*)
+         integer(c_int64_t), value :: keep_mask
       end function
       integer(c_int) function geosrad_lw_driver_chou_dev(ctx, stream, ncol, lm, fin, consts, trace, lcldmh, lcldlm, binary_clouds, fout) &
             bind(C, name='geosrad_lw_driver_chou_dev')
@@ -420,6 +441,56 @@ contains
       rc = geosrad_sw_driver_chou_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(lm,c_int), fin, consts, int(lcldmh,c_int), &
             int(lcldlm,c_int), hk_uv_temp, hk_ir_temp, merge(1_c_int, 0_c_int, do_drfband), fout)
    end subroutine
+
+   ! The two branches of SORADCORE on the un-packed tile (`daytime = ZTH > 0.`, GEOS_SolarGridComp.F90:3686; PackIt :3839-3894 and
+   ! UnPackIt :6520-6580 happen inside the call): fin / fout are fields of all ncol = IM*JM columns, d_idx / d_pos / NumLit what lit_index
+   ! gave; dark(k) is UnPackIt's DEFAULT of output k (the internal spec's default, :6534), keep(k) leaves its dark columns alone (an InOut
+   ! internal, :6523-6524).  The aerosol imports are only read.
+   subroutine sw_driver_rrtmg_lit(ncol, NumLit, d_idx, d_pos, lm, nb_aer, fin, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr, &
+         include_aerosols, lcldlm, lcldmh, dark, keep, fout, rc)
+      integer, intent(in) :: ncol, NumLit, lm, nb_aer, iceflgsw, liqflgsw, isolvar, dyofyr, lcldlm, lcldmh
+      type(c_ptr), intent(in) :: d_idx, d_pos
+      logical, intent(in) :: include_aerosols
+      real, intent(in) :: sc, dist
+      type(c_ptr), intent(in) :: fin(SWD_NIN), fout(SWD_NOUT)
+      real(c_double), intent(in) :: consts(SWD_NCONST)
+      real, intent(in) :: dark(:)
+      logical, intent(in) :: keep(:)
+      integer, intent(out) :: rc
+      if (size(dark) /= SWD_NOUT .or. size(keep) /= SWD_NOUT) error stop 'sw_driver_rrtmg_lit: dark and keep have SWD_NOUT entries'
+      rc = geosrad_sw_driver_rrtmg_lit_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(NumLit,c_int), d_idx, d_pos, int(lm,c_int), &
+            int(nb_aer,c_int), fin, consts, int(iceflgsw,c_int), int(liqflgsw,c_int), real(sc,c_double), real(dist,c_double), &
+            int(isolvar,c_int), int(dyofyr,c_int), merge(1_c_int, 0_c_int, include_aerosols), int(lcldlm,c_int), int(lcldmh,c_int), 1_c_int, &
+            c_null_ptr, c_null_ptr, real(dark,c_double), keep_mask(keep), fout)
+   end subroutine
+   subroutine sw_driver_chou_lit(ncol, NumLit, d_idx, d_pos, lm, fin, consts, lcldmh, lcldlm, hk_uv_temp, hk_ir_temp, do_drfband, dark, keep, &
+         fout, rc)
+      integer, intent(in) :: ncol, NumLit, lm, lcldmh, lcldlm
+      type(c_ptr), intent(in) :: d_idx, d_pos
+      type(c_ptr), intent(in) :: fin(SWC_NIN), fout(SWC_NOUT)
+      real(c_double), intent(in) :: consts(SWC_NCONST)
+      real, intent(in) :: hk_uv_temp(5), hk_ir_temp(3,10)
+      logical, intent(in) :: do_drfband
+      real, intent(in) :: dark(:)
+      logical, intent(in) :: keep(:)
+      integer, intent(out) :: rc
+      if (size(dark) /= SWC_NOUT .or. size(keep) /= SWC_NOUT) error stop 'sw_driver_chou_lit: dark and keep have SWC_NOUT entries'
+      rc = load_chou_sw_tables()
+      if (rc /= 0) return
+      rc = geosrad_sw_driver_chou_lit_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(NumLit,c_int), d_idx, d_pos, int(lm,c_int), &
+            fin, consts, int(lcldmh,c_int), int(lcldlm,c_int), hk_uv_temp, hk_ir_temp, merge(1_c_int, 0_c_int, do_drfband), &
+            real(dark,c_double), keep_mask(keep), fout)
+   end subroutine
+   ! bit k - 1 of the mask = keep(k)
+   pure function keep_mask(keep) result(m)
+      logical, intent(in) :: keep(:)
+      integer(c_int64_t) :: m
+      integer :: k
+      m = 0
+      do k = 1, size(keep)
+         if (keep(k)) m = ibset(m, k - 1)
+      end do
+   end function
 
    ! sorad's coefficient tables (the reference keeps them as module data in sorad_constants / rad_constants), once per process
    integer function load_chou_sw_tables() result(rc)

@@ -630,6 +630,35 @@ int geosrad_lit_pack_dev(geosrad_ctx *ctx, void *stream, int pdim, int udim, int
 int geosrad_lit_unpack_dev(geosrad_ctx *ctx, void *stream, int pdim, int udim, int nlev, const int32_t *lit_pos, const void *packed,
                            void *unpacked, int use_default, double dflt);
 
+/* ---- the SW branch of SORADCORE on the un-packed tile ------------------------------------------------------------------
+ * geosrad_sw_driver_rrtmg_lit_dev / geosrad_sw_driver_chou_lit_dev: geosrad_sw_driver_rrtmg_dev / geosrad_sw_driver_chou_dev with
+ * SORADCORE's PackIt of every import (GEOS_SolarGridComp.F90:3839-3894) and UnPackIt(..., DEFAULT) of every result (:6520-6580,
+ * :7753-7799) inside: `in` and `out` (the same GEOSRAD_SWD_* / GEOSRAD_SWC_* orders) are fields of the whole tile, leading dimension
+ * ncol = IM*JM; lit_index / lit_pos / nlit are what geosrad_lit_index_dev returned for `daytime = ZTH > 0.` (:3686) and are trusted; the
+ * call does not synchronise.  The prep kernels read every import at column lit_index[m]; the solver runs on nlit columns with the
+ * workspace contents of the packed route, so on a lit column every output is bit for bit what geosrad_lit_pack_dev of every input, the
+ * packed driver and geosrad_lit_unpack_dev of every output give.  On a dark column output k receives dark[k] (host array in the output
+ * enum's order, converted to the real kind: UnPackIt's DEFAULT, the internal spec's default, :6534) unless bit k of keep_mask is set, in
+ * which case it keeps its value (an InOut internal, :6523-6524).  A NULL output stays "not associated".  With include_aerosols == 0 the
+ * RRTMG driver leaves CLD?S of the lit columns alone, as the packed driver does (:6405).
+ * The aerosol imports TAUA / SSAA / ASYA are READ ONLY here: the reference normalises its packed buffer (:6116-6125 act on BufInp), never
+ * the import, whereas geosrad_sw_driver_rrtmg_dev, which is handed that buffer, normalises it in place.
+ * The workspace is sized by nlit.  geosrad_set_chunk, the inhomogeneity and correlation-length settings, GEOSRAD_SW_PATH and
+ * geosrad_set_overcast apply as for the packed drivers.  nlit == 0: no solver kernel runs, the dark values are written, GEOSRAD_OK.
+ * GEOSRAD_EINVAL (GEOSRAD_EINPUT where the packed driver gives that), nothing launched: nlit < 0 or > ncol; lit_index or lit_pos NULL
+ * with nlit > 0; lit_pos or dark NULL while a requested output has its keep bit clear; whatever the packed driver or its solver rejects
+ * (isolvar == 1 for RRTMG).  The Chou-Suarez driver wants all of FSW .. FSWBAND (and DRBAND / DFBAND with do_drfband), like sorad; with
+ * do_drfband == 0 it neither writes nor fills DRBAND / DFBAND and asks nothing of their dark values. */
+int geosrad_sw_driver_rrtmg_lit_dev(geosrad_ctx *ctx, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos,
+                                    int lm, int nb_aer, const void *const *in, const double *consts, int iceflgsw, int liqflgsw, double sc,
+                                    double dist, int isolvar, int dyofyr, int include_aerosols, int lcldlm, int lcldmh, int normflx,
+                                    const void *bndsolvar, const void *indsolvar, const double *dark /*[GEOSRAD_SWD_NOUT]*/,
+                                    uint64_t keep_mask, void *const *out);
+int geosrad_sw_driver_chou_lit_dev(geosrad_ctx *ctx, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos,
+                                   int lm, const void *const *in, const double *consts, int lcldmh, int lcldlm, const void *hk_uv,
+                                   const void *hk_ir, int do_drfband, const double *dark /*[GEOSRAD_SWC_NOUT]*/, uint64_t keep_mask,
+                                   void *const *out);
+
 #ifdef __cplusplus
 }
 #endif
