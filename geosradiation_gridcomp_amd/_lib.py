@@ -26,6 +26,7 @@ EXPORTS = [
     "geosrad_read_table", "geosrad_rrtmg_sw_cldprmc", "geosrad_set_overcast", "geosrad_get_overcast", "geosrad_lit_index_dev", "geosrad_lit_pack_dev", "geosrad_lit_unpack_dev", "geosrad_dbg_fast64",
     "geosrad_rrtmg_sw_radval", "geosrad_rrtmg_sw_radval_dev",
     "geosrad_sw_driver_rrtmg_lit_dev", "geosrad_sw_driver_chou_lit_dev",
+    "geosrad_obio_weights", "geosrad_sw_update_obio_dev", "geosrad_sw_driver_rrtmg_obio_dev", "geosrad_sw_driver_rrtmg_obio_lit_dev",
 ]
 
 _lib = None

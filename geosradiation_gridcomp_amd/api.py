@@ -609,6 +609,47 @@ class Context:
         self._chk(self.L.geosrad_sw_update_export_dev(self.h, ctypes.c_void_p(stream), ci(ncol), ci(lm), ci(nbands),
                                                       self._ptr_array(G.SWU_IN, ptr), self._ptr_array(G.SWU_OUT, ptr)))
 
+    def sw_update_obio_dev(self, stream, ncol, scheme, slr, drbandn=None, dfbandn=None, drobio=None, dfobio=None, bands=None):
+        """SOLAR TO OBIO conversion of UPDATE_EXPORT (GEOS_SolarGridComp.F90:7584-7737): device addresses of SLR (ncol), DRBANDN / DFBANDN
+        (ncol,nbands) and the exports DROBIO / DFOBIO (ncol,33); None / 0 = not associated.  scheme: gridcomp.OBIO_CHOU | OBIO_RRTMG, or
+        OBIO_BANDS with bands = (wvn1, wvn2, order) as for obio_weights."""
+        nb, w1, w2, od = _obio_bands(scheme, bands)
+        v = lambda a: ctypes.c_void_p(a or None)
+        self._chk(self.L.geosrad_sw_update_obio_dev(self.h, ctypes.c_void_p(stream), ctypes.c_int(ncol), ctypes.c_int(int(scheme)), ctypes.c_int(nb),
+                                                    w1, w2, od, v(slr), v(drbandn), v(dfbandn), v(drobio), v(dfobio)))
+
+    def sw_driver_rrtmg_obio_dev(self, stream, ncol, lm, nb_aer, ptr, consts, iceflg, liqflg, sc, dist, isolvar, dyofyr, include_aerosols,
+                                 lcldlm, lcldmh, normflx=1, bndsolvar=None, indsolvar=None):
+        """sw_driver_rrtmg_dev that also returns the internals DRBANDN / DFBANDN of the ocean-biology coupling (GEOS_SolarGridComp.F90:6385,
+        :4148-4151): `ptr` may hold "DRBAND" and "DFBAND" (ncol,14), both or neither (gridcomp.SWD_OBIO_OUT)."""
+        from . import gridcomp as G
+        ci = ctypes.c_int
+        cs = (ctypes.c_double * len(G.SWD_CONST))(*consts)
+        bs = None if bndsolvar is None else np.ascontiguousarray(bndsolvar, dtype=self.dtype)
+        ins = None if indsolvar is None else np.ascontiguousarray(indsolvar, dtype=self.dtype)
+        self._chk(self.L.geosrad_sw_driver_rrtmg_obio_dev(
+            self.h, ctypes.c_void_p(stream), ci(ncol), ci(lm), ci(nb_aer), self._ptr_array(G.SWD_IN, ptr), cs, ci(iceflg), ci(liqflg),
+            ctypes.c_double(sc), ctypes.c_double(dist), ci(isolvar), ci(int(dyofyr)), ci(1 if include_aerosols else 0), ci(int(lcldlm)),
+            ci(int(lcldmh)), ci(normflx), None if bs is None else _p(bs), None if ins is None else _p(ins),
+            self._ptr_array(G.SWD_OUT, ptr), *[ctypes.c_void_p(ptr.get(k) or None) for k in G.SWD_OBIO_OUT]))
+
+    def sw_driver_rrtmg_obio_lit_dev(self, stream, ncol, nlit, lit_index, lit_pos, lm, nb_aer, ptr, consts, iceflg, liqflg, sc, dist, isolvar,
+                                     dyofyr, include_aerosols, lcldlm, lcldmh, normflx=1, bndsolvar=None, indsolvar=None, dark=None, keep=()):
+        """sw_driver_rrtmg_lit_dev with "DRBAND" / "DFBAND" as in sw_driver_rrtmg_obio_dev; dark / keep by name over gridcomp.SWD_OUT +
+        SWD_OBIO_OUT."""
+        from . import gridcomp as G
+        ci = ctypes.c_int
+        cs = (ctypes.c_double * len(G.SWD_CONST))(*consts)
+        bs = None if bndsolvar is None else np.ascontiguousarray(bndsolvar, dtype=self.dtype)
+        ins = None if indsolvar is None else np.ascontiguousarray(indsolvar, dtype=self.dtype)
+        li, lp, dk, mask = self._lit_args(G.SWD_OUT, lit_index, lit_pos, dark, [k for k in keep if k in G.SWD_OUT])
+        _, _, dko, masko = self._lit_args(G.SWD_OBIO_OUT, 0, 0, dark, [k for k in keep if k in G.SWD_OBIO_OUT])
+        self._chk(self.L.geosrad_sw_driver_rrtmg_obio_lit_dev(
+            self.h, ctypes.c_void_p(stream), ci(ncol), ci(nlit), li, lp, ci(lm), ci(nb_aer), self._ptr_array(G.SWD_IN, ptr), cs, ci(iceflg),
+            ci(liqflg), ctypes.c_double(sc), ctypes.c_double(dist), ci(isolvar), ci(int(dyofyr)), ci(1 if include_aerosols else 0),
+            ci(int(lcldlm)), ci(int(lcldmh)), ci(normflx), None if bs is None else _p(bs), None if ins is None else _p(ins), dk, mask,
+            self._ptr_array(G.SWD_OUT, ptr), dko, ci(masko.value), *[ctypes.c_void_p(ptr.get(k) or None) for k in G.SWD_OBIO_OUT]))
+
     def rad_tendencies_dev(self, stream, ncol, lm, grav, cp, ptr):
         """heating rates of the parent GridComp (GEOS_RadiationGridComp.F90:798-819)."""
         from . import gridcomp as G
@@ -685,3 +726,30 @@ class Context:
                                         ctypes.c_int(int(cloudLM)), ctypes.c_int(int(cloudMH)), _p(cldy), _p(cnt))
         self._chk(rc)
         return cnt
+
+
+def _obio_bands(scheme, bands):
+    """(nbands, wvn1, wvn2, order) ctypes arguments of geosrad_obio_weights / geosrad_sw_update_obio_dev"""
+    from . import gridcomp as G
+    if int(scheme) != G.OBIO_BANDS:
+        return G.OBIO_NBANDS.get(int(scheme), 0) if bands is None else int(bands), None, None, None
+    w1, w2, od = bands
+    nb = len(w1)
+    return (nb, (ctypes.c_double * nb)(*[float(x) for x in w1]), (ctypes.c_double * nb)(*[float(x) for x in w2]),
+            (ctypes.c_int32 * len(od))(*[int(x) for x in od]))
+
+
+def obio_weights(scheme, real_kind, bands=None):
+    """geosrad_obio_weights (no device, no context): the (nbands, 33) array of wavenumber-overlap fractions of the SOLAR TO OBIO conversion
+    (GEOS_SolarGridComp.F90:7665-7728), computed in real_kind and widened to float64, and the number of overlaps.  scheme: gridcomp.OBIO_CHOU
+    | OBIO_RRTMG | OBIO_BANDS; bands = (wvn1, wvn2, order) in cm-1 / 1-based for OBIO_BANDS (for a built-in scheme an int overrides nbands)."""
+    L = _lib.lib()
+    nb, w1, w2, od = _obio_bands(scheme, bands)
+    w = np.zeros((max(nb, 0), 33), dtype=np.float64)
+    npairs = ctypes.c_int32(0)
+    rc = L.geosrad_obio_weights(ctypes.c_int(int(scheme)), ctypes.c_int(int(real_kind)), ctypes.c_int(nb), w1, w2, od, _p(w), ctypes.byref(npairs))
+    if rc:
+        err = GeosradError(L.geosrad_last_error(None).decode())
+        err.rc = rc
+        raise err
+    return w, npairs.value

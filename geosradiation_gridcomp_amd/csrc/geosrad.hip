@@ -327,6 +327,12 @@ struct LitTile {
     const double *dark;
     uint64_t keep;
 };
+// DRBAND / DFBAND of geosrad_sw_driver_rrtmg_obio*_dev: the two arrays (both or none) and, on a tile, their dark values and keep bits
+struct SwdObio {
+    void *drband, *dfband;
+    const double *dark;
+    int keep;
+};
 
 // ---------------------------------------------------------------------------------------------------
 struct geosrad_ctx {
@@ -606,7 +612,7 @@ struct geosrad_ctx {
     virtual int sw_driver_dev(hipStream_t st, int ncol, int lm, int nb, const void *const *in, const double *consts, int iceflg,
                               int liqflg, double sc, double dist, int isolvar, int dyofyr, int include_aerosols, int lcldlm,
                               int lcldmh, int normflx, const void *bndsolvar, const void *indsolvar, void *const *out,
-                              const LitTile *lit) = 0;
+                              const LitTile *lit, const SwdObio *obio) = 0;
     virtual int lw_chou_post_dev(hipStream_t st, int ncol, int lm, const void *const *in, void *const *out) = 0;
     virtual int lw_driver_chou_dev(hipStream_t st, int ncol, int lm, const void *const *in, const double *consts, int trace, int lcldmh,
                                    int lcldlm, int binary_clouds, void *const *out) = 0;
@@ -619,6 +625,9 @@ struct geosrad_ctx {
                                     const void *tsinst, const void *ts_int, const void *olrb_int, const void *dolrb_int, void *olrb_exp,
                                     void *tbrb_exp) = 0;
     virtual int sw_update_export_dev(hipStream_t st, int ncol, int lm, int nbands, const void *const *in, void *const *out) = 0;
+    virtual int sw_update_obio_dev(hipStream_t st, int ncol, int scheme, int nbands, const double *wvn1, const double *wvn2,
+                                   const int32_t *order, const void *slr, const void *drbandn, const void *dfbandn, void *drobio,
+                                   void *dfobio) = 0;
     virtual int sw_update_surface_dev(hipStream_t st, int ncol, int lm, double undef, const void *const *in, void *const *out) = 0;
     virtual int sw_update_clouds_dev(hipStream_t st, int ncol, int lm, int lcldmh, int lcldlm, double taucrit, const double *consts,
                                      const void *const *in, void *const *out) = 0;
@@ -1353,11 +1362,29 @@ template <typename R> struct Ctx : geosrad_ctx {
 
     int sw_driver_dev(hipStream_t st, int ncol, int lm, int nb, const void *const *in, const double *consts, int iceflg, int liqflg,
                       double sc, double dist, int isolvar, int dyofyr, int include_aerosols, int lcldlm, int lcldmh, int normflx,
-                      const void *bndsolvar, const void *indsolvar, void *const *out, const LitTile *lit) override
+                      const void *bndsolvar, const void *indsolvar, void *const *out, const LitTile *lit, const SwdObio *obio) override
     {
         HIPCHK(hipSetDevice(device));
         if ((lit ? lit->tile : ncol) <= 0 || lm < 4 || nb < 0 || nb > 14) return fail(GEOSRAD_EINVAL, "bad ncol/lm/nb_aer");
         if (lit) if (const int rc = lit_check(*lit, ncol, out, GEOSRAD_SWD_NOUT)) return rc;
+        if (obio && !obio->drband != !obio->dfband) return fail(GEOSRAD_EINVAL, "DRBAND and DFBAND go together");
+        // do_drfband = SOLAR_TO_OBIO .and. include_aerosols (SOL:6385): without aerosols the two arrays are not touched at all
+        const bool drf = obio && obio->drband && include_aerosols != 0;
+        if (drf && lit && (obio->keep & 3) != 3 && (!lit->pos || !obio->dark))
+            return fail(GEOSRAD_EINVAL, "DRBAND / DFBAND with a clear keep bit need lit_pos and dark_obio");
+        // the tile's scatter list with DRBAND, DFBAND as outputs GEOSRAD_SWD_NOUT, + 1
+        enum { X_DRBAND = GEOSRAD_SWD_NOUT, X_DFBAND, X_NOUT };
+        void *xout[X_NOUT];
+        double xdark[X_NOUT];
+        LitTile xl{};
+        if (lit) {
+            xl = *lit;
+            for (int k = 0; k < GEOSRAD_SWD_NOUT; k++) { xout[k] = out[k]; xdark[k] = lit->dark ? lit->dark[k] : 0.0; }
+            xout[X_DRBAND] = drf ? obio->drband : nullptr; xout[X_DFBAND] = drf ? obio->dfband : nullptr;
+            for (int k = 0; k < 2; k++) xdark[X_DRBAND + k] = drf && obio->dark ? obio->dark[k] : 0.0;
+            xl.dark = xdark;
+            xl.keep = (lit->keep & ((1ull << GEOSRAD_SWD_NOUT) - 1)) | (drf ? (uint64_t)(obio->keep & 3) << GEOSRAD_SWD_NOUT : 0);
+        }
         // SORADCORE asserts the solar-variability options it supports before the call (GEOS_SolarGridComp.F90:6286-6292): no isolvar 1
         if (isolvar == 1) return fail(GEOSRAD_EINPUT, "SORADCORE: ISOLVAR == 1 is not supported by the GridComp (the solver entry point rrtmg_sw accepts it)");
         for (int k = 0; k < GEOSRAD_SWD_NIN; k++)
@@ -1377,12 +1404,13 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (lit && ncol == 0) {        // no daytime column: the dark fill alone
             LitFields F;
             for (int k = 0; k < GEOSRAD_SWD_NOUT; k++) F.push_back({k, nullptr, rows(k)});
-            return lit_scatter(st, *lit, 0, out, F);
+            if (drf) for (int k = X_DRBAND; k < X_NOUT; k++) F.push_back({k, nullptr, 14});
+            return lit_scatter(st, xl, 0, xout, F);
         }
         const size_t n = (size_t)ncol, cl = n * lm, cv = n * (lm + 1);
         const bool want_na = out[GEOSRAD_SWD_FSWNA] || out[GEOSRAD_SWD_FSCNA] || out[GEOSRAD_SWD_FSWUNA] || out[GEOSRAD_SWD_FSCUNA] ||
                              out[GEOSRAD_SWD_FSWBANDNA];
-        R *lay[13], *lev[2], *aerp[3], *flux[4], *scal[6], *cot[8], *band, *nflux[4] = {}, *nsc[14] = {}, *nband = nullptr, *col[6] = {};
+        R *lay[13], *lev[2], *aerp[3], *flux[4], *scal[6], *cot[8], *band, *nflux[4] = {}, *nsc[14] = {}, *nband = nullptr, *col[6] = {}, *drfb[2] = {};
         int32_t *cc;
         auto carve = [&](Carve c) {
             for (auto &q : lay) q = c.take<R>(cl);
@@ -1399,6 +1427,7 @@ template <typename R> struct Ctx : geosrad_ctx {
                 nband = c.take<R>(n * 14);
             }
             if (lit) for (auto &q : col) q = c.take<R>(n);      // the packed per-column imports the solver reads as they are
+            if (lit && drf) for (auto &q : drfb) q = c.take<R>(n * 14);      // DRBAND, DFBAND of the packed columns
             return c.off;
         };
         if (const int rc = drv_reserve(1, carve(Carve()))) return rc;
@@ -1444,6 +1473,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         for (int k = 0; k < 6; k++) sout[SO_NIRR + k] = direct(sc_ix[k], scal[k]);
         sout[SO_FSWBAND] = direct(GEOSRAD_SWD_FSWBAND, band);
         for (int k = 0; k < 8; k++) sout[SO_COT0 + k] = cot[k];      // cotd t/h/m/l then cotn t/h/m/l
+        if (drf) { sout[SO_DRBAND] = lit ? (void *)drfb[0] : obio->drband; sout[SO_DFBAND] = lit ? (void *)drfb[1] : obio->dfband; }
         // IAER = 10 always (SOL:6235; without aerosols the arrays are zero); super-layer indices flipped in the call (SOL:6341)
         void *nout[SO_NOUT] = {};
         if (want_na) {
@@ -1453,7 +1483,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             nout[SO_FSWBAND] = direct(GEOSRAD_SWD_FSWBANDNA, nband);
         }
         if (const int rc = sw_run(st, ncol, lm, sc, dist, isolvar, sin, iceflg, liqflg, dyofyr, 10, lm - lcldlm + 1, lm - lcldmh + 1,
-                                  normflx, cc, sout, 0, bndsolvar, indsolvar, nullptr, nullptr, want_na ? nout : nullptr)) return rc;
+                                  normflx, cc, sout, drf ? 1 : 0, bndsolvar, indsolvar, nullptr, nullptr, want_na ? nout : nullptr)) return rc;
         SwdPostLit<R> QL{};
         SwdPost<R> &Q = QL;
         Q.ncol = ncol; Q.lm = lm; Q.ngpt = NG_SW; Q.aerosols = include_aerosols; Q.undef = (R)consts[GEOSRAD_SWD_C_UNDEF];
@@ -1490,7 +1520,8 @@ template <typename R> struct Ctx : geosrad_ctx {
             for (int k = 0; k < 6; k++) F.push_back({sc_ix[k], scal[k], 1});
             F.push_back({GEOSRAD_SWD_FSWBAND, band, 14});
             if (want_na) F.push_back({GEOSRAD_SWD_FSWBANDNA, nband, 14});
-            if (const int rc = lit_scatter(st, *lit, ncol, out, F)) return rc;
+            if (drf) for (int k = 0; k < 2; k++) F.push_back({X_DRBAND + k, drfb[k], 14});
+            if (const int rc = lit_scatter(st, xl, ncol, xout, F)) return rc;
         }
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
@@ -1778,6 +1809,48 @@ template <typename R> struct Ctx : geosrad_ctx {
         const bool wide = wide16(ncol, {{in, GEOSRAD_SWU_NIN}, {out, GEOSRAD_SWU_NOUT}});
         if (wide) hipLaunchKernelGGL((k_sw_update_export<R, VW>), dim3(grid256(ncol / VW), lm + 1 + nbands), dim3(256), 0, st, U);
         else hipLaunchKernelGGL((k_sw_update_export<R, 1>), dim3(grid256(ncol), lm + 1 + nbands), dim3(256), 0, st, U);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+
+    // the walk of SOL:7665-7728 in R, as the list k_sw_update_obio takes
+    int obio_table(int scheme, int nbands, const double *wvn1, const double *wvn2, const int32_t *order, ObioUpd<R> &U)
+    {
+        R s1[OBIO_MAXBANDS], s2[OBIO_MAXBANDS];
+        int ord[OBIO_MAXBANDS], npairs = 0;
+        if (const char *e = obio_solar_bands<R>(scheme, nbands, wvn1, wvn2, order, s1, s2, ord)) return fail(GEOSRAD_EINVAL, e);
+        U.nbands = nbands;
+        for (int jb = 0; jb < nbands; jb++) { U.ib[jb] = ord[jb] - 1; U.np[jb] = 0; }
+        bool fed[NB_OBIO] = {};
+        const char *e = obio_walk<R>(nbands, s1, s2, ord, [&](int jb, int, int kb, R sfrac) {
+            if (npairs < OBIO_MAXPAIRS) { U.w[npairs] = sfrac; U.kb[npairs] = kb - 1; U.np[jb]++; fed[kb - 1] = true; }
+            npairs++;
+        });
+        if (e) return fail(GEOSRAD_EINVAL, e);
+        if (npairs > OBIO_MAXPAIRS) return fail(GEOSRAD_EINVAL, "SOLAR TO OBIO: more overlaps than two gapless band sets can have");
+        for (int p = 0; p < npairs; p++) if (p + 1 == npairs || U.kb[p + 1] != U.kb[p]) U.kb[p] |= 128;
+        for (int k = 0; k < NB_OBIO; k++) if (!fed[k]) U.zkb[U.nzero++] = k;
+        return GEOSRAD_OK;
+    }
+
+    int sw_update_obio_dev(hipStream_t st, int ncol, int scheme, int nbands, const double *wvn1, const double *wvn2, const int32_t *order,
+                           const void *slr, const void *drbandn, const void *dfbandn, void *drobio, void *dfobio) override
+    {
+        if (ncol < 1) return fail(GEOSRAD_EINVAL, "bad ncol");
+        ObioUpd<R> U{};
+        if (const int rc = obio_table(scheme, nbands, wvn1, wvn2, order, U)) return rc;
+        if (!drobio && !dfobio) return GEOSRAD_OK;
+        if (!slr || (drobio && !drbandn) || (dfobio && !dfbandn))
+            return fail(GEOSRAD_EINVAL, "an export was requested without the internal field it is computed from");
+        HIPCHK(hipSetDevice(device));
+        U.ncol = ncol; U.slr = (const R *)slr;
+        int nfam = 0;
+        if (drobio) { U.x[nfam] = (const R *)drbandn; U.y[nfam++] = (R *)drobio; }
+        if (dfobio) { U.x[nfam] = (const R *)dfbandn; U.y[nfam++] = (R *)dfobio; }
+        const void *ptrs[5] = {slr, U.x[0], U.y[0], U.x[nfam - 1], U.y[nfam - 1]};
+        const bool wide = wide16(ncol, {{ptrs, 5}});
+        if (wide) hipLaunchKernelGGL((k_sw_update_obio<R, VW>), dim3(grid256(ncol / VW), nfam), dim3(256), 0, st, U);
+        else hipLaunchKernelGGL((k_sw_update_obio<R, 1>), dim3(grid256(ncol), nfam), dim3(256), 0, st, U);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -2927,7 +3000,7 @@ struct MultiCtx final : geosrad_ctx {
     int lw_driver_dev(hipStream_t, int, int, int, const void *const *, const double *, int, int, int, int, int, const int32_t *, void *const *, int,
                       const int32_t *, void *const *) override { return nodev("geosrad_lw_driver_rrtmg_dev"); }
     int sw_driver_dev(hipStream_t, int, int, int, const void *const *, const double *, int, int, double, double, int, int, int, int, int, int,
-                      const void *, const void *, void *const *, const LitTile *lit) override
+                      const void *, const void *, void *const *, const LitTile *lit, const SwdObio *) override
     { return nodev(lit ? "geosrad_sw_driver_rrtmg_lit_dev" : "geosrad_sw_driver_rrtmg_dev"); }
     int lw_chou_post_dev(hipStream_t, int, int, const void *const *, void *const *) override { return nodev("geosrad_lw_chou_post_dev"); }
     int lw_driver_chou_dev(hipStream_t, int, int, const void *const *, const double *, int, int, int, int, void *const *) override { return nodev("geosrad_lw_driver_chou_dev"); }
@@ -2938,6 +3011,8 @@ struct MultiCtx final : geosrad_ctx {
     int lw_update_bands_dev(hipStream_t, int, const int32_t *, const double *, const double *, double, const void *, const void *, const void *,
                             const void *, void *, void *) override { return nodev("geosrad_lw_update_bands_dev"); }
     int sw_update_export_dev(hipStream_t, int, int, int, const void *const *, void *const *) override { return nodev("geosrad_sw_update_export_dev"); }
+    int sw_update_obio_dev(hipStream_t, int, int, int, const double *, const double *, const int32_t *, const void *, const void *, const void *,
+                           void *, void *) override { return nodev("geosrad_sw_update_obio_dev"); }
     int sw_update_surface_dev(hipStream_t, int, int, double, const void *const *, void *const *) override { return nodev("geosrad_sw_update_surface_dev"); }
     int sw_update_clouds_dev(hipStream_t, int, int, int, int, double, const double *, const void *const *, void *const *) override { return nodev("geosrad_sw_update_clouds_dev"); }
     int sw_update_cldhb_dev(hipStream_t, int, int, int, int, int, const double *, const void *const *, void *const *) override { return nodev("geosrad_sw_update_cldhb_dev"); }
@@ -3022,7 +3097,9 @@ int geosrad_create(geosrad_ctx **out, int device_id, int real_kind)
 }
 
 int geosrad_destroy(geosrad_ctx *c) { if (!c) return GEOSRAD_EINVAL; (void)hipSetDevice(c->device); delete c; return GEOSRAD_OK; }
-const char *geosrad_last_error(const geosrad_ctx *c) { return c ? c->last_error.c_str() : "null context"; }
+// ctx-less entry points (geosrad_obio_weights) leave their complaint here, per thread
+static thread_local std::string g_ctxless_error;
+const char *geosrad_last_error(const geosrad_ctx *c) { return c ? c->last_error.c_str() : g_ctxless_error.empty() ? "null context" : g_ctxless_error.c_str(); }
 int geosrad_real_kind(const geosrad_ctx *c) { return c ? c->real_kind : 0; }
 int geosrad_set_chunk(geosrad_ctx *c, int n)
 {
@@ -3375,7 +3452,7 @@ int geosrad_sw_driver_rrtmg_dev(geosrad_ctx *c, void *stream, int ncol, int lm, 
 {
     if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
     return c->sw_driver_dev((hipStream_t)stream, ncol, lm, nb_aer, in, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr,
-                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, nullptr);
+                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, nullptr, nullptr);
 }
 
 int geosrad_sw_driver_rrtmg_lit_dev(geosrad_ctx *c, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos, int lm,
@@ -3386,7 +3463,31 @@ int geosrad_sw_driver_rrtmg_lit_dev(geosrad_ctx *c, void *stream, int ncol, int 
     if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
     const LitTile lit{ncol, lit_index, lit_pos, dark, keep_mask};
     return c->sw_driver_dev((hipStream_t)stream, nlit, lm, nb_aer, in, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr,
-                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, &lit);
+                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, &lit, nullptr);
+}
+
+int geosrad_sw_driver_rrtmg_obio_dev(geosrad_ctx *c, void *stream, int ncol, int lm, int nb_aer, const void *const *in, const double *consts,
+                                     int iceflgsw, int liqflgsw, double sc, double dist, int isolvar, int dyofyr, int include_aerosols,
+                                     int lcldlm, int lcldmh, int normflx, const void *bndsolvar, const void *indsolvar, void *const *out,
+                                     void *drband, void *dfband)
+{
+    if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
+    const SwdObio obio{drband, dfband, nullptr, 0};
+    return c->sw_driver_dev((hipStream_t)stream, ncol, lm, nb_aer, in, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr,
+                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, nullptr, &obio);
+}
+
+int geosrad_sw_driver_rrtmg_obio_lit_dev(geosrad_ctx *c, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos,
+                                         int lm, int nb_aer, const void *const *in, const double *consts, int iceflgsw, int liqflgsw,
+                                         double sc, double dist, int isolvar, int dyofyr, int include_aerosols, int lcldlm, int lcldmh,
+                                         int normflx, const void *bndsolvar, const void *indsolvar, const double *dark, uint64_t keep_mask,
+                                         void *const *out, const double *dark_obio, int keep_obio, void *drband, void *dfband)
+{
+    if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
+    const LitTile lit{ncol, lit_index, lit_pos, dark, keep_mask};
+    const SwdObio obio{drband, dfband, dark_obio, keep_obio};
+    return c->sw_driver_dev((hipStream_t)stream, nlit, lm, nb_aer, in, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr,
+                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, &lit, &obio);
 }
 
 int geosrad_sw_driver_chou_dev(geosrad_ctx *c, void *stream, int ncol, int lm, const void *const *in, const double *consts, int lcldmh,
@@ -3444,6 +3545,35 @@ int geosrad_sw_update_export_dev(geosrad_ctx *c, void *stream, int ncol, int lm,
 {
     if (!c || !in || !out) return GEOSRAD_EINVAL;
     return c->sw_update_export_dev((hipStream_t)stream, ncol, lm, nbands, in, out);
+}
+
+int geosrad_obio_weights(int scheme, int real_kind, int nbands, const double *wvn1, const double *wvn2, const int32_t *order,
+                         double *weights, int32_t *npairs)
+{
+    auto run = [&](auto zero) -> const char * {
+        using T = decltype(zero);
+        T s1[OBIO_MAXBANDS], s2[OBIO_MAXBANDS];
+        int ord[OBIO_MAXBANDS], np = 0;
+        if (const char *e = obio_solar_bands<T>(scheme, nbands, wvn1, wvn2, order, s1, s2, ord)) return e;
+        if (weights) for (int k = 0; k < NB_OBIO * nbands; k++) weights[k] = 0.0;
+        const char *e = obio_walk<T>(nbands, s1, s2, ord, [&](int, int ib, int kb, T sfrac) {
+            if (weights) weights[(size_t)(ib - 1) * NB_OBIO + (kb - 1)] = (double)sfrac;
+            np++;
+        });
+        if (!e && npairs) *npairs = np;
+        return e;
+    };
+    const char *e = real_kind == 4 ? run(0.0f) : real_kind == 8 ? run(0.0) : "real_kind must be 4 or 8";
+    if (!e) return GEOSRAD_OK;
+    g_ctxless_error = e;
+    return GEOSRAD_EINVAL;
+}
+
+int geosrad_sw_update_obio_dev(geosrad_ctx *c, void *stream, int ncol, int scheme, int nbands, const double *wvn1, const double *wvn2,
+                               const int32_t *order, const void *slr, const void *drbandn, const void *dfbandn, void *drobio, void *dfobio)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    return c->sw_update_obio_dev((hipStream_t)stream, ncol, scheme, nbands, wvn1, wvn2, order, slr, drbandn, dfbandn, drobio, dfobio);
 }
 
 int geosrad_sw_update_surface_dev(geosrad_ctx *c, void *stream, int ncol, int lm, double undef, const void *const *in, void *const *out)

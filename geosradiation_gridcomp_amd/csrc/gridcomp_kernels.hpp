@@ -12,6 +12,7 @@
 //   k_lw_update_flx                      Update_Flx (IRR:3861-3999): the heartbeat linearisation of the LW fluxes in the surface
 //                                        temperature, every model step between two full calculations
 //   k_sw_update_export                   the 3-D / TOA / surface flux part of UPDATE_EXPORT (SOL:7540-7579): normalised fluxes x SLR
+//   k_sw_update_obio                     the SOLAR TO OBIO band conversion of UPDATE_EXPORT (SOL:7584-7737): DRBANDN / DFBANDN -> DROBIO / DFOBIO
 //   k_rad_tendencies                     the parent's heating rates (GEOS_RadiationGridComp.F90:798-819)
 // GEOS fields are (IM,JM,levels): column index fastest, which is the [level][column] layout of every kernel here (lane = column,
 // blockIdx.y = level): all accesses are coalesced, nothing is transposed, the vertical flip is an index calculation.
@@ -22,6 +23,7 @@
 #include "lw_device.hpp"
 #include "chou_kernels.hpp"      // gr_log10
 #include "sorad_kernels.hpp"     // SoradDev: the Chou-Suarez SW tables (caif, aib_uv, awb_uv, arb_uv)
+#include "obio_bands.hpp"        // NB_OBIO, OBIO_MAXBANDS, OBIO_MAXPAIRS
 
 namespace geosrad {
 
@@ -768,7 +770,7 @@ template <typename R> __global__ void __launch_bounds__(256) k_swd_post_lit(SwdP
 
 // UnPackIt (SOL:7776-7799) of every result a solver leaves as it is, in one launch: field k holds the rows f[k].row0 .. f[k + 1].row0 - 1 of
 // blockIdx.y; UnPacked(c, l) = Packed(pos[c], l) on a lit column, `dark` on a dark one unless `keep`.  One thread per (tile column, row).
-constexpr int LIT_NFIELD = 24;
+constexpr int LIT_NFIELD = 26;      // the 24 GEOSRAD_SWD_* outputs + DRBAND, DFBAND
 template <typename R> struct LitScatter {
     int tile, nlit, nf;
     const int32_t *pos;
@@ -1033,6 +1035,60 @@ template <typename R, int V> __global__ void __launch_bounds__(256) k_sw_update_
         VSET(U.rsrsna, ij, wna[v] * slr[v]);
         VSET(U.rscsna, ij, cna[v] * slr[v]);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// UPDATE_EXPORT, SOLAR TO OBIO conversion (SOL:7584-7737): the surface beam / diffuse fluxes of the solver's bands spread over the 33
+// ocean-biology bands in proportion to the wavenumber overlap, then x SLR.  The overlaps are a fixed list (obio_bands.hpp: the walk of
+// :7665-7728) that travels by value: `w`, `kb` in the walk's own order = solar bands in increasing wavenumber (position jb) and, within
+// one, OBIO bands in increasing wavenumber; both partitions are gapless, so the pairs of one OBIO band are consecutive and already in
+// the order the reference adds them.  Bit 7 of kb[p] marks the last pair of its OBIO band.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <typename R> struct ObioUpd {
+    int ncol, nbands, nzero;
+    const R *slr;                     // (IM,JM)
+    const R *x[2];                    // the requested of DRBANDN, DFBANDN (IM,JM,nbands) ...
+    R *y[2];                          // ... and their DROBIO, DFOBIO (IM,JM,33): blockIdx.y
+    R w[OBIO_MAXPAIRS];               // sfrac of pair p
+    int kb[OBIO_MAXPAIRS];            // its OBIO band, 0-based | 128 on the band's last pair
+    int ib[OBIO_MAXBANDS];            // SOLAR_band_number_in_wvn_order - 1 at position jb
+    int np[OBIO_MAXBANDS];            // pairs of that solar band
+    int zkb[NB_OBIO];                 // the nzero OBIO bands no solar band reaches: 0 * SLR
+};
+
+// One thread = V columns of one family.  Its nbands inputs are loaded once, all loads in flight together, into registers indexed by the
+// unrolled position jb; the pairs are then walked in a wave-uniform loop whose weights and indices are scalar loads from the arguments.
+// Per OBIO band: accumulator from zero, + x(ib) * sfrac in the reference's order, * SLR, one store (:7666-7734 without the read-modify-
+// write passes over DROBIO).
+template <typename R, int V> __global__ void __launch_bounds__(256) k_sw_update_obio(ObioUpd<R> U)
+{
+#pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
+    const int ij = (blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (ij >= U.ncol) return;
+    const int n = U.ncol, nb = U.nbands;
+    const R *__restrict__ xin = U.x[blockIdx.y];
+    R *__restrict__ out = U.y[blockIdx.y];
+    R slr[V], acc[V], x[OBIO_MAXBANDS][V];
+    ldv<R, V>(U.slr, ij, slr);
+#pragma unroll
+    for (int jb = 0; jb < OBIO_MAXBANDS; jb++)
+        if (jb < nb) ldv<R, V>(xin, (size_t)U.ib[jb] * n + ij, x[jb]);
+    VFOR acc[v] = 0;
+    int p = 0;
+#pragma unroll
+    for (int jb = 0; jb < OBIO_MAXBANDS; jb++) {
+        const int e = jb < nb ? p + U.np[jb] : p;
+        for (; p < e; p++) {
+            const R w = U.w[p];
+            const int k = U.kb[p];
+            VFOR acc[v] = acc[v] + x[jb][v] * w;
+            if (k & 128) {
+                VSET(out, (size_t)(k & 127) * n + ij, acc[v] * slr[v]);
+                VFOR acc[v] = 0;
+            }
+        }
+    }
+    for (int z = 0; z < U.nzero; z++) VSET(out, (size_t)U.zkb[z] * n + ij, (R)0 * slr[v]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

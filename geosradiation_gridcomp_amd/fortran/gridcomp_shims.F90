@@ -10,6 +10,9 @@ module geosrad_gridcomp
    private
    public :: lw_driver_rrtmg, lw_driver_rrtmg_rats, lw_update_rats, lw_update_bands, sw_update_surface, sw_update_clouds, sw_update_cldhb, sw_driver_rrtmg, sw_driver_chou, lw_driver_chou, lw_chou_post, lw_update_flx, sw_update_export, rad_tendencies
    public :: lit_index, lit_pack, lit_unpack, sw_driver_rrtmg_lit, sw_driver_chou_lit
+   public :: sw_update_obio, sw_driver_rrtmg_obio, sw_driver_rrtmg_obio_lit
+   ! ocean-biology coupling (SOLAR_TO_OBIO): the schemes of sw_update_obio (GEOSRAD_OBIO_*) and the number of OBIO bands
+   integer, parameter, public :: OBIO_CHOU = 0, OBIO_RRTMG = 1, OBIO_BANDS = 2, NB_OBIO = 33
    public :: dev_alloc, dev_free, dev_put, dev_get, dev_sync
 
    ! ---- GEOSRAD_LWD_* ----
@@ -184,6 +187,33 @@ module geosrad_gridcomp
          type(c_ptr), intent(in) :: fin(*), fout(*)
          real(c_double), intent(in) :: consts(*), dark(*)
          integer(c_int64_t), value :: keep_mask
+      end function
+      integer(c_int) function geosrad_sw_driver_rrtmg_obio_dev(ctx, stream, ncol, lm, nb_aer, fin, consts, iceflgsw, liqflgsw, sc, dist, isolvar, &
+            dyofyr, include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, fout, drband, dfband) &
+            bind(C, name='geosrad_sw_driver_rrtmg_obio_dev')
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: ctx, stream, bndsolvar, indsolvar, drband, dfband
+         integer(c_int), value :: ncol, lm, nb_aer, iceflgsw, liqflgsw, isolvar, dyofyr, include_aerosols, lcldlm, lcldmh, normflx
+         real(c_double), value :: sc, dist
+         type(c_ptr), intent(in) :: fin(*), fout(*)
+         real(c_double), intent(in) :: consts(*)
+      end function
+      integer(c_int) function geosrad_sw_driver_rrtmg_obio_lit_dev(ctx, stream, ncol, nlit, lit_index, lit_pos, lm, nb_aer, fin, consts, &
+            iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr, include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, dark, keep_mask, &
+            fout, dark_obio, keep_obio, drband, dfband) bind(C, name='geosrad_sw_driver_rrtmg_obio_lit_dev')
+         import :: c_int, c_ptr, c_double, c_int64_t
+         type(c_ptr), value :: ctx, stream, lit_index, lit_pos, bndsolvar, indsolvar, drband, dfband
+         integer(c_int), value :: ncol, nlit, lm, nb_aer, iceflgsw, liqflgsw, isolvar, dyofyr, include_aerosols, lcldlm, lcldmh, normflx, keep_obio
+         real(c_double), value :: sc, dist
+         type(c_ptr), intent(in) :: fin(*), fout(*)
+         real(c_double), intent(in) :: consts(*), dark(*), dark_obio(*)
+         integer(c_int64_t), value :: keep_mask
+      end function
+      integer(c_int) function geosrad_sw_update_obio_dev(ctx, stream, ncol, scheme, nbands, wvn1, wvn2, order, slr, drbandn, dfbandn, drobio, &
+            dfobio) bind(C, name='geosrad_sw_update_obio_dev')
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx, stream, wvn1, wvn2, order, slr, drbandn, dfbandn, drobio, dfobio
+         integer(c_int), value :: ncol, scheme, nbands
       end function
       integer(c_int) function geosrad_sw_driver_chou_lit_dev(ctx, stream, ncol, nlit, lit_index, lit_pos, lm, fin, consts, lcldmh, lcldlm, &
             hk_uv, hk_ir, do_drfband, dark, keep_mask, fout) bind(C, name='geosrad_sw_driver_chou_lit_dev')
@@ -463,6 +493,40 @@ contains
             int(isolvar,c_int), int(dyofyr,c_int), merge(1_c_int, 0_c_int, include_aerosols), int(lcldlm,c_int), int(lcldmh,c_int), 1_c_int, &
             c_null_ptr, c_null_ptr, real(dark,c_double), keep_mask(keep), fout)
    end subroutine
+   ! sw_driver_rrtmg / sw_driver_rrtmg_lit of a GEOS build with ocean biology (USE_OCEANOBIOGEOCHEM: 1 -> SOLAR_TO_OBIO): the same call that
+   ! also fills the internals DRBANDN / DFBANDN (IM,JM,14) (GEOS_SolarGridComp.F90:778-796, :4148-4151), rrtmg_sw being called with
+   ! do_drfband = SOLAR_TO_OBIO .and. include_aerosols (:6385); without aerosols the two arrays are left as they are.  On the tile
+   ! dark_obio(2) / keep_obio(2) are the DEFAULT and the keep flag of DRBAND, DFBAND.
+   subroutine sw_driver_rrtmg_obio(ncol, lm, nb_aer, fin, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr, include_aerosols, lcldlm, &
+         lcldmh, fout, drband, dfband, rc)
+      integer, intent(in) :: ncol, lm, nb_aer, iceflgsw, liqflgsw, isolvar, dyofyr, lcldlm, lcldmh
+      logical, intent(in) :: include_aerosols
+      real, intent(in) :: sc, dist
+      type(c_ptr), intent(in) :: fin(SWD_NIN), fout(SWD_NOUT), drband, dfband
+      real(c_double), intent(in) :: consts(SWD_NCONST)
+      integer, intent(out) :: rc
+      rc = geosrad_sw_driver_rrtmg_obio_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(lm,c_int), int(nb_aer,c_int), fin, consts, &
+            int(iceflgsw,c_int), int(liqflgsw,c_int), real(sc,c_double), real(dist,c_double), int(isolvar,c_int), int(dyofyr,c_int), &
+            merge(1_c_int, 0_c_int, include_aerosols), int(lcldlm,c_int), int(lcldmh,c_int), 1_c_int, c_null_ptr, c_null_ptr, fout, drband, dfband)
+   end subroutine
+   subroutine sw_driver_rrtmg_obio_lit(ncol, NumLit, d_idx, d_pos, lm, nb_aer, fin, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr, &
+         include_aerosols, lcldlm, lcldmh, dark, keep, fout, dark_obio, keep_obio, drband, dfband, rc)
+      integer, intent(in) :: ncol, NumLit, lm, nb_aer, iceflgsw, liqflgsw, isolvar, dyofyr, lcldlm, lcldmh
+      type(c_ptr), intent(in) :: d_idx, d_pos
+      logical, intent(in) :: include_aerosols
+      real, intent(in) :: sc, dist
+      type(c_ptr), intent(in) :: fin(SWD_NIN), fout(SWD_NOUT), drband, dfband
+      real(c_double), intent(in) :: consts(SWD_NCONST)
+      real, intent(in) :: dark(:), dark_obio(2)
+      logical, intent(in) :: keep(:), keep_obio(2)
+      integer, intent(out) :: rc
+      if (size(dark) /= SWD_NOUT .or. size(keep) /= SWD_NOUT) error stop 'sw_driver_rrtmg_obio_lit: dark and keep have SWD_NOUT entries'
+      rc = geosrad_sw_driver_rrtmg_obio_lit_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(NumLit,c_int), d_idx, d_pos, &
+            int(lm,c_int), int(nb_aer,c_int), fin, consts, int(iceflgsw,c_int), int(liqflgsw,c_int), real(sc,c_double), real(dist,c_double), &
+            int(isolvar,c_int), int(dyofyr,c_int), merge(1_c_int, 0_c_int, include_aerosols), int(lcldlm,c_int), int(lcldmh,c_int), 1_c_int, &
+            c_null_ptr, c_null_ptr, real(dark,c_double), keep_mask(keep), fout, real(dark_obio,c_double), int(keep_mask(keep_obio),c_int), &
+            drband, dfband)
+   end subroutine
    subroutine sw_driver_chou_lit(ncol, NumLit, d_idx, d_pos, lm, fin, consts, lcldmh, lcldlm, hk_uv_temp, hk_ir_temp, do_drfband, dark, keep, &
          fout, rc)
       integer, intent(in) :: ncol, NumLit, lm, lcldmh, lcldlm
@@ -550,6 +614,16 @@ contains
    end subroutine
 
    ! flux part of UPDATE_EXPORT (GEOS_SolarGridComp.F90:7540-7579)
+   ! SOLAR TO OBIO conversion of UPDATE_EXPORT (GEOS_SolarGridComp.F90:7584-7737) for the RRTMG (scheme = OBIO_RRTMG, nbands = 14) and
+   ! Chou-Suarez (OBIO_CHOU, 8) bands: d_slr = SLR (IM,JM), d_drbandn / d_dfbandn = DRBANDN / DFBANDN (IM,JM,nbands), d_drobio / d_dfobio =
+   ! DROBIO / DFOBIO (IM,JM,33); c_null_ptr = not associated
+   subroutine sw_update_obio(ncol, scheme, nbands, d_slr, d_drbandn, d_dfbandn, d_drobio, d_dfobio)
+      integer, intent(in) :: ncol, scheme, nbands
+      type(c_ptr), intent(in) :: d_slr, d_drbandn, d_dfbandn, d_drobio, d_dfobio
+      if (geosrad_sw_update_obio_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(scheme,c_int), int(nbands,c_int), c_null_ptr, &
+            c_null_ptr, c_null_ptr, d_slr, d_drbandn, d_dfbandn, d_drobio, d_dfobio) /= 0) call geosrad_fail('UPDATE_EXPORT (SOLAR TO OBIO)')
+   end subroutine
+
    subroutine sw_update_export(ncol, lm, nbands, fin, fout)
       integer, intent(in) :: ncol, lm, nbands
       type(c_ptr), intent(in) :: fin(SWU_NIN), fout(SWU_NOUT)

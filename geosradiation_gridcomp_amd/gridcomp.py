@@ -76,6 +76,19 @@ SWHB_IN = ["FCLD", "PLE", "T", "QI", "QL", "LATS"]
 SWHB_CONST = ["GRAV", "RGAS"]
 SWHB_OUT = ["CLDTT", "CLDHI", "CLDMD", "CLDLO"]
 
+# ocean-biology coupling (SOLAR_TO_OBIO): the two arrays the geosrad_sw_driver_rrtmg_obio*_dev entry points add to SWD_OUT (SOL:4148-4151),
+# the schemes of geosrad_obio_weights / geosrad_sw_update_obio_dev (GEOSRAD_OBIO_*) and the SOLAR TO OBIO conversion (SOL:7584-7737)
+SWD_OBIO_OUT = ["DRBAND", "DFBAND"]
+OBIO_CHOU, OBIO_RRTMG, OBIO_BANDS = 0, 1, 2
+NB_OBIO = 33
+OBIO_NBANDS = {OBIO_CHOU: 8, OBIO_RRTMG: 14}
+SWO_IN = ["SLR", "DRBANDN", "DFBANDN"]
+SWO_OUT = ["DROBIO", "DFOBIO"]
+# rrsw_wvn: wavenum1 / wavenum2 (16:29) of RRTMG_SW [cm-1] (rrtmg_sw_init.F90:187-190) and their order in increasing wavenumber (SOL:7643-7644)
+SW_WAVENUM1 = [2600., 3250., 4000., 4650., 5150., 6150., 7700., 8050., 12850., 16000., 22650., 29000., 38000., 820.]
+SW_WAVENUM2 = [3250., 4000., 4650., 5150., 6150., 7700., 8050., 12850., 16000., 22650., 29000., 38000., 50000., 2600.]
+SW_WVN_ORDER = [14] + list(range(1, 14))
+
 # MAPL_Constants (not in the reference repository): defaults only
 MAPL = {"AIRMW": 28.965, "H2OMW": 18.015, "O3MW": 47.9982, "RUNIV": 8314.47, "GRAV": 9.80665, "CP": 1004.6830, "UNDEF": 1.0e15}
 MAPL["RGAS"] = MAPL["RUNIV"] / MAPL["AIRMW"]

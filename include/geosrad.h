@@ -552,6 +552,38 @@ enum { GEOSRAD_SWU_FSW, GEOSRAD_SWU_FSC, GEOSRAD_SWU_FSWNA, GEOSRAD_SWU_FSCNA, G
 int geosrad_sw_update_export_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm, int nbands, const void *const *in,
                                  void *const *out);
 
+/* ---- the ocean-biology coupling (USE_OCEANOBIOGEOCHEM: 1 -> SOLAR_TO_OBIO) ---------------------------------------------------------
+ * geosrad_obio_weights: the band bookkeeping of UPDATE_EXPORT's SOLAR TO OBIO conversion (GEOS_SolarGridComp.F90:7584-7737) on the host;
+ * no device and no context are needed (ctx-less: geosrad_last_error(NULL) gives this thread's last complaint).  The solver's bands are
+ * walked together with the 33 OBIO bands (OBIO_bands_nm, :6794-6835; OBIO_bands_wavenum = 1.e7 / OBIO_bands_nm(2:1:-1,:)) in increasing
+ * wavenumber (:7665-7728, with its early exits, the kb_start carry and both continuity checks); every overlapping pair contributes
+ * sfrac = (min(swvn2,owvn2) - max(swvn1,owvn1)) / (swvn2 - swvn1).  Every operation is made in real_kind (4 float, 8 double).
+ *   scheme GEOSRAD_OBIO_RRTMG: rrsw_wvn's wavenum1/2(16:29), order 14, 1..13 (:7636-7648); nbands must be 14
+ *          GEOSRAD_OBIO_CHOU : 1.e7 / CHOU_bands_nm (:6838-6847, band 2 = 285-300 nm), order 8..1 (:7652-7661); nbands must be 8
+ *          GEOSRAD_OBIO_BANDS: the caller's limits wvn1 / wvn2 [cm-1] (nbands) and `order`, the 1-based band numbers in increasing
+ *                              wavenumber (what the RRTMGP branch takes from its k-distribution, :7624-7628); 1 <= nbands <= 16
+ *   For the two built-in schemes wvn1 / wvn2 / order are ignored and may be NULL.
+ *   weights (33, nbands), OBIO band fastest: sfrac of the pair in real_kind widened to double, 0 where the bands do not overlap;
+ *   npairs: the number of overlaps (46 for RRTMG, 39 for Chou-Suarez).  Either may be NULL.
+ * GEOSRAD_EINVAL with the reference's text where it asserts ('SOLAR bands not complete and unique!', 'OBIO bands not complete and
+ * unique!'), and for a bad scheme / real_kind / nbands, wvn1 >= wvn2, or an `order` that is no permutation of 1..nbands. */
+enum { GEOSRAD_OBIO_CHOU, GEOSRAD_OBIO_RRTMG, GEOSRAD_OBIO_BANDS };
+enum { GEOSRAD_NB_OBIO = 33, GEOSRAD_OBIO_MAXBANDS = 16 };
+int geosrad_obio_weights(int scheme, int real_kind, int nbands, const double *wvn1, const double *wvn2, const int32_t *order,
+                         double *weights /* (33, nbands), OBIO band fastest */, int32_t *npairs);
+
+/* geosrad_sw_update_obio_dev: the conversion itself (GEOS_SolarGridComp.F90:7584-7737), every model step over all columns:
+ * DROBIO(:,:,kb) = SLR * sum over the overlapping solar bands ib, in increasing wavenumber, of DRBANDN(:,:,ib) * sfrac, the accumulator
+ * starting from zero (:7666-7667, :7719-7720, :7731-7734); DFOBIO likewise from DFBANDN.  Bit for bit the Fortran statements without
+ * contraction.  scheme / nbands / wvn1 / wvn2 / order (host) as for geosrad_obio_weights.  slr (ncol), drbandn / dfbandn (ncol,nbands)
+ * as the drivers return DRBAND / DFBAND, drobio / dfobio (ncol,33): device pointers of the context's real kind.  A NULL output is "not
+ * associated" and skipped; with both NULL nothing is launched and the call returns GEOSRAD_OK.  No solver tables are needed; the call does
+ * not synchronise.  GEOSRAD_EINVAL, nothing launched: slr or the matching input NULL while its output is requested, ncol < 1, or anything
+ * geosrad_obio_weights rejects. */
+int geosrad_sw_update_obio_dev(geosrad_ctx *ctx, void *stream, int ncol, int scheme, int nbands, const double *wvn1, const double *wvn2,
+                               const int32_t *order, const void *slr, const void *drbandn, const void *dfbandn, void *drobio,
+                               void *dfobio);
+
 /* geosrad_sw_update_surface_dev: the 2-D block of UPDATE_EXPORT above the flux part (GEOS_SolarGridComp.F90:7403-7533): the four
  * albedo exports (import where SLR > 0, else MAPL_UNDEF), the total surface albedo ALB / ALBEDO (:7458-7465), the incident and
  * surface fluxes SLRTP, DR/DF UVR PAR NIR, the normal-incidence DRN*, SLRSF*, SLRSUF* (with SLN = SLR / ZTH where ZTH > 0, :6877-6881).
@@ -658,6 +690,26 @@ int geosrad_sw_driver_chou_lit_dev(geosrad_ctx *ctx, void *stream, int ncol, int
                                    int lm, const void *const *in, const double *consts, int lcldmh, int lcldlm, const void *hk_uv,
                                    const void *hk_ir, int do_drfband, const double *dark /*[GEOSRAD_SWC_NOUT]*/, uint64_t keep_mask,
                                    void *const *out);
+
+/* geosrad_sw_driver_rrtmg_obio_dev / geosrad_sw_driver_rrtmg_obio_lit_dev: geosrad_sw_driver_rrtmg_dev / geosrad_sw_driver_rrtmg_lit_dev
+ * with the per-band surface beam and diffuse fluxes a coupled ocean biology needs, the internals DRBANDN / DFBANDN
+ * (GEOS_SolarGridComp.F90:778-796, :4148-4151): drband / dfband (ncol,14), fractions of the TOA insolation like FSWBAND, both given or both
+ * NULL (else GEOSRAD_EINVAL; both NULL = the plain driver).  When they are given and include_aerosols != 0 the with-aerosol rrtmg_sw call
+ * runs with do_drfband = SOLAR_TO_OBIO .and. include_aerosols (:6385) and writes them; with include_aerosols == 0 the two arrays are left
+ * untouched on lit and dark columns alike (the reference does not compute them in its no-aerosol call, :4010-4016).  The no-aerosol second
+ * pass never computes them.  Every output of `out` is bit for bit what the plain entry point returns.  On the tile: dark_obio[2] (host) are
+ * UnPackIt's DEFAULTs of DRBAND, DFBAND; bits 0, 1 of keep_obio make their dark columns keep their values; dark_obio may be NULL when both
+ * bits are set. */
+int geosrad_sw_driver_rrtmg_obio_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm, int nb_aer, const void *const *in,
+                                     const double *consts, int iceflgsw, int liqflgsw, double sc, double dist, int isolvar, int dyofyr,
+                                     int include_aerosols, int lcldlm, int lcldmh, int normflx, const void *bndsolvar,
+                                     const void *indsolvar, void *const *out, void *drband, void *dfband);
+int geosrad_sw_driver_rrtmg_obio_lit_dev(geosrad_ctx *ctx, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos,
+                                         int lm, int nb_aer, const void *const *in, const double *consts, int iceflgsw, int liqflgsw,
+                                         double sc, double dist, int isolvar, int dyofyr, int include_aerosols, int lcldlm, int lcldmh,
+                                         int normflx, const void *bndsolvar, const void *indsolvar, const double *dark /*[GEOSRAD_SWD_NOUT]*/,
+                                         uint64_t keep_mask, void *const *out, const double *dark_obio /*[2]*/,
+                                         int keep_obio /*bit 0 DRBAND, bit 1 DFBAND*/, void *drband, void *dfband);
 
 #ifdef __cplusplus
 }
