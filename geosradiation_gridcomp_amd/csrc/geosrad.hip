@@ -577,73 +577,59 @@ struct geosrad_ctx {
     virtual size_t workspace_bytes() const = 0;
     // RATS diagnostics of LW_Driver (GEOS_IrradGridComp.F90:3405-3468): total-sky profiles with one gas removed, per gas
     struct LwRats { int n; int gas[GEOSRAD_RAT_NGAS]; void *uflx, *dflx, *duflx_dTs; };      // outputs [n][nlay+1][ncol]
-    virtual int lw_dev(hipStream_t st, int ncol, int nlay, int dudTs, const void *const *in, int iceflg, int liqflg, int dyofyr,
-                       int cloudLM, int cloudMH, int32_t *clearCounts, void *const *out, const int32_t *band_output,
-                       void *dbg_taug, void *dbg_pfracs, const LwRats *rats) = 0;
+    // The `_dev` entry points: device pointers belong to ONE device, so a context that is not a single device's refuses them.  Arguments as
+    // in include/geosrad.h after the stream (solvers: as their *_host twin; lw_dev ends dbg_taug, dbg_pfracs, rats).
+    int nodev(const char *what) { return fail(GEOSRAD_EINVAL, std::string(what) + ": device-pointer entry points need a single-device context (geosrad_create)"); }
+    using In = const void *const *; using Out = void *const *;
+    virtual int lw_dev(hipStream_t, int, int, int, In, int, int, int, int, int, int32_t *, Out, const int32_t *, void *, void *, const LwRats *)
+    { return nodev("geosrad_rrtmg_lw_dev"); }
     virtual int lw_host(int ncol, int nlay, int dudTs, const void *const *in, int iceflg, int liqflg, int dyofyr, int cloudLM,
                         int cloudMH, int32_t *clearCounts, void *const *out, const int32_t *band_output, void *taug,
                         void *pfracs) = 0;
     virtual int mcica_host(int ncol, int nsubcol, int nlay, const void *zmid, const void *alat, int doy, const void *play,
                            const void *cldfrac, const void *ciwp, const void *clwp, double cwp_tiny, const int32_t *so,
                            int32_t *cldy, void *ciwp_s, void *clwp_s) = 0;
-    virtual int mcica_dev(hipStream_t st, int ncol, int nsubcol, int nlay, const void *zmid, const void *alat, int doy, const void *play,
-                          const void *cldfrac, const void *ciwp, const void *clwp, double cwp_tiny, const int32_t *so,
-                          int32_t *cldy, void *ciwp_s, void *clwp_s) = 0;
+    virtual int mcica_dev(hipStream_t, int, int, int, const void *, const void *, int, const void *, const void *, const void *, const void *, double,
+                          const int32_t *, int32_t *, void *, void *) { return nodev("geosrad_mcica_dev"); }
     virtual int check(hipStream_t st, int which = -1) = 0;      // which: -1 either solver's assertions, 0 RRTMG_LW (+ McICA), 1 RRTMG_SW
     virtual int set_tables_sw(const void *blob, size_t n) = 0;
     virtual int set_tables_chou_lw(const void *blob, size_t n) = 0;
     virtual int set_tables_chou_sw(const void *blob, size_t n) = 0;
-    virtual int sorad_dev(hipStream_t st, int m, int np, int nb, const void *const *in, double co2, int ict, int icb, const void *hk_uv,
-                          const void *hk_ir, void *const *out, int do_drfband) = 0;
+    virtual int sorad_dev(hipStream_t, int, int, int, In, double, int, int, const void *, const void *, Out, int) { return nodev("geosrad_sorad_dev"); }
     virtual int sorad_host(int m, int np, int nb, const void *const *in, double co2, int ict, int icb, const void *hk_uv, const void *hk_ir,
                            void *const *out, int do_drfband) = 0;
-    virtual int irrad_dev(hipStream_t st, int m, int np, const void *const *in, double co2, int trace, int ict, int icb, int ns, int na,
-                          int nb, void *const *aer, void *const *out) = 0;
+    virtual int irrad_dev(hipStream_t, int, int, In, double, int, int, int, int, int, int, Out, Out) { return nodev("geosrad_irrad_dev"); }
     virtual int irrad_host(int m, int np, const void *const *in, double co2, int trace, int ict, int icb, int ns, int na, int nb,
                            void *const *aer, void *const *out) = 0;
-    virtual int sw_dev(hipStream_t st, int ncol, int nlay, double scon, double adjes, int isolvar, const void *const *in, int iceflg,
-                       int liqflg, int dyofyr, int iaer, int cloudLM, int cloudMH, int normFlx, int32_t *clearCounts, void *const *out,
-                       int do_drfband, const void *bndscl, const void *indsolvar, const void *solcycfrac,
-                       void *const *dbg, void *radval) = 0;
-    virtual int lw_driver_dev(hipStream_t st, int ncol, int lm, int nb, const void *const *in, const double *consts, int iceflg,
-                              int liqflg, int doy, int lcldlm, int lcldmh, const int32_t *band_output, void *const *out, int nrats,
-                              const int32_t *rat_gas, void *const *rat_out) = 0;
+    virtual int sw_dev(hipStream_t, int, int, double, double, int, In, int, int, int, int, int, int, int, int32_t *, Out, int, const void *, const void *,
+                       const void *, Out, void *) { return nodev("geosrad_rrtmg_sw_dev"); }
+    virtual int lw_driver_dev(hipStream_t, int, int, int, In, const double *, int, int, int, int, int, const int32_t *, Out, int, const int32_t *, Out)
+    { return nodev("geosrad_lw_driver_rrtmg_dev"); }      // ... out, nrats, rat_gas, rat_out
     // lit != nullptr (both SW drivers): `in` / `out` are the un-packed tile's and ncol is NumLit (geosrad_sw_driver_*_lit_dev)
-    virtual int sw_driver_dev(hipStream_t st, int ncol, int lm, int nb, const void *const *in, const double *consts, int iceflg,
-                              int liqflg, double sc, double dist, int isolvar, int dyofyr, int include_aerosols, int lcldlm,
-                              int lcldmh, int normflx, const void *bndsolvar, const void *indsolvar, void *const *out,
-                              const LitTile *lit, const SwdObio *obio) = 0;
-    virtual int lw_chou_post_dev(hipStream_t st, int ncol, int lm, const void *const *in, void *const *out) = 0;
-    virtual int lw_driver_chou_dev(hipStream_t st, int ncol, int lm, const void *const *in, const double *consts, int trace, int lcldmh,
-                                   int lcldlm, int binary_clouds, void *const *out) = 0;
-    virtual int sw_driver_chou_dev(hipStream_t st, int ncol, int lm, const void *const *in, const double *consts, int lcldmh, int lcldlm,
-                                   const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out, const LitTile *lit) = 0;
-    virtual int lw_update_flx_dev(hipStream_t st, int ncol, int lm, int rrtmg, int lev_mid_high, int lev_low_mid, double undef,
-                                  const void *const *in, void *const *out) = 0;
-    virtual int lw_update_rats_dev(hipStream_t st, int ncol, int lm, int nrats, const void *const *in, void *const *out) = 0;
-    virtual int lw_update_bands_dev(hipStream_t st, int ncol, const int32_t *band_output, const double *wn1, const double *wn2, double undef,
-                                    const void *tsinst, const void *ts_int, const void *olrb_int, const void *dolrb_int, void *olrb_exp,
-                                    void *tbrb_exp) = 0;
-    virtual int sw_update_export_dev(hipStream_t st, int ncol, int lm, int nbands, const void *const *in, void *const *out) = 0;
-    virtual int sw_update_obio_dev(hipStream_t st, int ncol, int scheme, int nbands, const double *wvn1, const double *wvn2,
-                                   const int32_t *order, const void *slr, const void *drbandn, const void *dfbandn, void *drobio,
-                                   void *dfobio) = 0;
-    virtual int sw_update_surface_dev(hipStream_t st, int ncol, int lm, double undef, const void *const *in, void *const *out) = 0;
-    virtual int sw_update_clouds_dev(hipStream_t st, int ncol, int lm, int lcldmh, int lcldlm, double taucrit, const double *consts,
-                                     const void *const *in, void *const *out) = 0;
-    virtual int sw_update_cldhb_dev(hipStream_t st, int ncol, int lm, int lcldmh, int lcldlm, int doy, const double *consts,
-                                    const void *const *in, void *const *out) = 0;
-    virtual int rad_tendencies_dev(hipStream_t st, int ncol, int lm, double grav, double cp, const void *const *in,
-                                   void *const *out) = 0;
+    virtual int sw_driver_dev(hipStream_t, int, int, int, In, const double *, int, int, double, double, int, int, int, int, int, int, const void *, const void *, Out,
+                              const LitTile *lit, const SwdObio *) { return nodev(lit ? "geosrad_sw_driver_rrtmg_lit_dev" : "geosrad_sw_driver_rrtmg_dev"); }
+    virtual int lw_chou_post_dev(hipStream_t, int, int, In, Out) { return nodev("geosrad_lw_chou_post_dev"); }
+    virtual int lw_driver_chou_dev(hipStream_t, int, int, In, const double *, int, int, int, int, Out) { return nodev("geosrad_lw_driver_chou_dev"); }
+    virtual int sw_driver_chou_dev(hipStream_t, int, int, In, const double *, int, int, const void *, const void *, int, Out, const LitTile *lit)
+    { return nodev(lit ? "geosrad_sw_driver_chou_lit_dev" : "geosrad_sw_driver_chou_dev"); }
+    virtual int lw_update_flx_dev(hipStream_t, int, int, int, int, int, double, In, Out) { return nodev("geosrad_lw_update_flx_dev"); }
+    virtual int lw_update_rats_dev(hipStream_t, int, int, int, In, Out) { return nodev("geosrad_lw_update_rats_dev"); }
+    virtual int lw_update_bands_dev(hipStream_t, int, const int32_t *, const double *, const double *, double, const void *, const void *, const void *,
+                                    const void *, void *, void *) { return nodev("geosrad_lw_update_bands_dev"); }
+    virtual int sw_update_export_dev(hipStream_t, int, int, int, In, Out) { return nodev("geosrad_sw_update_export_dev"); }
+    virtual int sw_update_obio_dev(hipStream_t, int, int, int, const double *, const double *, const int32_t *, const void *, const void *, const void *,
+                                   void *, void *) { return nodev("geosrad_sw_update_obio_dev"); }
+    virtual int sw_update_surface_dev(hipStream_t, int, int, double, In, Out) { return nodev("geosrad_sw_update_surface_dev"); }
+    virtual int sw_update_clouds_dev(hipStream_t, int, int, int, int, double, const double *, In, Out) { return nodev("geosrad_sw_update_clouds_dev"); }
+    virtual int sw_update_cldhb_dev(hipStream_t, int, int, int, int, int, const double *, In, Out) { return nodev("geosrad_sw_update_cldhb_dev"); }
+    virtual int rad_tendencies_dev(hipStream_t, int, int, double, double, In, Out) { return nodev("geosrad_rad_tendencies_dev"); }
     virtual int sw_host(int ncol, int nlay, double scon, double adjes, int isolvar, const void *const *in, int iceflg, int liqflg,
                         int dyofyr, int iaer, int cloudLM, int cloudMH, int normFlx, int32_t *clearCounts, void *const *out,
                         int do_drfband, const void *bndscl, const void *indsolvar, const void *solcycfrac,
                        void *const *dbg, void *radval) = 0;
-    virtual int lit_index_dev(hipStream_t st, int ncol, const void *zth, int32_t *idx, int32_t *pos, int32_t *nlit_dev, int *nlit_host) = 0;
-    virtual int lit_pack_dev(hipStream_t st, int pdim, int udim, int nlev, const int32_t *idx, const int32_t *nlit_dev, const void *unpacked,
-                             void *packed) = 0;
-    virtual int lit_unpack_dev(hipStream_t st, int pdim, int udim, int nlev, const int32_t *pos, const void *packed, void *unpacked,
-                               int use_default, double dflt) = 0;
+    virtual int lit_index_dev(hipStream_t, int, const void *, int32_t *, int32_t *, int32_t *, int *) { return nodev("geosrad_lit_index_dev"); }
+    virtual int lit_pack_dev(hipStream_t, int, int, int, const int32_t *, const int32_t *, const void *, void *) { return nodev("geosrad_lit_pack_dev"); }
+    virtual int lit_unpack_dev(hipStream_t, int, int, int, const int32_t *, const void *, void *, int, double) { return nodev("geosrad_lit_unpack_dev"); }
 };
 
 // order of the `in` / `out` pointer arrays of sw_dev / sw_host
@@ -730,6 +716,10 @@ geosrad_ctx *geosrad_new_ctx_f64();
 #if !defined(GEOSRAD_PART) || GEOSRAD_PART != 0
 namespace {
 
+// inside Ctx<R> (its R, VW, grid256): kernel<R, VW> over a VW-th of the threads when `wide`, else kernel<R, 1>; `rows` = gridDim.y
+#define LAUNCH_WIDE(kernel, wide, ncol, rows, st, arg) do {                                                            \
+        if (wide) hipLaunchKernelGGL((kernel<R, VW>), dim3(grid256((ncol) / VW), rows), dim3(256), 0, st, arg);       \
+        else hipLaunchKernelGGL((kernel<R, 1>), dim3(grid256(ncol), rows), dim3(256), 0, st, arg); } while (0)
 template <typename R> struct Ctx : geosrad_ctx {
     using R2 = typename Vec2<R>::T;
     // tables
@@ -1298,13 +1288,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         carve(Carve(d_ws_drvs[0]));
         LwdArgs<R> A{};
         A.ncol = ncol; A.lm = lm; A.nb = in[GEOSRAD_LWD_TAUA] ? nb : 0; A.iceflg = iceflg; A.liqflg = liqflg;
-        auto I = [&](int k) { return (const R *)in[k]; };
-        A.ple = I(GEOSRAD_LWD_PLE); A.pl = I(GEOSRAD_LWD_PL); A.t = I(GEOSRAD_LWD_T); A.q = I(GEOSRAD_LWD_Q); A.o3 = I(GEOSRAD_LWD_O3);
-        A.ch4 = I(GEOSRAD_LWD_CH4); A.n2o = I(GEOSRAD_LWD_N2O); A.co2_3d = I(GEOSRAD_LWD_CO2_3D); A.cfc11 = I(GEOSRAD_LWD_CFC11);
-        A.cfc12 = I(GEOSRAD_LWD_CFC12); A.hcfc22 = I(GEOSRAD_LWD_HCFC22); A.fcld = I(GEOSRAD_LWD_FCLD);
-        A.cwc_liq = I(GEOSRAD_LWD_CWC_LIQ); A.cwc_ice = I(GEOSRAD_LWD_CWC_ICE); A.reff_liq = I(GEOSRAD_LWD_REFF_LIQ);
-        A.reff_ice = I(GEOSRAD_LWD_REFF_ICE); A.taua = I(GEOSRAD_LWD_TAUA); A.ssaa = I(GEOSRAD_LWD_SSAA); A.ts = I(GEOSRAD_LWD_TS);
-        A.emis = I(GEOSRAD_LWD_EMIS); A.lats = I(GEOSRAD_LWD_LATS); A.t2m = I(GEOSRAD_LWD_T2M);
+        bind_in<Fields<LwdArgs<R>>>(A, in);
         A.co2_fixed = (R)consts[GEOSRAD_LWD_C_CO2_FIXED]; A.o2 = (R)consts[GEOSRAD_LWD_C_O2]; A.ccl4 = (R)consts[GEOSRAD_LWD_C_CCL4];
         // (MAPL_AIRMW/MAPL_H2OMW), (MAPL_AIRMW/MAPL_O3MW): constant expressions of the caller's real kind
         A.airmw_over_h2omw = (R)consts[GEOSRAD_C_AIRMW] / (R)consts[GEOSRAD_C_H2OMW];
@@ -1339,22 +1323,14 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (nrats > 0) {
             LwdRatPost<R> RP{};
             RP.ncol = ncol; RP.lm = lm; RP.nrats = nrats; RP.uflx = rat[0]; RP.dflx = rat[1]; RP.duflx = rat[2]; RP.emis = A.emis;
-            RP.flxu_rat = (R *)rat_out[GEOSRAD_LWD_FLXU_RAT]; RP.flxd_rat = (R *)rat_out[GEOSRAD_LWD_FLXD_RAT];
-            RP.flx_rat = (R *)rat_out[GEOSRAD_LWD_FLX_RAT]; RP.dfdts_rat = (R *)rat_out[GEOSRAD_LWD_DFDTS_RAT];
-            RP.sfcem_rat = (R *)rat_out[GEOSRAD_LWD_SFCEM_RAT];
+            bind_out<Fields<LwdRatPost<R>>>(RP, rat_out);
             hipLaunchKernelGGL((k_lwd_rat_post<R>), dim3(gx, lm + 1, nrats), blk, 0, st, RP);
         }
         LwdPost<R> Q{};
         Q.ncol = ncol; Q.lm = lm; Q.ngpt = NG_LW;
         Q.uflx = flux[0]; Q.dflx = flux[1]; Q.uflxc = flux[2]; Q.dflxc = flux[3]; Q.duflx = flux[4];
         Q.duflxc = flux[5]; Q.clearCounts = cc; Q.emis = A.emis; Q.ts = A.ts;
-        auto O = [&](int k) { return (R *)out[k]; };
-        Q.flxu_int = O(GEOSRAD_LWD_FLXU_INT); Q.flxd_int = O(GEOSRAD_LWD_FLXD_INT); Q.flcu_int = O(GEOSRAD_LWD_FLCU_INT);
-        Q.flcd_int = O(GEOSRAD_LWD_FLCD_INT); Q.dfdts = O(GEOSRAD_LWD_DFDTS); Q.dfdtsc = O(GEOSRAD_LWD_DFDTSC);
-        Q.dfdtsna = O(GEOSRAD_LWD_DFDTSNA); Q.dfdtscna = O(GEOSRAD_LWD_DFDTSCNA); Q.flx_int = O(GEOSRAD_LWD_FLX_INT);
-        Q.flc_int = O(GEOSRAD_LWD_FLC_INT); Q.sfcem_int = O(GEOSRAD_LWD_SFCEM_INT); Q.ts_int = O(GEOSRAD_LWD_TS_INT);
-        Q.cldttlw = O(GEOSRAD_LWD_CLDTTLW); Q.cldhilw = O(GEOSRAD_LWD_CLDHILW); Q.cldmdlw = O(GEOSRAD_LWD_CLDMDLW);
-        Q.cldlolw = O(GEOSRAD_LWD_CLDLOLW);
+        bind_out<Fields<LwdPost<R>>>(Q, out);
         hipLaunchKernelGGL((k_lwd_post<R>), dim3(gx, lm + 1), blk, 0, st, Q);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
@@ -1432,14 +1408,10 @@ template <typename R> struct Ctx : geosrad_ctx {
         };
         if (const int rc = drv_reserve(1, carve(Carve()))) return rc;
         carve(Carve(d_ws_drvs[1]));
-        auto I = [&](int k) { return (const R *)in[k]; };
         SwdLit<R> AL{};
         SwdArgs<R> &A = AL;
         A.ncol = ncol; A.lm = lm; A.nb = 14; A.iceflg = iceflg; A.liqflg = liqflg;
-        A.ple = I(GEOSRAD_SWD_PLE); A.pl = I(GEOSRAD_SWD_PL); A.t = I(GEOSRAD_SWD_T); A.q = I(GEOSRAD_SWD_Q); A.o3 = I(GEOSRAD_SWD_O3);
-        A.ch4 = I(GEOSRAD_SWD_CH4); A.cl = I(GEOSRAD_SWD_CL); A.ts = I(GEOSRAD_SWD_TS); A.qq_ice = I(GEOSRAD_SWD_QQ_ICE);
-        A.qq_liq = I(GEOSRAD_SWD_QQ_LIQ); A.rr_ice = I(GEOSRAD_SWD_RR_ICE); A.rr_liq = I(GEOSRAD_SWD_RR_LIQ);
-        A.taua = (R *)in[GEOSRAD_SWD_TAUA]; A.ssaa = (R *)in[GEOSRAD_SWD_SSAA]; A.asya = (R *)in[GEOSRAD_SWD_ASYA];
+        bind_in<Fields<SwdLit<R>>>(AL, in);
         A.co2 = (R)consts[GEOSRAD_SWD_C_CO2]; A.o2 = (R)consts[GEOSRAD_SWD_C_O2];
         A.airmw_over_h2omw = (R)consts[GEOSRAD_SWD_C_AIRMW] / (R)consts[GEOSRAD_SWD_C_H2OMW];
         A.airmw_over_o3mw = (R)consts[GEOSRAD_SWD_C_AIRMW] / (R)consts[GEOSRAD_SWD_C_O3MW];
@@ -1450,12 +1422,10 @@ template <typename R> struct Ctx : geosrad_ctx {
         const dim3 blk(256);
         const unsigned gx = grid256(ncol);
         // ZT ALAT ALBVR ALBVF ALBNR ALBNF: the caller's packed arrays, or the tile's gathered by the prep kernel
-        static const int col_ix[6] = {GEOSRAD_SWD_ZT, GEOSRAD_SWD_ALAT, GEOSRAD_SWD_ALBVR, GEOSRAD_SWD_ALBVF, GEOSRAD_SWD_ALBNR, GEOSRAD_SWD_ALBNF};
         const void *cin[6];
-        for (int k = 0; k < 6; k++) cin[k] = lit ? col[k] : in[col_ix[k]];
+        for (int k = 0; k < 6; k++) { AL.col_out[k] = col[k]; cin[k] = lit ? col[k] : AL.col_in[k]; }
         if (lit) {
             AL.tile = lit->tile; AL.lit = lit->idx;
-            for (int k = 0; k < 6; k++) { AL.col_in[k] = I(col_ix[k]); AL.col_out[k] = col[k]; }
             hipLaunchKernelGGL((k_swd_prep<R, true>), dim3(gx, lm), blk, 0, st, AL);
         } else hipLaunchKernelGGL((k_swd_prep<R>), dim3(gx, lm), blk, 0, st, A);
         hipLaunchKernelGGL((k_swd_zm<R>), dim3(gx), blk, 0, st, A);
@@ -1488,10 +1458,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         SwdPost<R> &Q = QL;
         Q.ncol = ncol; Q.lm = lm; Q.ngpt = NG_SW; Q.aerosols = include_aerosols; Q.undef = (R)consts[GEOSRAD_SWD_C_UNDEF];
         Q.swuflx = flux[0]; Q.swdflx = flux[1]; Q.swuflxc = flux[2]; Q.swdflxc = flux[3]; Q.clearCounts = cc;
-        for (int k = 0; k < 4; k++) { Q.cotd[k] = cot[k]; Q.cotn[k] = cot[4 + k]; Q.cot[k] = (R *)out[GEOSRAD_SWD_COTTP + k]; }
-        Q.fsw = (R *)out[GEOSRAD_SWD_FSW]; Q.fsc = (R *)out[GEOSRAD_SWD_FSC]; Q.fswu = (R *)out[GEOSRAD_SWD_FSWU]; Q.fscu = (R *)out[GEOSRAD_SWD_FSCU];
-        Q.cldts = (R *)out[GEOSRAD_SWD_CLDTS]; Q.cldhs = (R *)out[GEOSRAD_SWD_CLDHS]; Q.cldms = (R *)out[GEOSRAD_SWD_CLDMS];
-        Q.cldls = (R *)out[GEOSRAD_SWD_CLDLS];
+        for (int k = 0; k < 4; k++) { Q.cotd[k] = cot[k]; Q.cotn[k] = cot[4 + k]; }
+        bind_out<Fields<SwdPost<R>>>(Q, out);
         // k_swd_post_lit's dark values and keep bits, from the outputs its slots stand for (-1: none)
         auto post_lit = [&](SwdPostLit<R> &P, std::initializer_list<int> ix) {
             P.tile = lit->tile; P.pos = lit->pos; P.keep = 0;
@@ -1510,8 +1478,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             SwdPost<R> &N = NL;
             N.ncol = ncol; N.lm = lm; N.ngpt = NG_SW; N.aerosols = 0; N.undef = Q.undef;
             N.swuflx = nflux[0]; N.swdflx = nflux[1]; N.swuflxc = nflux[2]; N.swdflxc = nflux[3]; N.clearCounts = cc;
-            N.fsw = (R *)out[GEOSRAD_SWD_FSWNA]; N.fsc = (R *)out[GEOSRAD_SWD_FSCNA]; N.fswu = (R *)out[GEOSRAD_SWD_FSWUNA];
-            N.fscu = (R *)out[GEOSRAD_SWD_FSCUNA];
+            bind_out<SwdPostNa<R>>(N, out);
             if (lit) post_lit(NL, {GEOSRAD_SWD_FSWNA, GEOSRAD_SWD_FSCNA, GEOSRAD_SWD_FSWUNA, GEOSRAD_SWD_FSCUNA, -1, -1, -1, -1, -1, -1, -1, -1});
             else hipLaunchKernelGGL((k_swd_post<R>), dim3(gx, lm + 1), blk, 0, st, N);
         }
@@ -1533,12 +1500,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (ncol <= 0 || lm <= 0) return fail(GEOSRAD_EINVAL, "bad ncol/lm");
         LwcPost<R> P{};
         P.ncol = ncol; P.lm = lm;
-        static_assert(offsetof(LwcPost<R>, ts) - offsetof(LwcPost<R>, flxu) == (GEOSRAD_LWC_NIN - 1) * sizeof(void *), "LwcPost input layout");
-        static_assert(offsetof(LwcPost<R>, ts_int) - offsetof(LwcPost<R>, sfcem_int) == (GEOSRAD_LWC_NOUT - 1) * sizeof(void *), "LwcPost output layout");
-        const R **ip = &P.flxu;
-        for (int k = 0; k < GEOSRAD_LWC_NIN; k++) ip[k] = (const R *)in[k];
-        R **op = &P.sfcem_int;
-        for (int k = 0; k < GEOSRAD_LWC_NOUT; k++) op[k] = (R *)out[k];
+        bind(P, in, out);
         auto need = [&](const R *o, const R *a, const R *b = (const R *)1) { return !o || (a && b); };
         if (!(need(P.flx_int, P.flxd, P.flxu) && need(P.flxa_int, P.flxad, P.flxau) && need(P.flc_int, P.flcd, P.flcu) &&
               need(P.fla_int, P.flad, P.flau) && need(P.dfdtsna, P.dfdts) && need(P.ts_int, P.ts)))
@@ -1580,13 +1542,11 @@ template <typename R> struct Ctx : geosrad_ctx {
                                         {out + GEOSRAD_LWK_DFDTS, GEOSRAD_LWK_NOUT - GEOSRAD_LWK_DFDTS}});
         LwkSurf<R> S{};
         S.ncol = ncol; S.lm = lm; S.mkappa = -(R)consts[GEOSRAD_LWK_C_KAPPA];
-        S.ple = I(GEOSRAD_LWK_PLE); S.t = I(GEOSRAD_LWK_T); S.ts = I(GEOSRAD_LWK_TS); S.emis = I(GEOSRAD_LWK_EMIS);
+        bind_in<Fields<LwkSurf<R>>>(S, in);
         S.t2m = O(GEOSRAD_LWK_T2M) ? O(GEOSRAD_LWK_T2M) : ws;
         S.fs = ws + (size_t)ncol; S.tg = ws + (size_t)2 * ncol; S.tv = ws + (size_t)3 * ncol;
         S.eg = ws + (size_t)4 * ncol; S.ev = ws + (size_t)14 * ncol; S.rv = ws + (size_t)24 * ncol;
-        const dim3 blk(256), gw(grid256(ncol / VW)), g1(grid256(ncol));
-        if (wide) hipLaunchKernelGGL((k_lwk_surface<R, VW>), dim3(gw.x, 11), blk, 0, st, S);
-        else hipLaunchKernelGGL((k_lwk_surface<R, 1>), dim3(g1.x, 11), blk, 0, st, S);
+        LAUNCH_WIDE(k_lwk_surface, wide, ncol, 11, st, S);
         HIPCHK(hipGetLastError());
         const void *ci[C_NIN] = {};
         ci[C_PLE] = in[GEOSRAD_LWK_PLE]; ci[C_TA] = in[GEOSRAD_LWK_T]; ci[C_WA] = in[GEOSRAD_LWK_Q]; ci[C_OA] = in[GEOSRAD_LWK_O3]; ci[C_TB] = S.t2m;
@@ -1613,14 +1573,9 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (const int rc2 = lw_chou_post_dev(st, ncol, lm, pi, po)) return rc2;
         LwkDiag<R> D{};
         D.ncol = ncol; D.lm = lm; D.taucrit = (R)consts[GEOSRAD_LWK_C_TAUCRIT] / (R)2.13; D.undef = G.undef;
-        D.taudiag = taudiag; D.t = S.t; D.ple = S.ple; D.ts = S.ts; D.dfdts = O(GEOSRAD_LWK_DFDTS); D.sfcem_int = O(GEOSRAD_LWK_SFCEM_INT);
-        D.flx_int = O(GEOSRAD_LWK_FLX_INT);
-        D.tauir = O(GEOSRAD_LWK_TAUIR); D.cldtmp = O(GEOSRAD_LWK_CLDTMP); D.cldprs = O(GEOSRAD_LWK_CLDPRS); D.tsreff = O(GEOSRAD_LWK_TSREFF);
-        D.dsfdts0 = O(GEOSRAD_LWK_DSFDTS0); D.sfcem0 = O(GEOSRAD_LWK_SFCEM0); D.lws0 = O(GEOSRAD_LWK_LWS0);
-        if (D.tauir || D.cldtmp || D.cldprs || D.tsreff || D.dsfdts0 || D.sfcem0 || D.lws0) {
-            if (wide) hipLaunchKernelGGL((k_lwk_diag<R, VW>), gw, blk, 0, st, D);
-            else hipLaunchKernelGGL((k_lwk_diag<R, 1>), g1, blk, 0, st, D);
-        }
+        D.taudiag = taudiag;
+        bind(D, in, out);
+        if (D.tauir || D.cldtmp || D.cldprs || D.tsreff || D.dsfdts0 || D.sfcem0 || D.lws0) LAUNCH_WIDE(k_lwk_diag, wide, ncol, 1, st, D);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1670,19 +1625,14 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (d_ws_swc.reserve(carve(Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "SORADCORE (Chou-Suarez) workspace");
         carve(Carve(d_ws_swc));
         P.ncol = ncol; P.lm = lm;
-        P.ple = (const R *)in[GEOSRAD_SWC_PLE]; P.ox = (const R *)in[GEOSRAD_SWC_OX];
-        for (int s = 0; s < 4; s++) { P.q[s] = (const R *)in[GEOSRAD_SWC_QI + s]; P.r[s] = (const R *)in[GEOSRAD_SWC_RI + s]; }
+        bind_in<Fields<SwcLit<R>>>(PL, in);
         P.o3fac = (R)consts[GEOSRAD_SWC_C_O3MW] / (R)consts[GEOSRAD_SWC_C_AIRMW]; P.undef = (R)consts[GEOSRAD_SWC_C_UNDEF];
         // T Q CL, TAUA SSAA ASYA, ZT ALBVR ALBVF ALBNR ALBNF: the caller's packed arrays, or the tile's gathered by the prep kernel
-        static const int lay_ix[3] = {GEOSRAD_SWC_T, GEOSRAD_SWC_Q, GEOSRAD_SWC_CL}, aer_ix[3] = {GEOSRAD_SWC_TAUA, GEOSRAD_SWC_SSAA, GEOSRAD_SWC_ASYA},
-                         col_ix[5] = {GEOSRAD_SWC_ZT, GEOSRAD_SWC_ALBVR, GEOSRAD_SWC_ALBVF, GEOSRAD_SWC_ALBNR, GEOSRAD_SWC_ALBNF};
         const void *lay[3], *aerp[3], *col[5];
-        for (int k = 0; k < 3; k++) { lay[k] = lit ? PL.lay_out[k] : in[lay_ix[k]]; aerp[k] = !aer ? zero : (lit ? PL.aer_out[k] : in[aer_ix[k]]); }
-        for (int k = 0; k < 5; k++) col[k] = lit ? PL.col_out[k] : in[col_ix[k]];
+        for (int k = 0; k < 3; k++) { lay[k] = lit ? PL.lay_out[k] : PL.lay_in[k]; aerp[k] = !aer ? zero : (lit ? PL.aer_out[k] : PL.aer_in[k]); }
+        for (int k = 0; k < 5; k++) col[k] = lit ? PL.col_out[k] : PL.col_in[k];
         if (lit) {
             PL.tile = lit->tile; PL.lit = lit->idx;
-            for (int k = 0; k < 3; k++) { PL.lay_in[k] = (const R *)in[lay_ix[k]]; PL.aer_in[k] = (const R *)in[aer_ix[k]]; }
-            for (int k = 0; k < 5; k++) PL.col_in[k] = (const R *)in[col_ix[k]];
             hipLaunchKernelGGL((k_swc_prep<R, true>), dim3(grid256(ncol), lm + 1), dim3(256), 0, st, PL);
         } else hipLaunchKernelGGL((k_swc_prep<R>), dim3(grid256(ncol), lm + 1), dim3(256), 0, st, P);
         HIPCHK(hipGetLastError());
@@ -1719,19 +1669,9 @@ template <typename R> struct Ctx : geosrad_ctx {
             if (!in[k] && !(rrtmg && na(k))) return fail(GEOSRAD_EINVAL, "null internal-state array");
         LwUpd<R> U{};
         U.ncol = ncol; U.lm = lm; U.rrtmg = rrtmg; U.lev_mid_high = lev_mid_high; U.lev_low_mid = lev_low_mid; U.undef = (R)undef;
-        auto I = [&](int k) { return (const R *)in[k]; };
-        U.tsinst = I(GEOSRAD_LWU_TSINST); U.ts_int = I(GEOSRAD_LWU_TS_INT); U.sfcem_int = I(GEOSRAD_LWU_SFCEM_INT); U.fcld = I(GEOSRAD_LWU_FCLD);
-        U.flx_int = I(GEOSRAD_LWU_FLX_INT); U.flxa_int = I(GEOSRAD_LWU_FLXA_INT); U.flc_int = I(GEOSRAD_LWU_FLC_INT); U.fla_int = I(GEOSRAD_LWU_FLA_INT);
-        U.flxu_int = I(GEOSRAD_LWU_FLXU_INT); U.flxau_int = I(GEOSRAD_LWU_FLXAU_INT); U.flcu_int = I(GEOSRAD_LWU_FLCU_INT);
-        U.flau_int = I(GEOSRAD_LWU_FLAU_INT); U.flxd_int = I(GEOSRAD_LWU_FLXD_INT); U.flxad_int = I(GEOSRAD_LWU_FLXAD_INT);
-        U.flcd_int = I(GEOSRAD_LWU_FLCD_INT); U.flad_int = I(GEOSRAD_LWU_FLAD_INT); U.dfdts = I(GEOSRAD_LWU_DFDTS);
-        U.dfdtsna = I(GEOSRAD_LWU_DFDTSNA); U.dfdtsc = I(GEOSRAD_LWU_DFDTSC); U.dfdtscna = I(GEOSRAD_LWU_DFDTSCNA);
-        static_assert(offsetof(LwUpd<R>, cldtt) - offsetof(LwUpd<R>, flx) == (GEOSRAD_LWU_NOUT - 1) * sizeof(void *), "LwUpd export layout");
-        R **o3 = &U.flx;       // the export pointers are laid out in the order of the GEOSRAD_LWU_* output enum
-        for (int k = 0; k < GEOSRAD_LWU_NOUT; k++) o3[k] = (R *)out[k];
+        bind(U, in, out);
         const bool wide = wide16(ncol, {{in, GEOSRAD_LWU_NIN}, {out, GEOSRAD_LWU_NOUT}});
-        if (wide) hipLaunchKernelGGL((k_lw_update_flx<R, VW>), dim3(grid256(ncol / VW), lm + 1), dim3(256), 0, st, U);
-        else hipLaunchKernelGGL((k_lw_update_flx<R, 1>), dim3(grid256(ncol), lm + 1), dim3(256), 0, st, U);
+        LAUNCH_WIDE(k_lw_update_flx, wide, ncol, lm + 1, st, U);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1747,12 +1687,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             return fail(GEOSRAD_EINVAL, "DFDTS_<gas> requested without DFDTS / DFDTS_RAT");
         LwRatUpd<R> U{};
         U.ncol = ncol; U.lm = lm; U.nrats = nrats;
-        auto I = [&](int k) { return (const R *)in[k]; };
-        U.flx_int = I(GEOSRAD_LWR_FLX_INT); U.sfcem_int = I(GEOSRAD_LWR_SFCEM_INT); U.dfdts = I(GEOSRAD_LWR_DFDTS);
-        U.flx_rat = I(GEOSRAD_LWR_FLX_RAT); U.sfcem_rat = I(GEOSRAD_LWR_SFCEM_RAT); U.dfdts_rat = I(GEOSRAD_LWR_DFDTS_RAT);
-        auto O = [&](int k) { return (R *)out[k]; };
-        U.dolr = O(GEOSRAD_LWR_DOLR); U.dlws = O(GEOSRAD_LWR_DLWS); U.dflns = O(GEOSRAD_LWR_DFLNS); U.dsfcem = O(GEOSRAD_LWR_DSFCEM);
-        U.nettrap = O(GEOSRAD_LWR_NETTRAP); U.coltrap = O(GEOSRAD_LWR_COLTRAP); U.flx = O(GEOSRAD_LWR_FLX); U.dfdts_out = O(GEOSRAD_LWR_DFDTS_OUT);
+        bind(U, in, out);
         hipLaunchKernelGGL((k_lw_update_rats<R>), dim3(grid256(ncol), lm + 1, nrats), dim3(256), 0, st, U);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
@@ -1789,12 +1724,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (ncol <= 0 || lm <= 0 || nbands < 0) return fail(GEOSRAD_EINVAL, "bad ncol/lm/nbands");
         SwUpd<R> U{};
         U.ncol = ncol; U.lm = lm; U.nbands = nbands;
-        static_assert(offsetof(SwUpd<R>, fswbandnan) - offsetof(SwUpd<R>, slr) == (GEOSRAD_SWU_NIN - 1) * sizeof(void *), "SwUpd input layout");
-        static_assert(offsetof(SwUpd<R>, osrcna) - offsetof(SwUpd<R>, fsw) == (GEOSRAD_SWU_NOUT - 1) * sizeof(void *), "SwUpd export layout");
-        const R **ip = &U.slr;      // members in the order of the GEOSRAD_SWU_* enums
-        for (int k = 0; k < GEOSRAD_SWU_NIN; k++) ip[k] = (const R *)in[k];
-        R **op = &U.fsw;
-        for (int k = 0; k < GEOSRAD_SWU_NOUT; k++) op[k] = (R *)out[k];
+        bind(U, in, out);
         if (!U.slr) return fail(GEOSRAD_EINVAL, "SLR is required");
         // an export needs the internals it is computed from
         auto need = [&](const R *o, const R *a, const R *b = (const R *)1) { return !o || (a && b); };
@@ -1807,8 +1737,7 @@ template <typename R> struct Ctx : geosrad_ctx {
                         need(U.rscna, U.fscnan) && need(U.rscsna, U.fscnan) && need(U.osrcna, U.fscnan);
         if (!ok) return fail(GEOSRAD_EINVAL, "an export was requested without the internal field it is computed from");
         const bool wide = wide16(ncol, {{in, GEOSRAD_SWU_NIN}, {out, GEOSRAD_SWU_NOUT}});
-        if (wide) hipLaunchKernelGGL((k_sw_update_export<R, VW>), dim3(grid256(ncol / VW), lm + 1 + nbands), dim3(256), 0, st, U);
-        else hipLaunchKernelGGL((k_sw_update_export<R, 1>), dim3(grid256(ncol), lm + 1 + nbands), dim3(256), 0, st, U);
+        LAUNCH_WIDE(k_sw_update_export, wide, ncol, lm + 1 + nbands, st, U);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1849,8 +1778,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (dfobio) { U.x[nfam] = (const R *)dfbandn; U.y[nfam++] = (R *)dfobio; }
         const void *ptrs[5] = {slr, U.x[0], U.y[0], U.x[nfam - 1], U.y[nfam - 1]};
         const bool wide = wide16(ncol, {{ptrs, 5}});
-        if (wide) hipLaunchKernelGGL((k_sw_update_obio<R, VW>), dim3(grid256(ncol / VW), nfam), dim3(256), 0, st, U);
-        else hipLaunchKernelGGL((k_sw_update_obio<R, 1>), dim3(grid256(ncol), nfam), dim3(256), 0, st, U);
+        LAUNCH_WIDE(k_sw_update_obio, wide, ncol, nfam, st, U);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1871,16 +1799,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             return fail(GEOSRAD_EINVAL, "a requested surface export needs an internal flux that is null");
         SwSfc<R> U{};
         U.ncol = ncol; U.lm = lm; U.undef = (R)undef;
-        auto I = [&](int k) { return (const R *)in[k]; };
-        auto O = [&](int k) { return (R *)out[k]; };
-        U.slr = I(GEOSRAD_SWS_SLR); U.zth = I(GEOSRAD_SWS_ZTH);
-        for (int k = 0; k < 4; k++) { U.alb_imp[k] = I(GEOSRAD_SWS_ALBVF + k); U.alb_exp[k] = O(GEOSRAD_SWS_ALBVF_X + k); }
-        for (int k = 0; k < 6; k++) { U.dn[k] = I(GEOSRAD_SWS_DRUVRN + k); U.dx[k] = O(GEOSRAD_SWS_DRUVR + k); }
-        U.fswn = I(GEOSRAD_SWS_FSWN); U.fscn = I(GEOSRAD_SWS_FSCN); U.fswnan = I(GEOSRAD_SWS_FSWNAN); U.fscnan = I(GEOSRAD_SWS_FSCNAN);
-        U.albedo = O(GEOSRAD_SWS_ALBEDO); U.slrtp = O(GEOSRAD_SWS_SLRTP);
-        for (int k = 0; k < 3; k++) U.drn[k] = O(GEOSRAD_SWS_DRNUVR + k);
-        U.slrsf = O(GEOSRAD_SWS_SLRSF); U.slrsfc = O(GEOSRAD_SWS_SLRSFC); U.slrsfna = O(GEOSRAD_SWS_SLRSFNA); U.slrsfcna = O(GEOSRAD_SWS_SLRSFCNA);
-        U.slrsuf = O(GEOSRAD_SWS_SLRSUF); U.slrsufc = O(GEOSRAD_SWS_SLRSUFC); U.slrsufna = O(GEOSRAD_SWS_SLRSUFNA); U.slrsufcna = O(GEOSRAD_SWS_SLRSUFCNA);
+        bind(U, in, out);
         hipLaunchKernelGGL((k_sw_update_surface<R>), dim3(grid256(ncol)), dim3(256), 0, st, U);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
@@ -2009,12 +1928,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (ncol <= 0 || lm <= 0) return fail(GEOSRAD_EINVAL, "bad ncol/lm");
         RadTend<R> P{};
         P.ncol = ncol; P.lm = lm; P.grav = (R)grav; P.cp = (R)cp;
-        static_assert(offsetof(RadTend<R>, trd) - offsetof(RadTend<R>, ple) == (GEOSRAD_RT_NIN - 1) * sizeof(void *), "RadTend input layout");
-        static_assert(offsetof(RadTend<R>, radsrf) - offsetof(RadTend<R>, dtdt) == (GEOSRAD_RT_NOUT - 1) * sizeof(void *), "RadTend export layout");
-        const R **ip = &P.ple;
-        for (int k = 0; k < GEOSRAD_RT_NIN; k++) ip[k] = (const R *)in[k];
-        R **op = &P.dtdt;
-        for (int k = 0; k < GEOSRAD_RT_NOUT; k++) op[k] = (R *)out[k];
+        bind(P, in, out);
         auto need = [&](const R *o, const R *a, const R *b = (const R *)1, const R *c = (const R *)1) { return !o || (a && b && c); };
         const bool any3 = P.radlw || P.radsw || P.radlwc || P.radswc || P.radswna || P.radlwcna || P.radswcna;
         const bool ok = need(P.dtdt, P.flw, P.fsw) && (!any3 || P.ple) && need(P.radlw, P.flw) && need(P.radsw, P.fsw) &&
@@ -2023,8 +1937,7 @@ template <typename R> struct Ctx : geosrad_ctx {
                         need(P.radsrf, P.fsw, P.flw);
         if (!ok) return fail(GEOSRAD_EINVAL, "an export was requested without the field it is computed from");
         const bool wide = wide16(ncol, {{in, GEOSRAD_RT_NIN}, {out, GEOSRAD_RT_NOUT}});
-        if (wide) hipLaunchKernelGGL((k_rad_tendencies<R, VW>), dim3(grid256(ncol / VW), lm), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((k_rad_tendencies<R, 1>), dim3(grid256(ncol), lm), dim3(256), 0, st, P);
+        LAUNCH_WIDE(k_rad_tendencies, wide, ncol, lm, st, P);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -2876,7 +2789,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 };
-
+#undef LAUNCH_WIDE
 }  // namespace
 
 #if !defined(GEOSRAD_PART) || GEOSRAD_PART == 4
@@ -2897,7 +2810,7 @@ geosrad_ctx *geosrad_new_ctx_f64() { return new Ctx<double>(); }
 // shards and run one child's pipeline per shard concurrently (one host thread each; a child reads / writes its shard of the
 // caller's arrays in place: base pointer + shard start, leading dimension = the full ncol).  Columns are independent, so the
 // result is bitwise the single-device one (tested with device_ids = {0, 0}).  Table / parameter setters go to every child;
-// the `_dev` entry points (device pointers belong to ONE device) are refused.
+// the `_dev` entry points keep geosrad_ctx's refusal.
 // ---------------------------------------------------------------------------------------------------
 namespace {
 struct MultiCtx final : geosrad_ctx {
@@ -2909,7 +2822,6 @@ struct MultiCtx final : geosrad_ctx {
         for (auto *k : kid) { const int rc = f(k); if (rc) { last_error = k->last_error; return rc; } }
         return GEOSRAD_OK;
     }
-    int nodev(const char *what) { return fail(GEOSRAD_EINVAL, std::string(what) + ": device-pointer entry points need a single-device context (geosrad_create)"); }
     // shard s of n columns: [start, start + count)
     static void shard(int n, int nk, int s, int &start, int &count) { const int per = (n + nk - 1) / nk; start = s * per; count = start >= n ? 0 : (n - start < per ? n - start : per); }
     // fn(child, first column, columns) per shard, concurrently; the first failing shard's status and message
@@ -2989,37 +2901,6 @@ struct MultiCtx final : geosrad_ctx {
     }
     int mcica_host(int, int, int, const void *, const void *, int, const void *, const void *, const void *, const void *, double,
                    const int32_t *, int32_t *, void *, void *) override { return fail(GEOSRAD_EINVAL, "geosrad_mcica needs a single-device context"); }
-    int lw_dev(hipStream_t, int, int, int, const void *const *, int, int, int, int, int, int32_t *, void *const *, const int32_t *, void *, void *,
-               const LwRats *) override { return nodev("geosrad_rrtmg_lw_dev"); }
-    int mcica_dev(hipStream_t, int, int, int, const void *, const void *, int, const void *, const void *, const void *, const void *, double,
-                  const int32_t *, int32_t *, void *, void *) override { return nodev("geosrad_mcica_dev"); }
-    int sorad_dev(hipStream_t, int, int, int, const void *const *, double, int, int, const void *, const void *, void *const *, int) override { return nodev("geosrad_sorad_dev"); }
-    int irrad_dev(hipStream_t, int, int, const void *const *, double, int, int, int, int, int, int, void *const *, void *const *) override { return nodev("geosrad_irrad_dev"); }
-    int sw_dev(hipStream_t, int, int, double, double, int, const void *const *, int, int, int, int, int, int, int, int32_t *, void *const *, int,
-               const void *, const void *, const void *, void *const *, void *) override { return nodev("geosrad_rrtmg_sw_dev"); }
-    int lw_driver_dev(hipStream_t, int, int, int, const void *const *, const double *, int, int, int, int, int, const int32_t *, void *const *, int,
-                      const int32_t *, void *const *) override { return nodev("geosrad_lw_driver_rrtmg_dev"); }
-    int sw_driver_dev(hipStream_t, int, int, int, const void *const *, const double *, int, int, double, double, int, int, int, int, int, int,
-                      const void *, const void *, void *const *, const LitTile *lit, const SwdObio *) override
-    { return nodev(lit ? "geosrad_sw_driver_rrtmg_lit_dev" : "geosrad_sw_driver_rrtmg_dev"); }
-    int lw_chou_post_dev(hipStream_t, int, int, const void *const *, void *const *) override { return nodev("geosrad_lw_chou_post_dev"); }
-    int lw_driver_chou_dev(hipStream_t, int, int, const void *const *, const double *, int, int, int, int, void *const *) override { return nodev("geosrad_lw_driver_chou_dev"); }
-    int sw_driver_chou_dev(hipStream_t, int, int, const void *const *, const double *, int, int, const void *, const void *, int,
-                           void *const *, const LitTile *lit) override { return nodev(lit ? "geosrad_sw_driver_chou_lit_dev" : "geosrad_sw_driver_chou_dev"); }
-    int lw_update_flx_dev(hipStream_t, int, int, int, int, int, double, const void *const *, void *const *) override { return nodev("geosrad_lw_update_flx_dev"); }
-    int lw_update_rats_dev(hipStream_t, int, int, int, const void *const *, void *const *) override { return nodev("geosrad_lw_update_rats_dev"); }
-    int lw_update_bands_dev(hipStream_t, int, const int32_t *, const double *, const double *, double, const void *, const void *, const void *,
-                            const void *, void *, void *) override { return nodev("geosrad_lw_update_bands_dev"); }
-    int sw_update_export_dev(hipStream_t, int, int, int, const void *const *, void *const *) override { return nodev("geosrad_sw_update_export_dev"); }
-    int sw_update_obio_dev(hipStream_t, int, int, int, const double *, const double *, const int32_t *, const void *, const void *, const void *,
-                           void *, void *) override { return nodev("geosrad_sw_update_obio_dev"); }
-    int sw_update_surface_dev(hipStream_t, int, int, double, const void *const *, void *const *) override { return nodev("geosrad_sw_update_surface_dev"); }
-    int sw_update_clouds_dev(hipStream_t, int, int, int, int, double, const double *, const void *const *, void *const *) override { return nodev("geosrad_sw_update_clouds_dev"); }
-    int sw_update_cldhb_dev(hipStream_t, int, int, int, int, int, const double *, const void *const *, void *const *) override { return nodev("geosrad_sw_update_cldhb_dev"); }
-    int rad_tendencies_dev(hipStream_t, int, int, double, double, const void *const *, void *const *) override { return nodev("geosrad_rad_tendencies_dev"); }
-    int lit_index_dev(hipStream_t, int, const void *, int32_t *, int32_t *, int32_t *, int *) override { return nodev("geosrad_lit_index_dev"); }
-    int lit_pack_dev(hipStream_t, int, int, int, const int32_t *, const int32_t *, const void *, void *) override { return nodev("geosrad_lit_pack_dev"); }
-    int lit_unpack_dev(hipStream_t, int, int, int, const int32_t *, const void *, void *, int, double) override { return nodev("geosrad_lit_unpack_dev"); }
 };
 }  // namespace
 

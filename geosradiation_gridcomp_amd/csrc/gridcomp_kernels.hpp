@@ -18,6 +18,7 @@
 // blockIdx.y = level): all accesses are coalesced, nothing is transposed, the vertical flip is an index calculation.
 // A null output pointer = Fortran "not associated" (export not requested).
 #pragma once
+#include <iterator>
 #include <type_traits>
 #include "../../include/geosrad.h"
 #include "lw_device.hpp"
@@ -26,6 +27,30 @@
 #include "obio_bands.hpp"        // NB_OBIO, OBIO_MAXBANDS, OBIO_MAXPAIRS
 
 namespace geosrad {
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Host only: where slot k of an entry point's public `in[]` / `out[]` pointer table (the GEOSRAD_*_* enums of geosrad.h) goes in the argument
+// struct S of a kernel.  Next to each such struct stands Fields<S> (or a named variant) with one table per direction in the enum's order: a
+// pointer to member, elem<&S::array, k> for an element of an array member, {} where S has no member for the slot.  bind() fills a struct from
+// the caller's tables; a new field is one member, one enum value and one entry here.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <typename S, typename R> struct Slot {
+    const R *S::*rd = nullptr;
+    R *S::*wr = nullptr;
+    void (*el)(S &, R *) = nullptr;
+    constexpr Slot() {}
+    constexpr Slot(const R *S::*m) : rd(m) {}
+    constexpr Slot(R *S::*m) : wr(m) {}
+    constexpr Slot(void (*f)(S &, R *)) : el(f) {}
+    // a member that is written (an export, or an in-out import such as SwdArgs::taua from `in[]`) takes the pointer with its const cast away
+    void set(S &s, const void *p) const { if (rd) s.*rd = (const R *)p; else if (wr) s.*wr = (R *)p; else if (el) el(s, (R *)p); }
+};
+template <auto A, int K, typename S, typename R> void elem(S &s, R *p) { (s.*A)[K] = p; }
+template <typename S> struct Fields;
+#define GR_TABLE(dir, N, ...) static constexpr Slot<S, R> dir[] = {__VA_ARGS__}; static_assert(std::size(dir) == N, "one entry for each of the " #N " slots")
+template <typename F, typename S> void bind_in(S &s, const void *const *in) { int k = 0; for (const auto &f : F::in) f.set(s, in[k++]); }
+template <typename F, typename S> void bind_out(S &s, void *const *out) { int k = 0; for (const auto &f : F::out) f.set(s, out[k++]); }
+template <typename S> void bind(S &s, const void *const *in, void *const *out) { bind_in<Fields<S>>(s, in); bind_out<Fields<S>>(s, out); }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // LW_Driver, RRTMG branch
@@ -44,6 +69,10 @@ template <typename R> struct LwdArgs {
         *cldf, *ciwp, *clwp, *rei, *rel, *tauaer, *zm, *alat;
 };
 
+template <typename R> struct Fields<LwdArgs<R>> { using S = LwdArgs<R>;
+    GR_TABLE(in, GEOSRAD_LWD_NIN, &S::ple, &S::pl, &S::t, &S::q, &S::o3, &S::ch4, &S::n2o, &S::co2_3d, &S::cfc11, &S::cfc12, &S::hcfc22, &S::fcld, &S::cwc_liq,
+             &S::cwc_ice, &S::reff_liq, &S::reff_ice, &S::taua, &S::ssaa, &S::ts, &S::emis, &S::lats, &S::t2m);
+};
 // interface temperature of model level k (1..LM+1), IRR:3248-3256
 template <typename R> GR_DEV R lwd_tlev(const LwdArgs<R> &A, int k, int ij)
 {
@@ -160,6 +189,10 @@ template <typename R> struct LwdPost {
     R *sfcem_int, *ts_int, *cldttlw, *cldhilw, *cldmdlw, *cldlolw;
 };
 
+template <typename R> struct Fields<LwdPost<R>> { using S = LwdPost<R>;      // OLRB, DOLRB are the solver's own
+    GR_TABLE(out, GEOSRAD_LWD_NOUT, &S::flxu_int, &S::flxd_int, &S::flcu_int, &S::flcd_int, &S::dfdts, &S::dfdtsc, &S::dfdtsna, &S::dfdtscna, &S::flx_int,
+             &S::flc_int, &S::sfcem_int, &S::ts_int, &S::cldttlw, &S::cldhilw, &S::cldmdlw, &S::cldlolw, {}, {});
+};
 // one thread per (column, GEOS level K = 0..LM) (IRR:3487-3533, :3601-3615, :3560-3565)
 template <typename R> __global__ void __launch_bounds__(256) k_lwd_post(LwdPost<R> P)
 {
@@ -201,6 +234,9 @@ template <typename R> struct LwdRatPost {
     const R *emis;                              // EMIS(I,J) = EMISS(IJ,1): all bands share it (IRR:3249)
     R *flxu_rat, *flxd_rat, *flx_rat, *dfdts_rat, *sfcem_rat;     // (ncol,0:LM,nrats), SFCEM_RAT (ncol,nrats); any may be null
 };
+template <typename R> struct Fields<LwdRatPost<R>> { using S = LwdRatPost<R>;
+    GR_TABLE(out, GEOSRAD_LWD_NRATOUT, &S::flxu_rat, &S::flxd_rat, &S::flx_rat, &S::dfdts_rat, &S::sfcem_rat);
+};
 template <typename R> __global__ void __launch_bounds__(256) k_lwd_rat_post(LwdRatPost<R> P)
 {
 #pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
@@ -225,6 +261,10 @@ template <typename R> struct LwRatUpd {
     R *dolr, *dlws, *dflns, *dsfcem, *nettrap;            // (ncol,nrats)
     R *coltrap;                                           // (ncol,LM,nrats)
     R *flx, *dfdts_out;                                   // (ncol,0:LM,nrats)
+};
+template <typename R> struct Fields<LwRatUpd<R>> { using S = LwRatUpd<R>;
+    GR_TABLE(in, GEOSRAD_LWR_NIN, &S::flx_int, &S::sfcem_int, &S::dfdts, &S::flx_rat, &S::sfcem_rat, &S::dfdts_rat);
+    GR_TABLE(out, GEOSRAD_LWR_NOUT, &S::dolr, &S::dlws, &S::dflns, &S::dsfcem, &S::nettrap, &S::coltrap, &S::flx, &S::dfdts_out);
 };
 template <typename R> __global__ void __launch_bounds__(256) k_lw_update_rats(LwRatUpd<R> P)
 {
@@ -297,6 +337,10 @@ template <typename R> struct LwcPost {
     R *sfcem_int;                                                         // in: as irrad leaves it (negative); out: positive
     R *flx_int, *flxa_int, *flc_int, *fla_int, *dfdtsc, *dfdtsna, *dfdtscna, *ts_int;
 };
+template <typename R> struct Fields<LwcPost<R>> { using S = LwcPost<R>;
+    GR_TABLE(in, GEOSRAD_LWC_NIN, &S::flxu, &S::flcu, &S::flau, &S::flxau, &S::flxd, &S::flcd, &S::flad, &S::flxad, &S::dfdts, &S::ts);
+    GR_TABLE(out, GEOSRAD_LWC_NOUT, &S::sfcem_int, &S::flx_int, &S::flxa_int, &S::flc_int, &S::fla_int, &S::dfdtsc, &S::dfdtsna, &S::dfdtscna, &S::ts_int);
+};
 template <typename R> __global__ void __launch_bounds__(256) k_lwd_chou_post(LwcPost<R> P)
 {
 #pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
@@ -336,6 +380,11 @@ template <typename R> struct SwcLit : SwcPrep<R> {
     const int32_t *lit;
     const R *lay_in[3], *aer_in[3], *col_in[5];      // T Q CL; TAUA SSAA ASYA (all three or none); ZT ALBVR ALBVF ALBNR ALBNF
     R *lay_out[3], *aer_out[3], *col_out[5];
+};
+template <typename R> struct Fields<SwcLit<R>> { using S = SwcLit<R>;
+    GR_TABLE(in, GEOSRAD_SWC_NIN, &S::ple, elem<&S::lay_in, 0>, elem<&S::lay_in, 1>, &S::ox, elem<&S::lay_in, 2>, elem<&S::q, 0>, elem<&S::q, 1>,
+             elem<&S::q, 2>, elem<&S::q, 3>, elem<&S::r, 0>, elem<&S::r, 1>, elem<&S::r, 2>, elem<&S::r, 3>, elem<&S::aer_in, 0>, elem<&S::aer_in, 1>,
+             elem<&S::aer_in, 2>, elem<&S::col_in, 0>, elem<&S::col_in, 1>, elem<&S::col_in, 2>, elem<&S::col_in, 3>, elem<&S::col_in, 4>);
 };
 template <typename R, bool LIT> using SwcPrepOf = std::conditional_t<LIT, SwcLit<R>, SwcPrep<R>>;
 template <typename R, bool LIT = false> __global__ void __launch_bounds__(256) k_swc_prep(SwcPrepOf<R, LIT> P)
@@ -403,6 +452,14 @@ template <typename R> struct LwUpd {
         *sfcem0, *tsreff, *cldtt;
 };
 
+template <typename R> struct Fields<LwUpd<R>> { using S = LwUpd<R>;
+    GR_TABLE(in, GEOSRAD_LWU_NIN, &S::tsinst, &S::ts_int, &S::sfcem_int, &S::fcld, &S::flx_int, &S::flxa_int, &S::flc_int, &S::fla_int, &S::flxu_int,
+             &S::flxau_int, &S::flcu_int, &S::flau_int, &S::flxd_int, &S::flxad_int, &S::flcd_int, &S::flad_int, &S::dfdts, &S::dfdtsna, &S::dfdtsc,
+             &S::dfdtscna);
+    GR_TABLE(out, GEOSRAD_LWU_NOUT, &S::flx, &S::flxa, &S::flc, &S::fla, &S::flxu, &S::flxau, &S::flcu, &S::flau, &S::flxd, &S::flxad, &S::flcd, &S::flad,
+             &S::olr, &S::olra, &S::olc, &S::ola, &S::olcc5, &S::dsfdts, &S::sfcem, &S::lws, &S::lwsa, &S::lcs, &S::las, &S::lcsc5, &S::flns, &S::flnsna,
+             &S::flnsc, &S::flnsa, &S::dsfdts0, &S::sfcem0, &S::tsreff, &S::cldtt);
+};
 // V consecutive columns per thread (V = 4 floats / 2 doubles = one 16-byte access when the column count and the field
 // addresses allow, else V = 1): these kernels do nothing but stream, and wide accesses are what keeps enough bytes in flight
 template <typename R, int V> GR_DEV void ldv(const R *__restrict__ p, size_t o, R (&x)[V])
@@ -513,6 +570,9 @@ template <typename R> struct LwkSurf {
     const R *ple, *t, *ts, *emis;
     R *t2m, *fs, *tg, *tv, *eg, *ev, *rv;      // NS = 1: (ncol) x 4, (ncol,10) x 3
 };
+template <typename R> struct Fields<LwkSurf<R>> { using S = LwkSurf<R>;      // the per-layer fields go to irrad as they are
+    GR_TABLE(in, GEOSRAD_LWK_NIN, &S::ple, &S::t, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, &S::ts, &S::emis, {}, {}, {});
+};
 // one thread per (V columns, row): row 0 = T2M, FS, TG, TV; rows 1..10 = band row - 1 of EG, EV, RV
 template <typename R, int V> __global__ void __launch_bounds__(256) k_lwk_surface(LwkSurf<R> P)
 {
@@ -538,6 +598,11 @@ template <typename R> struct LwkDiag {
     R taucrit, undef;                          // TAUCRIT / 2.13 (IRR:3628), MAPL_UNDEF
     const R *taudiag, *t, *ple, *ts, *dfdts, *sfcem_int, *flx_int;      // sfcem_int already positive (IRR:3611)
     R *tauir, *cldtmp, *cldprs, *tsreff, *dsfdts0, *sfcem0, *lws0;
+};
+template <typename R> struct Fields<LwkDiag<R>> { using S = LwkDiag<R>;      // the INTERNAL fluxes are irrad's and k_lwd_chou_post's
+    GR_TABLE(in, GEOSRAD_LWK_NIN, &S::ple, &S::t, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, &S::ts, {}, {}, {}, {});
+    GR_TABLE(out, GEOSRAD_LWK_NOUT, {}, {}, {}, {}, {}, {}, {}, {}, &S::dfdts, &S::sfcem_int, &S::flx_int, {}, {}, {}, {}, {}, {}, {}, &S::tauir, &S::cldtmp,
+             &S::cldprs, &S::tsreff, &S::dsfdts0, &S::sfcem0, &S::lws0, {}, {});
 };
 // one thread per V columns, walking the layers from the top: TAUIR and the first layer whose infrared cloud optical thickness passes
 // the threshold (IRR:3634-3650); the refresh-time exports ride along (IRR:3659-3663)
@@ -602,6 +667,10 @@ template <typename R> struct SwdLit : SwdArgs<R> {
     const int32_t *lit;
     const R *col_in[6];      // ZT ALAT ALBVR ALBVF ALBNR ALBNF
     R *col_out[6];
+};
+template <typename R> struct Fields<SwdLit<R>> { using S = SwdLit<R>;
+    GR_TABLE(in, GEOSRAD_SWD_NIN, &S::ple, &S::pl, &S::t, &S::q, &S::o3, &S::ch4, &S::cl, &S::ts, &S::qq_ice, &S::qq_liq, &S::rr_ice, &S::rr_liq, &S::taua,
+             &S::ssaa, &S::asya, elem<&S::col_in, 0>, elem<&S::col_in, 1>, elem<&S::col_in, 2>, elem<&S::col_in, 3>, elem<&S::col_in, 4>, elem<&S::col_in, 5>);
 };
 template <typename R, bool LIT> using SwdArgsOf = std::conditional_t<LIT, SwdLit<R>, SwdArgs<R>>;
 
@@ -706,6 +775,14 @@ template <typename R> struct SwdPost {
     R *cldts, *cldhs, *cldms, *cldls, *cot[4];
 };
 
+// the aerosol pass, and the no-aerosol pass whose un-flipped fluxes are the FS*NA outputs; the scalars and band fluxes are the solver's own
+template <typename R> struct Fields<SwdPost<R>> { using S = SwdPost<R>;
+    GR_TABLE(out, GEOSRAD_SWD_NOUT, &S::fsw, &S::fsc, &S::fswu, &S::fscu, {}, {}, {}, {}, {}, {}, {}, &S::cldts, &S::cldhs, &S::cldms, &S::cldls,
+             elem<&S::cot, 0>, elem<&S::cot, 1>, elem<&S::cot, 2>, elem<&S::cot, 3>, {}, {}, {}, {}, {});
+};
+template <typename R> struct SwdPostNa { using S = SwdPost<R>;
+    GR_TABLE(out, GEOSRAD_SWD_NOUT, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, &S::fsw, &S::fsc, &S::fswu, &S::fscu, {});
+};
 // the statements of the post step for one (column, level L = model level 0..LM of the un-flipped arrays): the solver's results are read
 // at column ij of n, the outputs written at column c of ld
 template <typename R> GR_DEV void swd_post_cell(const SwdPost<R> &P, int L, int ij, int n, int c, int ld)
@@ -798,6 +875,13 @@ template <typename R> struct SwSfc {
     const R *slr, *zth, *alb_imp[4], *dn[6];          // ALBVF ALBVR ALBNF ALBNR; DRUVRN DFUVRN DRPARN DFPARN DRNIRN DFNIRN
     const R *fswn, *fscn, *fswnan, *fscnan;           // (ncol,0:LM)
     R *alb_exp[4], *albedo, *slrtp, *dx[6], *drn[3], *slrsf, *slrsfc, *slrsfna, *slrsfcna, *slrsuf, *slrsufc, *slrsufna, *slrsufcna;
+};
+template <typename R> struct Fields<SwSfc<R>> { using S = SwSfc<R>;
+    GR_TABLE(in, GEOSRAD_SWS_NIN, &S::slr, &S::zth, elem<&S::alb_imp, 0>, elem<&S::alb_imp, 1>, elem<&S::alb_imp, 2>, elem<&S::alb_imp, 3>, elem<&S::dn, 0>,
+             elem<&S::dn, 1>, elem<&S::dn, 2>, elem<&S::dn, 3>, elem<&S::dn, 4>, elem<&S::dn, 5>, &S::fswn, &S::fscn, &S::fswnan, &S::fscnan);
+    GR_TABLE(out, GEOSRAD_SWS_NOUT, elem<&S::alb_exp, 0>, elem<&S::alb_exp, 1>, elem<&S::alb_exp, 2>, elem<&S::alb_exp, 3>, &S::albedo, &S::slrtp,
+             elem<&S::dx, 0>, elem<&S::dx, 1>, elem<&S::dx, 2>, elem<&S::dx, 3>, elem<&S::dx, 4>, elem<&S::dx, 5>, elem<&S::drn, 0>, elem<&S::drn, 1>,
+             elem<&S::drn, 2>, &S::slrsf, &S::slrsfc, &S::slrsfna, &S::slrsfcna, &S::slrsuf, &S::slrsufc, &S::slrsufna, &S::slrsufcna);
 };
 template <typename R> __global__ void __launch_bounds__(256) k_sw_update_surface(SwSfc<R> U)
 {
@@ -979,6 +1063,13 @@ template <typename R> struct SwUpd {
     R *rsr, *rsc, *rsrna, *rscna, *rsrs, *rscs, *rsrsna, *rscsna, *osr, *osrclr, *osrna, *osrcna;
 };
 
+template <typename R> struct Fields<SwUpd<R>> { using S = SwUpd<R>;
+    GR_TABLE(in, GEOSRAD_SWU_NIN, &S::slr, &S::fswn, &S::fscn, &S::fswnan, &S::fscnan, &S::fswun, &S::fscun, &S::fswunan, &S::fscunan, &S::fswbandn,
+             &S::fswbandnan);
+    GR_TABLE(out, GEOSRAD_SWU_NOUT, &S::fsw, &S::fsc, &S::fswna, &S::fscna, &S::fswu, &S::fscu, &S::fswuna, &S::fscuna, &S::fswd, &S::fscd, &S::fswdna,
+             &S::fscdna, &S::fswband, &S::fswbandna, &S::rsr, &S::rsc, &S::rsrna, &S::rscna, &S::rsrs, &S::rscs, &S::rsrsna, &S::rscsna, &S::osr, &S::osrclr,
+             &S::osrna, &S::osrcna);
+};
 // blockIdx.y = level 0..LM, then the bands; V columns per thread
 template <typename R, int V> __global__ void __launch_bounds__(256) k_sw_update_export(SwUpd<R> U)
 {
@@ -1103,6 +1194,11 @@ template <typename R> struct RadTend {
     R *blw, *alw, *radsrf;
 };
 
+template <typename R> struct Fields<RadTend<R>> { using S = RadTend<R>;
+    GR_TABLE(in, GEOSRAD_RT_NIN, &S::ple, &S::flw, &S::fsw, &S::flwclr, &S::fswclr, &S::fswna, &S::fla, &S::fscna, &S::dsfdts, &S::sfcem, &S::trd);
+    GR_TABLE(out, GEOSRAD_RT_NOUT, &S::dtdt, &S::radlw, &S::radsw, &S::radlwc, &S::radswc, &S::radswna, &S::radlwcna, &S::radswcna, &S::blw, &S::alw,
+             &S::radsrf);
+};
 template <typename R, int V> __global__ void __launch_bounds__(256) k_rad_tendencies(RadTend<R> P)
 {
 #pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
@@ -1137,6 +1233,7 @@ template <typename R, int V> __global__ void __launch_bounds__(256) k_rad_tenden
 
 #undef VFOR
 #undef VSET
+#undef GR_TABLE
 
 // ---------------------------------------------------------------------------------------------------
 // Lit-column compaction of the solar component (GEOS_SolarGridComp.F90:3686 `daytime = ZTH > 0.`, PackIt / UnPackIt :7753-7799):
