@@ -319,21 +319,6 @@ static int default_host_threads()
     return (int)(n < 1 ? 1 : (n > 8 ? 8 : n));
 }
 
-// the un-packed tile of the lit-aware SW drivers (geosrad_sw_driver_*_lit_dev): its columns, geosrad_lit_index_dev's two index arrays
-// (device), UnPackIt's DEFAULT of every output (host) and the outputs whose dark columns keep their values
-struct LitTile {
-    int tile;
-    const int32_t *idx, *pos;
-    const double *dark;
-    uint64_t keep;
-};
-// DRBAND / DFBAND of geosrad_sw_driver_rrtmg_obio*_dev: the two arrays (both or none) and, on a tile, their dark values and keep bits
-struct SwdObio {
-    void *drband, *dfband;
-    const double *dark;
-    int keep;
-};
-
 // ---------------------------------------------------------------------------------------------------
 struct geosrad_ctx {
     int device = 0, real_kind = 4, chunk = 131072;
@@ -603,15 +588,11 @@ struct geosrad_ctx {
                            void *const *aer, void *const *out) = 0;
     virtual int sw_dev(hipStream_t, int, int, double, double, int, In, int, int, int, int, int, int, int, int32_t *, Out, int, const void *, const void *,
                        const void *, Out, void *) { return nodev("geosrad_rrtmg_sw_dev"); }
-    virtual int lw_driver_dev(hipStream_t, int, int, int, In, const double *, int, int, int, int, int, const int32_t *, Out, int, const int32_t *, Out)
-    { return nodev("geosrad_lw_driver_rrtmg_dev"); }      // ... out, nrats, rat_gas, rat_out
-    // lit != nullptr (both SW drivers): `in` / `out` are the un-packed tile's and ncol is NumLit (geosrad_sw_driver_*_lit_dev)
-    virtual int sw_driver_dev(hipStream_t, int, int, int, In, const double *, int, int, double, double, int, int, int, int, int, int, const void *, const void *, Out,
-                              const LitTile *lit, const SwdObio *) { return nodev(lit ? "geosrad_sw_driver_rrtmg_lit_dev" : "geosrad_sw_driver_rrtmg_dev"); }
+    virtual int lw_driver_dev(hipStream_t, const LwdCall &) { return nodev("geosrad_lw_driver_rrtmg_dev"); }
+    virtual int sw_driver_dev(hipStream_t, const SwdCall &C) { return nodev(C.lit ? "geosrad_sw_driver_rrtmg_lit_dev" : "geosrad_sw_driver_rrtmg_dev"); }
+    virtual int sw_driver_chou_dev(hipStream_t, const SwcCall &C) { return nodev(C.lit ? "geosrad_sw_driver_chou_lit_dev" : "geosrad_sw_driver_chou_dev"); }
     virtual int lw_chou_post_dev(hipStream_t, int, int, In, Out) { return nodev("geosrad_lw_chou_post_dev"); }
     virtual int lw_driver_chou_dev(hipStream_t, int, int, In, const double *, int, int, int, int, Out) { return nodev("geosrad_lw_driver_chou_dev"); }
-    virtual int sw_driver_chou_dev(hipStream_t, int, int, In, const double *, int, int, const void *, const void *, int, Out, const LitTile *lit)
-    { return nodev(lit ? "geosrad_sw_driver_chou_lit_dev" : "geosrad_sw_driver_chou_dev"); }
     virtual int lw_update_flx_dev(hipStream_t, int, int, int, int, int, double, In, Out) { return nodev("geosrad_lw_update_flx_dev"); }
     virtual int lw_update_rats_dev(hipStream_t, int, int, int, In, Out) { return nodev("geosrad_lw_update_rats_dev"); }
     virtual int lw_update_bands_dev(hipStream_t, int, const int32_t *, const double *, const double *, double, const void *, const void *, const void *,
@@ -1231,43 +1212,22 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 
-    // the lit-aware SW drivers: the arguments that describe the tile
-    int lit_check(const LitTile &t, int nlit, void *const *out, int nout)
+    // one k_lit_scatter over a tile's outputs (lit_scatter_pack)
+    int lit_scatter(hipStream_t st, const LitScatter<R> &S)
     {
-        if (nlit < 0 || nlit > t.tile) return fail(GEOSRAD_EINVAL, "nlit must lie in 0 .. ncol");
-        if (nlit > 0 && (!t.idx || !t.pos)) return fail(GEOSRAD_EINVAL, "lit_index / lit_pos null");
-        bool fill = false;
-        for (int k = 0; k < nout; k++) fill = fill || (out[k] && !(t.keep >> k & 1));
-        if (fill && (!t.pos || !t.dark)) return fail(GEOSRAD_EINVAL, "an output whose keep bit is clear needs lit_pos and dark");
-        return GEOSRAD_OK;
-    }
-    // one k_lit_scatter over the listed outputs the caller requested: output k from its packed plane of `rows` rows (nullptr with nlit == 0)
-    struct LitField { int k; const R *src; int rows; };
-    using LitFields = std::vector<LitField>;
-    int lit_scatter(hipStream_t st, const LitTile &t, int nlit, void *const *out, const LitFields &fields)
-    {
-        LitScatter<R> S{};
-        S.tile = t.tile; S.nlit = nlit; S.pos = t.pos;
-        for (const LitField &f : fields) {
-            const int keep = (int)(t.keep >> f.k & 1);
-            if (!out[f.k] || (nlit == 0 && keep)) continue;
-            if (S.nf == LIT_NFIELD) return fail(GEOSRAD_EINVAL, "lit_scatter: too many fields");
-            S.f[S.nf].src = f.src; S.f[S.nf].dst = (R *)out[f.k]; S.f[S.nf].row0 = S.rows; S.f[S.nf].keep = keep;
-            S.f[S.nf].dark = t.dark ? (R)t.dark[f.k] : (R)0;
-            S.nf++; S.rows += f.rows;
-        }
-        if (S.nf) hipLaunchKernelGGL((k_lit_scatter<R>), dim3(grid256(t.tile), S.rows), dim3(256), 0, st, S);
+        if (S.nf) hipLaunchKernelGGL((k_lit_scatter<R>), dim3(grid256(S.tile), S.rows), dim3(256), 0, st, S);
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
 
-    int lw_driver_dev(hipStream_t st, int ncol, int lm, int nb, const void *const *in, const double *consts, int iceflg, int liqflg,
-                      int doy, int lcldlm, int lcldmh, const int32_t *band_output, void *const *out, int nrats, const int32_t *rat_gas,
-                      void *const *rat_out) override
+    int lw_driver_dev(hipStream_t st, const LwdCall &C) override
     {
         HIPCHK(hipSetDevice(device));
-        if (ncol <= 0 || lm < 4 || nb < 0 || nb > 16) return fail(GEOSRAD_EINVAL, "bad ncol/lm/nb_aer");
-        if (nrats < 0 || nrats > GEOSRAD_RAT_NGAS || (nrats > 0 && (!rat_gas || !rat_out))) return fail(GEOSRAD_EINVAL, "bad RATS arguments");
+        const int ncol = C.ncol, lm = C.lm, nrats = C.nrats, iceflg = C.iceflg, liqflg = C.liqflg;
+        const void *const *in = C.in;
+        void *const *out = C.out;
+        if (ncol <= 0 || lm < 4 || C.nb < 0 || C.nb > 16) return fail(GEOSRAD_EINVAL, "bad ncol/lm/nb_aer");
+        if (nrats < 0 || nrats > GEOSRAD_RAT_NGAS || (nrats > 0 && (!C.rat_gas || !C.rat_out))) return fail(GEOSRAD_EINVAL, "bad RATS arguments");
         for (int k = 0; k < GEOSRAD_LWD_NIN; k++)
             if (!in[k] && k != GEOSRAD_LWD_CO2_3D && k != GEOSRAD_LWD_TAUA && k != GEOSRAD_LWD_SSAA) return fail(GEOSRAD_EINVAL, "null input array");
         if ((in[GEOSRAD_LWD_TAUA] == nullptr) != (in[GEOSRAD_LWD_SSAA] == nullptr)) return fail(GEOSRAD_EINVAL, "TAUA and SSAA go together");
@@ -1287,13 +1247,13 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (const int rc = drv_reserve(0, carve(Carve()))) return rc;
         carve(Carve(d_ws_drvs[0]));
         LwdArgs<R> A{};
-        A.ncol = ncol; A.lm = lm; A.nb = in[GEOSRAD_LWD_TAUA] ? nb : 0; A.iceflg = iceflg; A.liqflg = liqflg;
+        A.ncol = ncol; A.lm = lm; A.nb = in[GEOSRAD_LWD_TAUA] ? C.nb : 0; A.iceflg = iceflg; A.liqflg = liqflg;
         bind_in<Fields<LwdArgs<R>>>(A, in);
-        A.co2_fixed = (R)consts[GEOSRAD_LWD_C_CO2_FIXED]; A.o2 = (R)consts[GEOSRAD_LWD_C_O2]; A.ccl4 = (R)consts[GEOSRAD_LWD_C_CCL4];
+        A.co2_fixed = (R)C.consts[GEOSRAD_LWD_C_CO2_FIXED]; A.o2 = (R)C.consts[GEOSRAD_LWD_C_O2]; A.ccl4 = (R)C.consts[GEOSRAD_LWD_C_CCL4];
         // (MAPL_AIRMW/MAPL_H2OMW), (MAPL_AIRMW/MAPL_O3MW): constant expressions of the caller's real kind
-        A.airmw_over_h2omw = (R)consts[GEOSRAD_C_AIRMW] / (R)consts[GEOSRAD_C_H2OMW];
-        A.airmw_over_o3mw = (R)consts[GEOSRAD_C_AIRMW] / (R)consts[GEOSRAD_C_O3MW];
-        A.rgas = (R)consts[GEOSRAD_C_RGAS]; A.grav = (R)consts[GEOSRAD_C_GRAV];
+        A.airmw_over_h2omw = (R)C.consts[GEOSRAD_C_AIRMW] / (R)C.consts[GEOSRAD_C_H2OMW];
+        A.airmw_over_o3mw = (R)C.consts[GEOSRAD_C_AIRMW] / (R)C.consts[GEOSRAD_C_O3MW];
+        A.rgas = (R)C.consts[GEOSRAD_C_RGAS]; A.grav = (R)C.consts[GEOSRAD_C_GRAV];
         A.play = lay[0]; A.tlay = lay[1]; A.h2o = lay[2]; A.o3_r = lay[3]; A.co2_r = lay[4]; A.ch4_r = lay[5];
         A.n2o_r = lay[6]; A.o2_r = lay[7]; A.cfc11_r = lay[8]; A.cfc12_r = lay[9]; A.cfc22_r = lay[10];
         A.ccl4_r = lay[11]; A.cldf = lay[12]; A.ciwp = lay[13]; A.clwp = lay[14]; A.rei = lay[15];
@@ -1304,7 +1264,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         hipLaunchKernelGGL((k_lwd_prep<R>), dim3(gx, lm), blk, 0, st, A);
         hipLaunchKernelGGL((k_lwd_zm<R>), dim3(gx), blk, 0, st, A);
         // reverse the super-layer interface indices (IRR:3237-3239) and call the solver with Ts_derivs = .true.
-        const int cloudMH = lm - lcldmh + 1, cloudLM = lm - lcldlm + 1;
+        const int cloudMH = lm - C.lcldmh + 1, cloudLM = lm - C.lcldlm + 1;
         const void *lin[I_NIN];
         lin[I_PLAY] = A.play; lin[I_PLEV] = A.plev; lin[I_TLAY] = A.tlay; lin[I_TLEV] = A.tlev; lin[I_TSFC] = A.tsfc; lin[I_EMIS] = A.emis_r;
         lin[I_H2O] = A.h2o; lin[I_O3] = A.o3_r; lin[I_CO2] = A.co2_r; lin[I_CH4] = A.ch4_r; lin[I_N2O] = A.n2o_r; lin[I_O2] = A.o2_r;
@@ -1317,13 +1277,13 @@ template <typename R> struct Ctx : geosrad_ctx {
         static const int32_t no_bands[16] = {0};
         LwRats RT{};
         RT.n = nrats; RT.uflx = rat[0]; RT.dflx = rat[1]; RT.duflx_dTs = rat[2];
-        for (int r = 0; r < nrats; r++) RT.gas[r] = rat_gas[r];
-        if (const int rc = lw_dev(st, ncol, lm, 1, lin, iceflg, liqflg, doy, cloudLM, cloudMH, cc, lout, band_output ? band_output : no_bands,
+        for (int r = 0; r < nrats; r++) RT.gas[r] = C.rat_gas[r];
+        if (const int rc = lw_dev(st, ncol, lm, 1, lin, iceflg, liqflg, C.doy, cloudLM, cloudMH, cc, lout, C.band_output ? C.band_output : no_bands,
                                   nullptr, nullptr, nrats > 0 ? &RT : nullptr)) return rc;
         if (nrats > 0) {
             LwdRatPost<R> RP{};
             RP.ncol = ncol; RP.lm = lm; RP.nrats = nrats; RP.uflx = rat[0]; RP.dflx = rat[1]; RP.duflx = rat[2]; RP.emis = A.emis;
-            bind_out<Fields<LwdRatPost<R>>>(RP, rat_out);
+            bind_out<Fields<LwdRatPost<R>>>(RP, C.rat_out);
             hipLaunchKernelGGL((k_lwd_rat_post<R>), dim3(gx, lm + 1, nrats), blk, 0, st, RP);
         }
         LwdPost<R> Q{};
@@ -1336,64 +1296,46 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 
-    int sw_driver_dev(hipStream_t st, int ncol, int lm, int nb, const void *const *in, const double *consts, int iceflg, int liqflg,
-                      double sc, double dist, int isolvar, int dyofyr, int include_aerosols, int lcldlm, int lcldmh, int normflx,
-                      const void *bndsolvar, const void *indsolvar, void *const *out, const LitTile *lit, const SwdObio *obio) override
+    // lit != nullptr (both SW drivers): `in` / `out` are the un-packed tile's and ncol is NumLit (geosrad_sw_driver_*_lit_dev)
+    int sw_driver_dev(hipStream_t st, const SwdCall &C) override
     {
         HIPCHK(hipSetDevice(device));
+        const int ncol = C.ncol, lm = C.lm, nb = C.nb, iceflg = C.iceflg, liqflg = C.liqflg;
+        const void *const *in = C.in;
+        void *const *out = C.out;
+        const LitTile *lit = C.lit;
+        const bool drf = C.drf();
         if ((lit ? lit->tile : ncol) <= 0 || lm < 4 || nb < 0 || nb > 14) return fail(GEOSRAD_EINVAL, "bad ncol/lm/nb_aer");
-        if (lit) if (const int rc = lit_check(*lit, ncol, out, GEOSRAD_SWD_NOUT)) return rc;
-        if (obio && !obio->drband != !obio->dfband) return fail(GEOSRAD_EINVAL, "DRBAND and DFBAND go together");
-        // do_drfband = SOLAR_TO_OBIO .and. include_aerosols (SOL:6385): without aerosols the two arrays are not touched at all
-        const bool drf = obio && obio->drband && include_aerosols != 0;
-        if (drf && lit && (obio->keep & 3) != 3 && (!lit->pos || !obio->dark))
+        if (lit) if (const char *msg = lit_check(*lit, ncol, out, GEOSRAD_SWD_NOUT)) return fail(GEOSRAD_EINVAL, msg);
+        if (!C.drband != !C.dfband) return fail(GEOSRAD_EINVAL, "DRBAND and DFBAND go together");
+        if (drf && lit && (C.keep_obio & 3) != 3 && (!lit->pos || !C.dark_obio))
             return fail(GEOSRAD_EINVAL, "DRBAND / DFBAND with a clear keep bit need lit_pos and dark_obio");
-        // the tile's scatter list with DRBAND, DFBAND as outputs GEOSRAD_SWD_NOUT, + 1
-        enum { X_DRBAND = GEOSRAD_SWD_NOUT, X_DFBAND, X_NOUT };
-        void *xout[X_NOUT];
-        double xdark[X_NOUT];
-        LitTile xl{};
-        if (lit) {
-            xl = *lit;
-            for (int k = 0; k < GEOSRAD_SWD_NOUT; k++) { xout[k] = out[k]; xdark[k] = lit->dark ? lit->dark[k] : 0.0; }
-            xout[X_DRBAND] = drf ? obio->drband : nullptr; xout[X_DFBAND] = drf ? obio->dfband : nullptr;
-            for (int k = 0; k < 2; k++) xdark[X_DRBAND + k] = drf && obio->dark ? obio->dark[k] : 0.0;
-            xl.dark = xdark;
-            xl.keep = (lit->keep & ((1ull << GEOSRAD_SWD_NOUT) - 1)) | (drf ? (uint64_t)(obio->keep & 3) << GEOSRAD_SWD_NOUT : 0);
-        }
         // SORADCORE asserts the solar-variability options it supports before the call (GEOS_SolarGridComp.F90:6286-6292): no isolvar 1
-        if (isolvar == 1) return fail(GEOSRAD_EINPUT, "SORADCORE: ISOLVAR == 1 is not supported by the GridComp (the solver entry point rrtmg_sw accepts it)");
+        if (C.isolvar == 1) return fail(GEOSRAD_EINPUT, "SORADCORE: ISOLVAR == 1 is not supported by the GridComp (the solver entry point rrtmg_sw accepts it)");
         for (int k = 0; k < GEOSRAD_SWD_NIN; k++)
             if (!in[k] && k != GEOSRAD_SWD_TAUA && k != GEOSRAD_SWD_SSAA && k != GEOSRAD_SWD_ASYA) return fail(GEOSRAD_EINVAL, "null input array");
         const bool aer = in[GEOSRAD_SWD_TAUA] != nullptr;
         if (aer && (!in[GEOSRAD_SWD_SSAA] || !in[GEOSRAD_SWD_ASYA])) return fail(GEOSRAD_EINVAL, "TAUA, SSAA and ASYA go together");
         if (aer && nb != 14) return fail(GEOSRAD_EINVAL, "RRTMG_SW aerosol arrays have 14 bands");
-        auto rows = [lm](int k) {      // of output k
-            return k <= GEOSRAD_SWD_FSCU || (k >= GEOSRAD_SWD_FSWNA && k <= GEOSRAD_SWD_FSCUNA) ? lm + 1
-                   : (k == GEOSRAD_SWD_FSWBAND || k == GEOSRAD_SWD_FSWBANDNA ? 14 : 1);
-        };
+        const LitTile xl{lit ? lit->tile : 0, lit ? lit->idx : nullptr, lit ? lit->pos : nullptr, C.dark, C.keep};      // the tile with DRBAND, DFBAND as rows
         if (lit) {      // what rrtmg_sw would reject, before anything is launched
-            if (const int rc = sw_check_options(1, lm, iceflg, liqflg, lm - lcldlm + 1, lm - lcldmh + 1, 10)) return rc;
+            if (const int rc = sw_check_options(1, lm, iceflg, liqflg, lm - C.lcldlm + 1, lm - C.lcldmh + 1, 10)) return rc;
             SwSolar<R> SV;
-            if (const int rc = sw_solar(sc, dist, isolvar, (const R *)bndsolvar, (const R *)indsolvar, nullptr, SV)) return rc;
+            if (const int rc = sw_solar(C.sc, C.dist, C.isolvar, (const R *)C.bndsolvar, (const R *)C.indsolvar, nullptr, SV)) return rc;
         }
-        if (lit && ncol == 0) {        // no daytime column: the dark fill alone
-            LitFields F;
-            for (int k = 0; k < GEOSRAD_SWD_NOUT; k++) F.push_back({k, nullptr, rows(k)});
-            if (drf) for (int k = X_DRBAND; k < X_NOUT; k++) F.push_back({k, nullptr, 14});
-            return lit_scatter(st, xl, 0, xout, F);
-        }
+        if (lit && ncol == 0) return lit_scatter(st, lit_scatter_pack<R>(swd_tile, SWD_NROW, lm, xl, 0, C.rows, nullptr));      // no daytime column: the dark fill
         const size_t n = (size_t)ncol, cl = n * lm, cv = n * (lm + 1);
         const bool want_na = out[GEOSRAD_SWD_FSWNA] || out[GEOSRAD_SWD_FSCNA] || out[GEOSRAD_SWD_FSWUNA] || out[GEOSRAD_SWD_FSCUNA] ||
                              out[GEOSRAD_SWD_FSWBANDNA];
-        R *lay[13], *lev[2], *aerp[3], *flux[4], *scal[6], *cot[8], *band, *nflux[4] = {}, *nsc[14] = {}, *nband = nullptr, *col[6] = {}, *drfb[2] = {};
+        R *lay[13], *lev[2], *aerp[3], *flux[4], *cot[8], *nflux[4] = {}, *nsc[14] = {}, *col[6] = {}, *plane[SWD_NPLANE] = {};
+        R **scal = plane, *&band = plane[SWD_P_BAND], *&nband = plane[SWD_P_NBAND], **drfb = plane + SWD_P_DRBAND;      // the planes of swd_tile
         int32_t *cc;
         auto carve = [&](Carve c) {
             for (auto &q : lay) q = c.take<R>(cl);
             for (auto &q : lev) q = c.take<R>(cv);
             for (auto &q : aerp) q = c.take<R>(cl * 14);
             for (auto &q : flux) q = c.take<R>(cv);
-            for (auto &q : scal) q = c.take<R>(n);
+            for (int k = 0; k < 6; k++) scal[k] = c.take<R>(n);
             for (auto &q : cot) q = c.take<R>(n);
             band = c.take<R>(n * 14);
             cc = (int32_t *)c.take<R>(n * 4);      // clearCounts (ncol, 4) int32 in 4 n reals, as in lw_driver_dev
@@ -1403,7 +1345,7 @@ template <typename R> struct Ctx : geosrad_ctx {
                 nband = c.take<R>(n * 14);
             }
             if (lit) for (auto &q : col) q = c.take<R>(n);      // the packed per-column imports the solver reads as they are
-            if (lit && drf) for (auto &q : drfb) q = c.take<R>(n * 14);      // DRBAND, DFBAND of the packed columns
+            if (lit && drf) for (int k = 0; k < 2; k++) drfb[k] = c.take<R>(n * 14);      // DRBAND, DFBAND of the packed columns
             return c.off;
         };
         if (const int rc = drv_reserve(1, carve(Carve()))) return rc;
@@ -1412,10 +1354,10 @@ template <typename R> struct Ctx : geosrad_ctx {
         SwdArgs<R> &A = AL;
         A.ncol = ncol; A.lm = lm; A.nb = 14; A.iceflg = iceflg; A.liqflg = liqflg;
         bind_in<Fields<SwdLit<R>>>(AL, in);
-        A.co2 = (R)consts[GEOSRAD_SWD_C_CO2]; A.o2 = (R)consts[GEOSRAD_SWD_C_O2];
-        A.airmw_over_h2omw = (R)consts[GEOSRAD_SWD_C_AIRMW] / (R)consts[GEOSRAD_SWD_C_H2OMW];
-        A.airmw_over_o3mw = (R)consts[GEOSRAD_SWD_C_AIRMW] / (R)consts[GEOSRAD_SWD_C_O3MW];
-        A.rgas = (R)consts[GEOSRAD_SWD_C_RGAS]; A.grav = (R)consts[GEOSRAD_SWD_C_GRAV];
+        A.co2 = (R)C.consts[GEOSRAD_SWD_C_CO2]; A.o2 = (R)C.consts[GEOSRAD_SWD_C_O2];
+        A.airmw_over_h2omw = (R)C.consts[GEOSRAD_SWD_C_AIRMW] / (R)C.consts[GEOSRAD_SWD_C_H2OMW];
+        A.airmw_over_o3mw = (R)C.consts[GEOSRAD_SWD_C_AIRMW] / (R)C.consts[GEOSRAD_SWD_C_O3MW];
+        A.rgas = (R)C.consts[GEOSRAD_SWD_C_RGAS]; A.grav = (R)C.consts[GEOSRAD_SWD_C_GRAV];
         A.play = lay[0]; A.tlay = lay[1]; A.h2o = lay[2]; A.o3_r = lay[3]; A.co2_r = lay[4]; A.ch4_r = lay[5];
         A.o2_r = lay[6]; A.cldf = lay[7]; A.ciwp = lay[8]; A.clwp = lay[9]; A.rei = lay[10]; A.rel = lay[11];
         A.zl = lay[12]; A.plev = lev[0]; A.tlev = lev[1]; A.tauaer = aerp[0]; A.ssaaer = aerp[1]; A.asmaer = aerp[2];
@@ -1437,13 +1379,12 @@ template <typename R> struct Ctx : geosrad_ctx {
         sin[S_ALDIR] = cin[4]; sin[S_ALDIF] = cin[5];
         void *sout[SO_NOUT] = {};
         for (int k = 0; k < 4; k++) sout[SO_UFLX + k] = flux[k];
-        const int sc_ix[6] = {GEOSRAD_SWD_NIRR, GEOSRAD_SWD_NIRF, GEOSRAD_SWD_PARR, GEOSRAD_SWD_PARF, GEOSRAD_SWD_UVRR, GEOSRAD_SWD_UVRF};
         // what the solver writes as the driver returns it goes straight to the caller's packed arrays; a tile's takes the workspace planes
         auto direct = [&](int k, R *plane) { return out[k] && !lit ? out[k] : (void *)plane; };
-        for (int k = 0; k < 6; k++) sout[SO_NIRR + k] = direct(sc_ix[k], scal[k]);
+        for (int k = 0; k < 6; k++) sout[SO_NIRR + k] = direct(GEOSRAD_SWD_NIRR + k, scal[k]);
         sout[SO_FSWBAND] = direct(GEOSRAD_SWD_FSWBAND, band);
         for (int k = 0; k < 8; k++) sout[SO_COT0 + k] = cot[k];      // cotd t/h/m/l then cotn t/h/m/l
-        if (drf) { sout[SO_DRBAND] = lit ? (void *)drfb[0] : obio->drband; sout[SO_DFBAND] = lit ? (void *)drfb[1] : obio->dfband; }
+        if (drf) { sout[SO_DRBAND] = lit ? (void *)drfb[0] : C.drband; sout[SO_DFBAND] = lit ? (void *)drfb[1] : C.dfband; }
         // IAER = 10 always (SOL:6235; without aerosols the arrays are zero); super-layer indices flipped in the call (SOL:6341)
         void *nout[SO_NOUT] = {};
         if (want_na) {
@@ -1452,26 +1393,19 @@ template <typename R> struct Ctx : geosrad_ctx {
             for (int k = 0; k < 8; k++) nout[SO_COT0 + k] = nsc[6 + k];
             nout[SO_FSWBAND] = direct(GEOSRAD_SWD_FSWBANDNA, nband);
         }
-        if (const int rc = sw_run(st, ncol, lm, sc, dist, isolvar, sin, iceflg, liqflg, dyofyr, 10, lm - lcldlm + 1, lm - lcldmh + 1,
-                                  normflx, cc, sout, drf ? 1 : 0, bndsolvar, indsolvar, nullptr, nullptr, want_na ? nout : nullptr)) return rc;
+        if (const int rc = sw_run(st, ncol, lm, C.sc, C.dist, C.isolvar, sin, iceflg, liqflg, C.dyofyr, 10, lm - C.lcldlm + 1, lm - C.lcldmh + 1,
+                                  C.normflx, cc, sout, drf ? 1 : 0, C.bndsolvar, C.indsolvar, nullptr, nullptr, want_na ? nout : nullptr)) return rc;
         SwdPostLit<R> QL{};
         SwdPost<R> &Q = QL;
-        Q.ncol = ncol; Q.lm = lm; Q.ngpt = NG_SW; Q.aerosols = include_aerosols; Q.undef = (R)consts[GEOSRAD_SWD_C_UNDEF];
+        Q.ncol = ncol; Q.lm = lm; Q.ngpt = NG_SW; Q.aerosols = C.include_aerosols; Q.undef = (R)C.consts[GEOSRAD_SWD_C_UNDEF];
         Q.swuflx = flux[0]; Q.swdflx = flux[1]; Q.swuflxc = flux[2]; Q.swdflxc = flux[3]; Q.clearCounts = cc;
         for (int k = 0; k < 4; k++) { Q.cotd[k] = cot[k]; Q.cotn[k] = cot[4 + k]; }
         bind_out<Fields<SwdPost<R>>>(Q, out);
-        // k_swd_post_lit's dark values and keep bits, from the outputs its slots stand for (-1: none)
-        auto post_lit = [&](SwdPostLit<R> &P, std::initializer_list<int> ix) {
-            P.tile = lit->tile; P.pos = lit->pos; P.keep = 0;
-            int s = 0;
-            for (const int k : ix) {
-                if (k >= 0 && (lit->keep >> k & 1)) P.keep |= 1u << s;
-                P.dark[s++] = k >= 0 && lit->dark ? (R)lit->dark[k] : (R)0;
-            }
+        auto post_lit = [&](SwdPostLit<R> &P, TileSrc pass) {
+            post_lit_pack(P, pass, xl);
             hipLaunchKernelGGL((k_swd_post_lit<R>), dim3(grid256(lit->tile), lm + 1), blk, 0, st, P);
         };
-        if (lit) post_lit(QL, {GEOSRAD_SWD_FSW, GEOSRAD_SWD_FSC, GEOSRAD_SWD_FSWU, GEOSRAD_SWD_FSCU, GEOSRAD_SWD_CLDTS, GEOSRAD_SWD_CLDHS,
-                               GEOSRAD_SWD_CLDMS, GEOSRAD_SWD_CLDLS, GEOSRAD_SWD_COTTP, GEOSRAD_SWD_COTHP, GEOSRAD_SWD_COTMP, GEOSRAD_SWD_COTLP});
+        if (lit) post_lit(QL, POST);
         else hipLaunchKernelGGL((k_swd_post<R>), dim3(gx, lm + 1), blk, 0, st, Q);
         if (want_na) {      // un-flip of the no-aerosol fluxes (the FS*NAN internals, SOL:4152-4159)
             SwdPostLit<R> NL{};
@@ -1479,17 +1413,10 @@ template <typename R> struct Ctx : geosrad_ctx {
             N.ncol = ncol; N.lm = lm; N.ngpt = NG_SW; N.aerosols = 0; N.undef = Q.undef;
             N.swuflx = nflux[0]; N.swdflx = nflux[1]; N.swuflxc = nflux[2]; N.swdflxc = nflux[3]; N.clearCounts = cc;
             bind_out<SwdPostNa<R>>(N, out);
-            if (lit) post_lit(NL, {GEOSRAD_SWD_FSWNA, GEOSRAD_SWD_FSCNA, GEOSRAD_SWD_FSWUNA, GEOSRAD_SWD_FSCUNA, -1, -1, -1, -1, -1, -1, -1, -1});
+            if (lit) post_lit(NL, POST_NA);
             else hipLaunchKernelGGL((k_swd_post<R>), dim3(gx, lm + 1), blk, 0, st, N);
         }
-        if (lit) {      // the results the solver wrote as the driver returns them
-            LitFields F;
-            for (int k = 0; k < 6; k++) F.push_back({sc_ix[k], scal[k], 1});
-            F.push_back({GEOSRAD_SWD_FSWBAND, band, 14});
-            if (want_na) F.push_back({GEOSRAD_SWD_FSWBANDNA, nband, 14});
-            if (drf) for (int k = 0; k < 2; k++) F.push_back({X_DRBAND + k, drfb[k], 14});
-            if (const int rc = lit_scatter(st, xl, ncol, xout, F)) return rc;
-        }
+        if (lit) return lit_scatter(st, lit_scatter_pack<R>(swd_tile, SWD_NROW, lm, xl, ncol, C.rows, plane));      // the results the solver wrote as returned
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1583,28 +1510,25 @@ template <typename R> struct Ctx : geosrad_ctx {
     // Chou-Suarez branch of SORADCORE: k_swc_prep + sorad_dev.  The prepared arrays live in a buffer of their own (sorad_dev's scratch is
     // sized per chunk, these per call).  On a tile (lit) that buffer also holds, NumLit wide, the imports sorad reads as they are and all its
     // results, which one k_lit_scatter takes to the tile.
-    int sw_driver_chou_dev(hipStream_t st, int ncol, int lm, const void *const *in, const double *consts, int lcldmh, int lcldlm,
-                           const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out, const LitTile *lit) override
+    int sw_driver_chou_dev(hipStream_t st, const SwcCall &C) override
     {
         HIPCHK(hipSetDevice(device));
+        const int ncol = C.ncol, lm = C.lm, nres = C.do_drfband ? GEOSRAD_SWC_NOUT : GEOSRAD_SWC_DRBAND;      // results sorad writes
+        const void *const *in = C.in;
+        void *const *out = C.out;
+        const LitTile *lit = C.lit;
         if ((lit ? lit->tile : ncol) <= 0 || lm < 4) return fail(GEOSRAD_EINVAL, "bad ncol/lm");
-        if (!consts) return fail(GEOSRAD_EINVAL, "consts null");
+        if (!C.consts) return fail(GEOSRAD_EINVAL, "consts null");
         const bool aer = in[GEOSRAD_SWC_TAUA] != nullptr;
         if (aer != (in[GEOSRAD_SWC_SSAA] != nullptr) || aer != (in[GEOSRAD_SWC_ASYA] != nullptr))
             return fail(GEOSRAD_EINVAL, "TAUA / SSAA / ASYA: all three or none");
         for (int k = 0; k < GEOSRAD_SWC_NIN; k++)
             if (!in[k] && !(k >= GEOSRAD_SWC_TAUA && k <= GEOSRAD_SWC_ASYA)) return fail(GEOSRAD_EINVAL, "null input field");
-        const int nres = do_drfband ? GEOSRAD_SWC_NOUT : GEOSRAD_SWC_DRBAND;      // results sorad writes
-        if (lit) if (const int rc = lit_check(*lit, ncol, out, nres)) return rc;
-        auto rows = [lm](int k) { return k <= GEOSRAD_SWC_FSCU ? lm + 1 : (k >= GEOSRAD_SWC_FSWBAND ? 8 : 1); };
+        if (lit) if (const char *msg = lit_check(*lit, ncol, out, nres)) return fail(GEOSRAD_EINVAL, msg);
         if (lit) {      // what sorad_dev would reject, before anything is launched
-            if (const int rc = sorad_check_options(1, lm, 8, lcldmh, lcldlm, hk_uv, hk_ir)) return rc;
+            if (const int rc = sorad_check_options(1, lm, 8, C.lcldmh, C.lcldlm, C.hk_uv, C.hk_ir)) return rc;
             for (int k = 0; k < nres; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
-            if (ncol == 0) {
-                LitFields F;
-                for (int k = 0; k < nres; k++) F.push_back({k, nullptr, rows(k)});
-                return lit_scatter(st, *lit, 0, out, F);
-            }
+            if (ncol == 0) return lit_scatter(st, lit_scatter_pack<R>(swc_tile, nres, lm, *lit, 0, out, nullptr));
         }
         const size_t n = (size_t)ncol, cl = (size_t)lm * ncol;
         SwcLit<R> PL{};
@@ -1618,7 +1542,7 @@ template <typename R> struct Ctx : geosrad_ctx {
                 for (auto &q : PL.lay_out) q = c.take<R>(cl);
                 if (aer) for (auto &q : PL.aer_out) q = c.take<R>(8 * cl);
                 for (auto &q : PL.col_out) q = c.take<R>(n);
-                for (int k = 0; k < nres; k++) res[k] = c.take<R>(n * rows(k));
+                for (int k = 0; k < nres; k++) res[k] = c.take<R>(n * swc_tile[k].nrows(lm));
             }
             return c.off;
         };
@@ -1626,7 +1550,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         carve(Carve(d_ws_swc));
         P.ncol = ncol; P.lm = lm;
         bind_in<Fields<SwcLit<R>>>(PL, in);
-        P.o3fac = (R)consts[GEOSRAD_SWC_C_O3MW] / (R)consts[GEOSRAD_SWC_C_AIRMW]; P.undef = (R)consts[GEOSRAD_SWC_C_UNDEF];
+        P.o3fac = (R)C.consts[GEOSRAD_SWC_C_O3MW] / (R)C.consts[GEOSRAD_SWC_C_AIRMW]; P.undef = (R)C.consts[GEOSRAD_SWC_C_UNDEF];
         // T Q CL, TAUA SSAA ASYA, ZT ALBVR ALBVF ALBNR ALBNF: the caller's packed arrays, or the tile's gathered by the prep kernel
         const void *lay[3], *aerp[3], *col[5];
         for (int k = 0; k < 3; k++) { lay[k] = lit ? PL.lay_out[k] : PL.lay_in[k]; aerp[k] = !aer ? zero : (lit ? PL.aer_out[k] : PL.aer_in[k]); }
@@ -1648,11 +1572,9 @@ template <typename R> struct Ctx : geosrad_ctx {
         so[SOO_FDIRIR] = O(GEOSRAD_SWC_NIRR); so[SOO_FDIFIR] = O(GEOSRAD_SWC_NIRF); so[SOO_FDIRPAR] = O(GEOSRAD_SWC_PARR);
         so[SOO_FDIFPAR] = O(GEOSRAD_SWC_PARF); so[SOO_FDIRUV] = O(GEOSRAD_SWC_UVRR); so[SOO_FDIFUV] = O(GEOSRAD_SWC_UVRF);
         so[SOO_SFCBAND] = O(GEOSRAD_SWC_FSWBAND); so[SOO_DRBAND] = O(GEOSRAD_SWC_DRBAND); so[SOO_DFBAND] = O(GEOSRAD_SWC_DFBAND);
-        if (const int rc = sorad_dev(st, ncol, lm, 8, si, consts[GEOSRAD_SWC_C_CO2], lcldmh, lcldlm, hk_uv, hk_ir, so, do_drfband)) return rc;
+        if (const int rc = sorad_dev(st, ncol, lm, 8, si, C.consts[GEOSRAD_SWC_C_CO2], C.lcldmh, C.lcldlm, C.hk_uv, C.hk_ir, so, C.do_drfband)) return rc;
         if (!lit) return GEOSRAD_OK;
-        LitFields F;
-        for (int k = 0; k < nres; k++) F.push_back({k, res[k], rows(k)});
-        return lit_scatter(st, *lit, ncol, out, F);
+        return lit_scatter(st, lit_scatter_pack<R>(swc_tile, nres, lm, *lit, ncol, out, res));
     }
 
     int lw_update_flx_dev(hipStream_t st, int ncol, int lm, int rrtmg, int lev_mid_high, int lev_low_mid, double undef,
@@ -3310,30 +3232,34 @@ int geosrad_rrtmg_lw_rats_dev(geosrad_ctx *c, void *stream, int ncol, int nlay, 
                      band_output, nullptr, nullptr, nrats > 0 ? &RT : nullptr);
 }
 
+// The drivers with a call record (gridcomp_kernels.hpp): an entry point fills it, its family's one statement passes it on (a tile's through swd_merge).
+static int lwd_call(geosrad_ctx *c, void *st, const LwdCall &C) { return !c || !C.in || !C.consts || !C.out ? GEOSRAD_EINVAL : c->lw_driver_dev((hipStream_t)st, C); }
+#define LWD_COMMON ncol, lm, nb_aer, in, consts, iceflglw, liqflglw, doy, lcldlm, lcldmh, band_output, out
 int geosrad_lw_driver_rrtmg_dev(geosrad_ctx *c, void *stream, int ncol, int lm, int nb_aer, const void *const *in, const double *consts,
                                 int iceflglw, int liqflglw, int doy, int lcldlm, int lcldmh, const int32_t *band_output, void *const *out)
 {
-    if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
-    return c->lw_driver_dev((hipStream_t)stream, ncol, lm, nb_aer, in, consts, iceflglw, liqflglw, doy, lcldlm, lcldmh, band_output, out, 0,
-                            nullptr, nullptr);
+    return lwd_call(c, stream, {LWD_COMMON, 0, nullptr, nullptr});
 }
 
 int geosrad_lw_driver_rrtmg_rats_dev(geosrad_ctx *c, void *stream, int ncol, int lm, int nb_aer, const void *const *in, const double *consts,
                                      int iceflglw, int liqflglw, int doy, int lcldlm, int lcldmh, const int32_t *band_output,
                                      void *const *out, int nrats, const int32_t *rat_gas, void *const *rat_out)
 {
-    if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
-    return c->lw_driver_dev((hipStream_t)stream, ncol, lm, nb_aer, in, consts, iceflglw, liqflglw, doy, lcldlm, lcldmh, band_output, out,
-                            nrats, rat_gas, rat_out);
+    return lwd_call(c, stream, {LWD_COMMON, nrats, rat_gas, rat_out});
 }
-
+#undef LWD_COMMON
+static int swd_call(geosrad_ctx *c, void *stream, SwdCall C)
+{
+    if (!c || !C.in || !C.consts || !C.out) return GEOSRAD_EINVAL;
+    if (C.lit) swd_merge(C);
+    return c->sw_driver_dev((hipStream_t)stream, C);
+}
+#define SWD_COMMON lm, nb_aer, in, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr, include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out
 int geosrad_sw_driver_rrtmg_dev(geosrad_ctx *c, void *stream, int ncol, int lm, int nb_aer, const void *const *in, const double *consts,
                                 int iceflgsw, int liqflgsw, double sc, double dist, int isolvar, int dyofyr, int include_aerosols,
                                 int lcldlm, int lcldmh, int normflx, const void *bndsolvar, const void *indsolvar, void *const *out)
 {
-    if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
-    return c->sw_driver_dev((hipStream_t)stream, ncol, lm, nb_aer, in, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr,
-                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, nullptr, nullptr);
+    return swd_call(c, stream, {ncol, SWD_COMMON});
 }
 
 int geosrad_sw_driver_rrtmg_lit_dev(geosrad_ctx *c, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos, int lm,
@@ -3341,10 +3267,8 @@ int geosrad_sw_driver_rrtmg_lit_dev(geosrad_ctx *c, void *stream, int ncol, int 
                                     int isolvar, int dyofyr, int include_aerosols, int lcldlm, int lcldmh, int normflx, const void *bndsolvar,
                                     const void *indsolvar, const double *dark, uint64_t keep_mask, void *const *out)
 {
-    if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
     const LitTile lit{ncol, lit_index, lit_pos, dark, keep_mask};
-    return c->sw_driver_dev((hipStream_t)stream, nlit, lm, nb_aer, in, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr,
-                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, &lit, nullptr);
+    return swd_call(c, stream, {nlit, SWD_COMMON, &lit});
 }
 
 int geosrad_sw_driver_rrtmg_obio_dev(geosrad_ctx *c, void *stream, int ncol, int lm, int nb_aer, const void *const *in, const double *consts,
@@ -3352,10 +3276,7 @@ int geosrad_sw_driver_rrtmg_obio_dev(geosrad_ctx *c, void *stream, int ncol, int
                                      int lcldlm, int lcldmh, int normflx, const void *bndsolvar, const void *indsolvar, void *const *out,
                                      void *drband, void *dfband)
 {
-    if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
-    const SwdObio obio{drband, dfband, nullptr, 0};
-    return c->sw_driver_dev((hipStream_t)stream, ncol, lm, nb_aer, in, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr,
-                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, nullptr, &obio);
+    return swd_call(c, stream, {ncol, SWD_COMMON, nullptr, drband, dfband});
 }
 
 int geosrad_sw_driver_rrtmg_obio_lit_dev(geosrad_ctx *c, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos,
@@ -3364,27 +3285,24 @@ int geosrad_sw_driver_rrtmg_obio_lit_dev(geosrad_ctx *c, void *stream, int ncol,
                                          int normflx, const void *bndsolvar, const void *indsolvar, const double *dark, uint64_t keep_mask,
                                          void *const *out, const double *dark_obio, int keep_obio, void *drband, void *dfband)
 {
-    if (!c || !in || !consts || !out) return GEOSRAD_EINVAL;
     const LitTile lit{ncol, lit_index, lit_pos, dark, keep_mask};
-    const SwdObio obio{drband, dfband, dark_obio, keep_obio};
-    return c->sw_driver_dev((hipStream_t)stream, nlit, lm, nb_aer, in, consts, iceflgsw, liqflgsw, sc, dist, isolvar, dyofyr,
-                            include_aerosols, lcldlm, lcldmh, normflx, bndsolvar, indsolvar, out, &lit, &obio);
+    return swd_call(c, stream, {nlit, SWD_COMMON, &lit, drband, dfband, dark_obio, keep_obio});
 }
+#undef SWD_COMMON
+static int swc_call(geosrad_ctx *c, void *st, const SwcCall &C) { return !c || !C.in || !C.out ? GEOSRAD_EINVAL : c->sw_driver_chou_dev((hipStream_t)st, C); }
 
 int geosrad_sw_driver_chou_dev(geosrad_ctx *c, void *stream, int ncol, int lm, const void *const *in, const double *consts, int lcldmh,
                                int lcldlm, const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out)
 {
-    if (!c || !in || !out) return GEOSRAD_EINVAL;
-    return c->sw_driver_chou_dev((hipStream_t)stream, ncol, lm, in, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, out, nullptr);
+    return swc_call(c, stream, {ncol, lm, in, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, out, nullptr});
 }
 
 int geosrad_sw_driver_chou_lit_dev(geosrad_ctx *c, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos, int lm,
                                    const void *const *in, const double *consts, int lcldmh, int lcldlm, const void *hk_uv, const void *hk_ir,
                                    int do_drfband, const double *dark, uint64_t keep_mask, void *const *out)
 {
-    if (!c || !in || !out) return GEOSRAD_EINVAL;
     const LitTile lit{ncol, lit_index, lit_pos, dark, keep_mask};
-    return c->sw_driver_chou_dev((hipStream_t)stream, nlit, lm, in, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, out, &lit);
+    return swc_call(c, stream, {nlit, lm, in, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, out, &lit});
 }
 
 int geosrad_lw_driver_chou_dev(geosrad_ctx *c, void *stream, int ncol, int lm, const void *const *in, const double *consts, int trace,

@@ -52,6 +52,22 @@ template <typename F, typename S> void bind_in(S &s, const void *const *in) { in
 template <typename F, typename S> void bind_out(S &s, void *const *out) { int k = 0; for (const auto &f : F::out) f.set(s, out[k++]); }
 template <typename S> void bind(S &s, const void *const *in, void *const *out) { bind_in<Fields<S>>(s, in); bind_out<Fields<S>>(s, out); }
 
+// the un-packed tile of the lit-aware SW drivers (geosrad_sw_driver_*_lit_dev): its columns, geosrad_lit_index_dev's two index arrays
+// (device), UnPackIt's DEFAULT of every output (host) and the outputs whose dark columns keep their values
+struct LitTile { int tile; const int32_t *idx, *pos; const double *dark; uint64_t keep; };
+inline const char *lit_check(const LitTile &t, int nlit, void *const *out, int nout)      // what is wrong with the tile's description, or null
+{
+    if (nlit < 0 || nlit > t.tile) return "nlit must lie in 0 .. ncol";
+    if (nlit > 0 && (!t.idx || !t.pos)) return "lit_index / lit_pos null";
+    bool fill = false;
+    for (int k = 0; k < nout; k++) fill = fill || (out[k] && !(t.keep >> k & 1));
+    return fill && (!t.pos || !t.dark) ? "an output whose keep bit is clear needs lit_pos and dark" : nullptr;
+}
+// One output of an SW driver on a tile, in its out[] enum's order: its rows (0: lm + 1) and where its packed result is: slot `at` of the post kernel
+// of the aerosol (POST) or no-aerosol pass (POST_NA), which un-packs it itself, or plane `at` of the driver's workspace, which k_lit_scatter un-packs.
+enum TileSrc { POST, POST_NA, PLANE };
+struct TileOut { int rows; TileSrc src; int at; int nrows(int lm) const { return rows ? rows : lm + 1; } };
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // LW_Driver, RRTMG branch
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -72,6 +88,11 @@ template <typename R> struct LwdArgs {
 template <typename R> struct Fields<LwdArgs<R>> { using S = LwdArgs<R>;
     GR_TABLE(in, GEOSRAD_LWD_NIN, &S::ple, &S::pl, &S::t, &S::q, &S::o3, &S::ch4, &S::n2o, &S::co2_3d, &S::cfc11, &S::cfc12, &S::hcfc22, &S::fcld, &S::cwc_liq,
              &S::cwc_ice, &S::reff_liq, &S::reff_ice, &S::taua, &S::ssaa, &S::ts, &S::emis, &S::lats, &S::t2m);
+};
+// geosrad_lw_driver_rrtmg*_dev, as geosrad.h has it (nrats == 0 without the RATS diagnostics)
+struct LwdCall {
+    int ncol, lm, nb; const void *const *in; const double *consts; int iceflg, liqflg, doy, lcldlm, lcldmh; const int32_t *band_output; void *const *out;
+    int nrats; const int32_t *rat_gas; void *const *rat_out;
 };
 // interface temperature of model level k (1..LM+1), IRR:3248-3256
 template <typename R> GR_DEV R lwd_tlev(const LwdArgs<R> &A, int k, int ij)
@@ -386,6 +407,14 @@ template <typename R> struct Fields<SwcLit<R>> { using S = SwcLit<R>;
              elem<&S::q, 2>, elem<&S::q, 3>, elem<&S::r, 0>, elem<&S::r, 1>, elem<&S::r, 2>, elem<&S::r, 3>, elem<&S::aer_in, 0>, elem<&S::aer_in, 1>,
              elem<&S::aer_in, 2>, elem<&S::col_in, 0>, elem<&S::col_in, 1>, elem<&S::col_in, 2>, elem<&S::col_in, 3>, elem<&S::col_in, 4>);
 };
+// geosrad_sw_driver_chou*_dev, as geosrad.h has it; with `lit`, in / out are the un-packed tile's and ncol is NumLit
+struct SwcCall {
+    int ncol, lm; const void *const *in; const double *consts; int lcldmh, lcldlm; const void *hk_uv, *hk_ir; int do_drfband; void *const *out; const LitTile *lit;
+};
+// sorad's results on a tile: each in a plane of its own
+constexpr TileOut swc_tile[] = {{0, PLANE, 0}, {0, PLANE, 1}, {0, PLANE, 2}, {0, PLANE, 3}, {1, PLANE, 4}, {1, PLANE, 5}, {1, PLANE, 6}, {1, PLANE, 7},
+                                {1, PLANE, 8}, {1, PLANE, 9}, {8, PLANE, 10}, {8, PLANE, 11}, {8, PLANE, 12}};
+static_assert(std::size(swc_tile) == GEOSRAD_SWC_NOUT && GEOSRAD_SWC_FSCU == 3 && GEOSRAD_SWC_FSWBAND == 10, "one row for each GEOSRAD_SWC_* output");
 template <typename R, bool LIT> using SwcPrepOf = std::conditional_t<LIT, SwcLit<R>, SwcPrep<R>>;
 template <typename R, bool LIT = false> __global__ void __launch_bounds__(256) k_swc_prep(SwcPrepOf<R, LIT> P)
 {
@@ -672,6 +701,30 @@ template <typename R> struct Fields<SwdLit<R>> { using S = SwdLit<R>;
     GR_TABLE(in, GEOSRAD_SWD_NIN, &S::ple, &S::pl, &S::t, &S::q, &S::o3, &S::ch4, &S::cl, &S::ts, &S::qq_ice, &S::qq_liq, &S::rr_ice, &S::rr_liq, &S::taua,
              &S::ssaa, &S::asya, elem<&S::col_in, 0>, elem<&S::col_in, 1>, elem<&S::col_in, 2>, elem<&S::col_in, 3>, elem<&S::col_in, 4>, elem<&S::col_in, 5>);
 };
+// The driver's outputs on a tile: GEOSRAD_SWD_*, then DRBAND and DFBAND of the ocean-biology coupling.  The driver's workspace planes: 0 - 5 the
+// solver's surface scalars, then the band fluxes of the aerosol and the no-aerosol pass, DRBAND and DFBAND.
+enum { SWD_DRBAND = GEOSRAD_SWD_NOUT, SWD_DFBAND, SWD_NROW, SWD_P_BAND = 6, SWD_P_NBAND, SWD_P_DRBAND, SWD_P_DFBAND, SWD_NPLANE };
+constexpr TileOut swd_tile[] = {{0, POST, 0}, {0, POST, 1}, {0, POST, 2}, {0, POST, 3}, {1, PLANE, 0}, {1, PLANE, 1}, {1, PLANE, 2}, {1, PLANE, 3}, {1, PLANE, 4},
+                                {1, PLANE, 5}, {14, PLANE, SWD_P_BAND}, {1, POST, 4}, {1, POST, 5}, {1, POST, 6}, {1, POST, 7}, {1, POST, 8}, {1, POST, 9},
+                                {1, POST, 10}, {1, POST, 11}, {0, POST_NA, 0}, {0, POST_NA, 1}, {0, POST_NA, 2}, {0, POST_NA, 3}, {14, PLANE, SWD_P_NBAND},
+                                {14, PLANE, SWD_P_DRBAND}, {14, PLANE, SWD_P_DFBAND}};
+static_assert(std::size(swd_tile) == SWD_NROW && GEOSRAD_SWD_NIRR == 4 && GEOSRAD_SWD_FSWBAND == 10 && GEOSRAD_SWD_CLDTS == 11 && GEOSRAD_SWD_COTTP == 15 &&
+              GEOSRAD_SWD_FSWNA == 19 && GEOSRAD_SWD_FSWBANDNA == 23, "one row for each GEOSRAD_SWD_* output, then DRBAND and DFBAND");
+// geosrad_sw_driver_rrtmg*_dev, as geosrad.h has it; with `lit`, in / out are the un-packed tile's and ncol is NumLit; drband / dfband: the _obio
+// entry points'.  rows / dark / keep: a tile's SWD_NROW outputs; the driver reads them, so a tile's record goes through swd_merge first (swd_call).
+struct SwdCall {
+    int ncol, lm, nb; const void *const *in; const double *consts; int iceflg, liqflg; double sc, dist; int isolvar, dyofyr, include_aerosols, lcldlm, lcldmh;
+    int normflx; const void *bndsolvar, *indsolvar; void *const *out; const LitTile *lit; void *drband, *dfband; const double *dark_obio; int keep_obio;
+    void *rows[SWD_NROW]; double dark[SWD_NROW]; uint64_t keep;
+    bool drf() const { return drband && include_aerosols != 0; }      // do_drfband = SOLAR_TO_OBIO .and. include_aerosols (SOL:6385), else untouched
+};
+inline void swd_merge(SwdCall &C)
+{
+    for (int k = 0; k < GEOSRAD_SWD_NOUT; k++) { C.rows[k] = C.out[k]; C.dark[k] = C.lit->dark ? C.lit->dark[k] : 0.0; }
+    C.rows[SWD_DRBAND] = C.drf() ? C.drband : nullptr; C.rows[SWD_DFBAND] = C.drf() ? C.dfband : nullptr;
+    for (int k = 0; k < 2; k++) C.dark[SWD_DRBAND + k] = C.drf() && C.dark_obio ? C.dark_obio[k] : 0.0;
+    C.keep = (C.lit->keep & ((1ull << GEOSRAD_SWD_NOUT) - 1)) | (C.drf() ? (uint64_t)(C.keep_obio & 3) << GEOSRAD_SWD_NOUT : 0);
+}
 template <typename R, bool LIT> using SwdArgsOf = std::conditional_t<LIT, SwdLit<R>, SwdArgs<R>>;
 
 // ij, n: the column of the imports and their leading dimension
@@ -854,6 +907,34 @@ template <typename R> struct LitScatter {
     struct { const R *src; R *dst; int row0, keep; R dark; } f[LIT_NFIELD];
     int rows;                                             // row0 of the field after the last
 };
+// Host: k_lit_scatter's argument over the first n rows of a driver's tile table, for the outputs the caller requested.  With daytime columns
+// the PLANE rows, from plane[at]; with none (nlit == 0) the dark fill of every row whose keep bit is clear.
+template <typename R, size_t N>
+LitScatter<R> lit_scatter_pack(const TileOut (&rows)[N], int n, int lm, const LitTile &t, int nlit, void *const *out, const R *const *plane)
+{
+    static_assert(N <= LIT_NFIELD, "a field of LitScatter for every row");
+    LitScatter<R> S{};
+    S.tile = t.tile; S.nlit = nlit; S.pos = t.pos;
+    for (int k = 0; k < n; k++) {
+        const int keep = (int)(t.keep >> k & 1);
+        if (!out[k] || (nlit == 0 ? keep != 0 : rows[k].src != PLANE)) continue;
+        S.f[S.nf].src = nlit ? plane[rows[k].at] : nullptr; S.f[S.nf].dst = (R *)out[k]; S.f[S.nf].row0 = S.rows; S.f[S.nf].keep = keep;
+        S.f[S.nf].dark = t.dark ? (R)t.dark[k] : (R)0;
+        S.nf++; S.rows += rows[k].nrows(lm);
+    }
+    return S;
+}
+// Host: k_swd_post_lit's tile, dark values and keep bits for one pass, from the rows of swd_tile that pass un-packs
+template <typename R> void post_lit_pack(SwdPostLit<R> &P, TileSrc pass, const LitTile &t)
+{
+    P.tile = t.tile; P.pos = t.pos; P.keep = 0;
+    for (R &d : P.dark) d = (R)0;
+    for (int k = 0; k < GEOSRAD_SWD_NOUT; k++) {
+        if (swd_tile[k].src != pass) continue;
+        if (t.keep >> k & 1) P.keep |= 1u << swd_tile[k].at;
+        P.dark[swd_tile[k].at] = t.dark ? (R)t.dark[k] : (R)0;
+    }
+}
 template <typename R> __global__ void __launch_bounds__(256) k_lit_scatter(LitScatter<R> S)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x, row = blockIdx.y;
