@@ -937,7 +937,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         w.pwvcm = c.take<R>(nc);
         w.colcloudy = c.take<uint8_t>(nc);
         w.perm = c.take<int32_t>(nc);
-        w.nclear = c.take<int32_t>(1);
+        w.nclear = c.take<int32_t>(1 + part_blocks(nc));      // + the tile counts of the partition (launch_partition)
         w.laycloudy = c.take<uint8_t>(cl);
         w.alpha = c.take<R>(cl);
         w.rcorr = c.take<R>(cl);
@@ -1024,8 +1024,9 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 
-    // The front end of both RRTMG solvers for one chunk, MODE 0: RRTMG_LW (A: LwArgs), 2: RRTMG_SW (A: SwArgs) - input assertions and the
-    // clear | cloudy partition in one profile slot, setcoef, the overlap correlations, the McICA sub-columns with their cloud optics
+    // The front end of both RRTMG solvers for one chunk, MODE 0: RRTMG_LW (A: LwArgs), 2: RRTMG_SW (A: SwArgs) - the column pass and the
+    // clear | cloudy partition in one profile slot, setcoef with the per-layer input assertions (the aerosol ones are made by the band
+    // sweeps), the overlap correlations, the McICA sub-columns with their cloud optics
     // (threads of clear columns exit at once).  radval: the RADVAL instantiation of the generator, which also fills rvsum.
     template <int MODE, typename Args> int rrtmg_front(hipStream_t st, const Args &A, bool radval = false, R *rvsum = nullptr)
     {
@@ -1037,13 +1038,12 @@ template <typename R> struct Ctx : geosrad_ctx {
         span_begin(SW ? 6 : 0, st);
         if constexpr (SW) {
             hipLaunchKernelGGL(k_sw_validate<R>, dim3(gx), blk, 0, st, A);
-            if (A.iaer == 10) hipLaunchKernelGGL(k_sw_validate_aer<R>, dim3(gx, A.nlay), blk, 0, st, A);
         } else hipLaunchKernelGGL(k_validate_pwv<R>, dim3(gx), blk, 0, st, A, d_T);
-        hipLaunchKernelGGL(k_partition, dim3(1), dim3(1024), 0, st, A.ncol, (const uint8_t *)A.colcloudy, A.perm, A.nclear);
+        launch_partition(st, A.ncol, A.colcloudy, A.perm, A.nclear);
         span_end(st);
         span_begin(SW ? 7 : 1, st);
         if constexpr (SW) hipLaunchKernelGGL(k_sw_setcoef<R>, dim3(gx, A.nlay), blk, 0, st, A, dS);
-        else hipLaunchKernelGGL(k_setcoef<R>, dim3(gx, A.nlay), blk, 0, st, A, d_T);
+        else hipLaunchKernelGGL((k_setcoef<R, true>), dim3(gx, A.nlay), blk, 0, st, A, d_T);
         span_end(st);
         span_begin(2, st);
         hipLaunchKernelGGL(k_overlap<R>, dim3(gx, A.nlay), blk, 0, st, A.ncol, A.ld, A.nlay, A.doy, A.zm, A.alat, (const int32_t *)A.perm,
@@ -1193,7 +1193,7 @@ template <typename R> struct Ctx : geosrad_ctx {
                 if (rats->gas[r] == GEOSRAD_RAT_H2O) B.pwvcm = zero;      // pwvcm is only read from here on
                 B.dbg_taug = nullptr; B.dbg_pfracs = nullptr;
                 B.band_mask = LW_RAT_BANDS[rats->gas[r]];
-                span_begin(1, st); hipLaunchKernelGGL(k_setcoef<R>, dim3(grid256(nc), nlay), dim3(256), 0, st, B, d_T); span_end(st);
+                span_begin(1, st); hipLaunchKernelGGL((k_setcoef<R, false>), dim3(grid256(nc), nlay), dim3(256), 0, st, B, d_T); span_end(st);
                 LwOut<R> OR{};
                 const size_t ro = (size_t)r * (nlay + 1) * ncol + c0;
                 OR.uflx = (R *)rats->uflx + ro; OR.dflx = (R *)rats->dflx + ro;
@@ -1782,7 +1782,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             const size_t cl = (size_t)lm * nc_max;
             H.alpha = c.take<R>(cl); H.rcorr = c.take<R>(cl);
             H.cf0 = c.take<uint16_t>(nc_max); H.cf1 = c.take<uint16_t>(nc_max); H.cloudy = c.take<uint8_t>(nc_max);
-            perm = c.take<int32_t>(compact ? nc_max : 0); nclear = c.take<int32_t>(compact ? 1 : 0);
+            perm = c.take<int32_t>(compact ? nc_max : 0); nclear = c.take<int32_t>(compact ? 1 + part_blocks(nc_max) : 0);
             H.cnt = c.take<int32_t>((size_t)4 * nc_max);
             return c.off;
         };
@@ -1800,7 +1800,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             H.qi = colp(in[GEOSRAD_SWHB_QI], c0); H.ql = colp(in[GEOSRAD_SWHB_QL], c0); H.lats = colp(in[GEOSRAD_SWHB_LATS], c0);
             for (int k = 0; k < GEOSRAD_SWHB_NOUT; k++) H.out[k] = colp(out[k], c0);
             hipLaunchKernelGGL((k_swhb_prep<R>), dim3(grid256(nc)), dim3(256), 0, st, H, dT);
-            if (compact) hipLaunchKernelGGL(k_partition, dim3(1), dim3(1024), 0, st, nc, (const uint8_t *)H.cloudy, perm, nclear);
+            if (compact) launch_partition(st, nc, H.cloudy, perm, nclear);
             hipLaunchKernelGGL((k_swhb_count<R>), dim3(xcd_grid(nc, 64, nseg)), dim3(64), 0, st, H, MP, dT);
             hipLaunchKernelGGL((k_swhb_export<R>), dim3(grid256(nc)), dim3(256), 0, st, H);
             return GEOSRAD_OK;
@@ -2038,7 +2038,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         w.scidx = c.take<uint32_t>(cl);
         w.colcloudy = c.take<uint8_t>(nc);
         w.perm = c.take<int32_t>(nc);
-        w.nclear = c.take<int32_t>(1);
+        w.nclear = c.take<int32_t>(1 + part_blocks(nc));      // + the tile counts of the partition (launch_partition)
         w.laycloudy = c.take<uint8_t>(cl);
         w.alpha = c.take<R>(cl);
         w.rcorr = c.take<R>(cl);

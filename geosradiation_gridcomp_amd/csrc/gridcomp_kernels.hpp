@@ -1319,7 +1319,7 @@ template <typename R, int V> __global__ void __launch_bounds__(256) k_rad_tenden
 // ---------------------------------------------------------------------------------------------------
 // Lit-column compaction of the solar component (GEOS_SolarGridComp.F90:3686 `daytime = ZTH > 0.`, PackIt / UnPackIt :7753-7799):
 // SORADCORE only sees the NumLit daytime columns, packed to the front of every field in (i, j) order.
-//   k_lit_index: stable list of the lit columns (one 1024-thread block, like k_partition): idx[m] = column of packed position m,
+//   k_lit_index: stable list of the lit columns (one 1024-thread block, like k_partition8 of sorad): idx[m] = column of packed position m,
 //                pos[column] = packed position or -1, *nlit = NumLit
 //   k_lit_pack  : Packed(m, l) = UnPacked(idx[m], l)
 //   k_lit_unpack: UnPacked(idx[m], l) = Packed(m, l); dark columns get DEFAULT when one is given (PRESENT(DEFAULT)), else keep their value

@@ -243,6 +243,7 @@ GR_DEV void lwc_band(const LwArgs<R> &A, const LwOut<R> &O, const LwDev<R> &T, R
             secdiff = secdiff > (R)1.80 ? (R)1.80 : (secdiff < (R)1.50 ? (R)1.50 : secdiff);
         }
         ta = A.tauaer ? ldg(A.tauaer + (size_t)(IB - 1) * nlay * ld, S.L.ab) : (R)0;
+        if (ta < 0) atomicOr(A.err, 1u << 20);      // the input assertion on tauaer (as in band_body, lw_kernels.hpp)
         blay = planck_at<R>(T.totplnk, IB, ldg(A.tlay, S.L.ab));
         const R plk_dn = planck_at<R>(T.totplnk, IB, ldg(A.tlev, S.L.ab));
         const R plk_up = planck_at<R>(T.totplnk, IB, ldg(A.tlev + ld, S.L.ab));

@@ -5,8 +5,9 @@
 //   lane = column, all HBM traffic coalesced over the column dimension, no cross-lane traffic, LDS only as a
 //   read-only copy of the transmittance table, no MFMA (the path is table interpolation + first-order vertical
 //   recurrences).  (The other mapping - lanes = layers, intermediates in LDS - is k_lw_cols, lw_cols_kernels.hpp.)
-//   k_validate_pwv : per column  - input checks, precipitable water, "any cloud" flag
-//   k_setcoef      : per (layer,column) - p/T interpolation record shared by all 16 bands
+//   k_validate_pwv : per column  - per-column input checks, precipitable water, cloud-top byte
+//   k_partition    : stable clear | cloudy partition of the columns, one block per 1024 columns
+//   k_setcoef      : per (layer,column) - p/T interpolation record shared by all 16 bands; the per-layer input checks
 //   k_lw_bands     : per (256-column block, band) (band_block: XCD-aware grid): fused taumol -> rtrnmc; down sweep
 //                    keeps the band's g-point radiances in registers and evaluates the k-distribution 4 or 8
 //                    g-points at a time, parking the 2-byte table index of every cell in HBM; the up sweep
@@ -96,6 +97,14 @@ template <typename T> GR_DEV void stg_nt(T *base, uint32_t byteoff, T v)
 {
     __builtin_nontemporal_store(v, reinterpret_cast<T *>(reinterpret_cast<char *>(base) + byteoff));
 }
+// an input assertion made where the value is loaded for use anyway (setcoef's arrays in k_setcoef / k_sw_setcoef, the aerosol planes in
+// the band kernels): one test per wave, the atomicOr on the rare path, so a kernel that walks layers keeps no error mask across them
+GR_DEV void err_wave(bool bad, uint32_t *err, int bit)
+{
+    if (__ballot(bad) != 0) {
+        if (bad) atomicOr(err, 1u << bit);
+    }
+}
 typedef float gr_v2f __attribute__((ext_vector_type(2)));
 typedef double gr_v2d __attribute__((ext_vector_type(2)));
 template <> GR_DEV float2 ldg_nt<float2>(const float2 *base, uint32_t byteoff)
@@ -120,8 +129,9 @@ template <> GR_DEV void stg_nt<double2>(double2 *base, uint32_t byteoff, double2
 }
 
 // ---------------------------------------------------------------------------------------------------
-// k_validate_pwv: one thread per column.
-//   - the reference's input assertions (LW/rrtmg_lw_rad.F90:209-318) -> error bits
+// k_validate_pwv: one thread per column - only what needs a whole column or is per column; it reads plev, h2o, cldf, play per layer.
+//   - of the reference's input assertions (LW/rrtmg_lw_rad.F90:209-318) those on tsfc, emis and level 0 of plev / tlev -> error bits
+//     (the per-layer ones are made by k_setcoef<R, true>, which loads most of those arrays anyway, tauaer's by the band kernels)
 //   - pwvcm (LW/rrtmg_lw_setcoef.F90:206-272), same summation order (bottom-up)
 //   - colcloudy = 1 + the highest layer with cldf > 0 (0: none; nlay <= mxlay = 203 fits a byte): lets later kernels skip McICA
 //     work for clear columns, and the generator stop above a wave's highest cloud, without changing results (all
@@ -136,22 +146,14 @@ __global__ void __launch_bounds__(256) k_validate_pwv(LwArgs<R> A, const LwDev<R
     const R amd = (R)28.9660, amw = (R)18.0160;
     const R grav = T->grav, avogad = T->avogad;
     uint32_t err = 0;
-    const R *chk[17] = {A.play, A.tlay, A.h2o, A.o3, A.co2, A.ch4, A.n2o, A.o2, A.cfc11, A.cfc12, A.cfc22, A.ccl4,
-                        A.cldf, A.ciwp, A.clwp, A.rei, A.rel};
     R amttl = 0, wvttl = 0;
     int cftop = 0;
     R pprev = A.plev[col];
     if (pprev < 0 || A.tlev[col] < 0) err |= 1u << 17;
+    bool upper = false, bad = false;
     for (int lay = 0; lay < nlay; lay++) {
         const size_t i = (size_t)lay * ld + col;
-#pragma unroll
-        for (int k = 0; k < 17; k++)
-            if (chk[k][i] < 0) err |= 1u << k;
         const R pup = A.plev[i + ld];
-        if (pup < 0 || A.tlev[i + ld] < 0) err |= 1u << 17;
-        if (A.tauaer)
-            for (int ib = 0; ib < NB_LW; ib++)
-                if (A.tauaer[((size_t)ib * nlay + lay) * ld + col] < 0) err |= 1u << 20;
         const R h2o = A.h2o[i];
         const R amm = ((R)1. - h2o) * amd + h2o * amw;
         const R coldry = (pprev - pup) * (R)1.e3 * avogad / ((R)1.e2 * grav * amm * ((R)1. + h2o));
@@ -159,9 +161,14 @@ __global__ void __launch_bounds__(256) k_validate_pwv(LwArgs<R> A, const LwDev<R
         amttl = amttl + coldry + btemp;
         wvttl = wvttl + btemp;
         if (A.cldf[i] > 0) cftop = lay + 1;
-        // pressure ordering (LW/rrtmg_lw_setcoef.F90:443-453): lower-atmosphere layer above an upper one
+        // pressure ordering (LW/rrtmg_lw_setcoef.F90:443-453): lower-atmosphere layer above an upper one, that is plog > 4.56
+        // somewhere above a layer with plog <= 4.56
+        const bool lower = gr_log<R>(A.play[i]) > (R)4.56;
+        if (lower && upper) bad = true;
+        if (!lower) upper = true;
         pprev = pup;
     }
+    if (bad) err |= 1u << ERR_PRESSURE_ORDER;
     if (A.tsfc[col] < 0) err |= 1u << 18;
     for (int ib = 0; ib < NB_LW; ib++)
         if (A.emis[(size_t)ib * ld + col] < 0) err |= 1u << 19;
@@ -172,21 +179,15 @@ __global__ void __launch_bounds__(256) k_validate_pwv(LwArgs<R> A, const LwDev<R
     // clear column: all sub-columns clear in every super-layer (cloud_subcol_gen.F90:649-659);
     // cloudy column: k_mcica's (column, band) threads add their counts
     for (int k = 0; k < 4; k++) A.clearCounts[(size_t)k * ld + col] = cloudy ? 0 : NG_LW;
-    // pressure misordering: plog > 4.56 somewhere above a layer with plog <= 4.56
-    {
-        bool upper = false, bad = false;
-        for (int lay = 0; lay < nlay; lay++) {
-            const bool lower = gr_log<R>(A.play[(size_t)lay * ld + col]) > (R)4.56;
-            if (lower && upper) bad = true;
-            if (!lower) upper = true;
-        }
-        if (bad) err |= 1u << ERR_PRESSURE_ORDER;
-    }
     if (err) atomicOr(A.err, err);
 }
 
 // ---------------------------------------------------------------------------------------------------
-// k_partition: stable partition of the batch's columns into clear | cloudy (one 1024-thread block).
+// k_partition: stable partition of the batch's columns into clear | cloudy, one 256-thread block per tile of PART_TILE columns:
+// k_partition_count leaves every tile's number of cloudy columns behind *nclear (tilecnt = nclear + 1, part_blocks(ncol) counts);
+// each block of k_partition then sums the counts of the tiles before its own and of all tiles, and scatters its tile's columns in
+// order: a column's rank among the cloudy ones is that sum + the ballot prefix inside the tile.  A batch of one tile needs no counts
+// (launch_partition).
 // Every later kernel works on COMPACTED positions: workspace arrays are indexed by the position, API arrays
 // by perm[position].  256-column blocks are then homogeneous (at most one mixed block), so clear blocks run the
 // cheaper clear-sky instantiation whatever the spatial distribution of the cloudy columns, and no wave
@@ -196,38 +197,82 @@ __global__ void __launch_bounds__(256) k_validate_pwv(LwArgs<R> A, const LwDev<R
 // and inside 256-column blocks: k_mcica gains 0.45 ms batch-wide, but every array read in the caller's column order then costs
 // more cache lines per wave and k_sw_reform loses 0.2-0.25 ms; the step does not move - profiles/r03_mcica_cloudtop.md.)
 // ---------------------------------------------------------------------------------------------------
-static __global__ void __launch_bounds__(1024) k_partition(int ncol, const uint8_t *__restrict__ colcloudy, int32_t *__restrict__ perm,
-                                                    int32_t *__restrict__ nclear)
+constexpr int PART_TILE = 1024;                     // 4 columns per thread, 256 apart
+inline int part_blocks(int ncol) { return (ncol + PART_TILE - 1) / PART_TILE; }
+
+static __global__ void __launch_bounds__(256) k_partition_count(int ncol, const uint8_t *__restrict__ colcloudy, int32_t *__restrict__ tilecnt)
 {
-    __shared__ int cnt[1024];
-    const int t = threadIdx.x;
-    const int chunk = (ncol + 1023) / 1024;
-    const int b = t * chunk, e = (b + chunk < ncol) ? b + chunk : ncol;
+    const int i0 = blockIdx.x * PART_TILE + threadIdx.x;
     int c = 0;
-    for (int i = b; i < e; i++) c += colcloudy[i] != 0;
-    cnt[t] = c;
+    for (int k = 0; k < PART_TILE / 256; k++) {
+        const int i = i0 + k * 256;
+        c += __syncthreads_count(i < ncol && colcloudy[i] != 0);
+    }
+    if (threadIdx.x == 0) tilecnt[blockIdx.x] = c;
+}
+
+static __global__ void __launch_bounds__(256) k_partition(int ncol, const uint8_t *__restrict__ colcloudy, int32_t *__restrict__ perm,
+                                                   int32_t *__restrict__ nclear, const int32_t *__restrict__ tilecnt)
+{
+    constexpr int NK = PART_TILE / 256, NW = 256 / 64;
+    __shared__ int wcnt[NK * NW];                   // cloudy columns of (pass k, wave w): the tile's columns in order
+    __shared__ int sums[2];                         // cloudy columns before this tile | of the batch
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int i0 = blockIdx.x * PART_TILE + t;
+    if (t < 2) sums[t] = 0;
+    bool f[NK];
+    int pre[NK];                                    // cloudy columns of the wave before this lane's
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const int i = i0 + k * 256;
+        f[k] = i < ncol && colcloudy[i] != 0;
+        const unsigned long long m = __ballot(f[k]);
+        pre[k] = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wcnt[k * NW + w] = __popcll(m);
+    }
     __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {          // inclusive Hillis-Steele scan
-        const int v = t >= d ? cnt[t - d] : 0;
+    int before = 0, total = 0;
+    if (gridDim.x > 1) {
+        for (int b = t; b < (int)gridDim.x; b += 256) {
+            const int v = tilecnt[b];
+            total += v;
+            if (b < (int)blockIdx.x) before += v;
+        }
+        if (before) atomicAdd(&sums[0], before);    // integer sums: the order does not matter
+        if (total) atomicAdd(&sums[1], total);
         __syncthreads();
-        cnt[t] += v;
-        __syncthreads();
+        before = sums[0]; total = sums[1];
+    } else {
+        for (int j = 0; j < NK * NW; j++) total += wcnt[j];
     }
-    const int ncloudy = cnt[1023];
-    const int ncl = ncol - ncloudy;
-    int cbefore = cnt[t] - c;                       // cloudy columns before this thread's chunk
-    for (int i = b; i < e; i++) {
-        if (colcloudy[i]) { perm[ncl + cbefore] = i; cbefore++; }
-        else perm[i - cbefore] = i;
+    const int ncl = ncol - total;
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const int i = i0 + k * 256;
+        if (i >= ncol) continue;
+        int cb = before + pre[k];                   // cloudy columns before column i
+        for (int j = 0; j < k * NW + w; j++) cb += wcnt[j];
+        if (f[k]) perm[ncl + cb] = i;
+        else perm[i - cb] = i;
     }
-    if (t == 0) *nclear = ncl;
+    if (blockIdx.x == 0 && t == 0) *nclear = ncl;
+}
+
+// nclear: 1 + part_blocks(ncol) integers, the tile counts behind the number of clear columns
+static inline void launch_partition(hipStream_t st, int ncol, const uint8_t *colcloudy, int32_t *perm, int32_t *nclear)
+{
+    const int nb = part_blocks(ncol);
+    if (nb > 1) hipLaunchKernelGGL(k_partition_count, dim3(nb), dim3(256), 0, st, ncol, colcloudy, nclear + 1);
+    hipLaunchKernelGGL(k_partition, dim3(nb), dim3(256), 0, st, ncol, colcloudy, perm, nclear, (const int32_t *)(nclear + 1));
 }
 
 // ---------------------------------------------------------------------------------------------------
 // k_setcoef: one thread per (layer, column); blockIdx.y = layer.  LW/rrtmg_lw_setcoef.F90:401-579
 // (everything that does not depend on the band; Planck terms are interpolated inside the band kernel).
+// CHECK: the reference's input assertions on every per-layer array but tauaer (LW/rrtmg_lw_rad.F90:209-318; error bit k: LW_NEG_NAMES[k])
+// and on plev / tlev above level 0 - the call's first launch; the RATS passes run the same inputs again and do not test.
 // ---------------------------------------------------------------------------------------------------
-template <typename R>
+template <typename R, bool CHECK>
 __global__ void __launch_bounds__(256) k_setcoef(LwArgs<R> A, const LwDev<R> *__restrict__ T)
 {
     const int col = blockIdx.x * blockDim.x + threadIdx.x;
@@ -238,9 +283,20 @@ __global__ void __launch_bounds__(256) k_setcoef(LwArgs<R> A, const LwDev<R> *__
     const R amd = (R)28.9660, amw = (R)18.0160;
     const R stpfac = (R)296. / (R)1013.;
     const R pavel = A.play[i], tavel = A.tlay[i], h2o = A.h2o[i];
+    const R pdn = A.plev[i], pup = A.plev[i + ld], o3 = A.o3[i], co2 = A.co2[i], ch4 = A.ch4[i], n2o = A.n2o[i], o2 = A.o2[i];
+    if constexpr (CHECK) {
+        const R v[17] = {pavel, tavel, h2o, o3, co2, ch4, n2o, o2, A.cfc11[i], A.cfc12[i], A.cfc22[i], A.ccl4[i],
+                         A.cldf[i], A.ciwp[i], A.clwp[i], A.rei[i], A.rel[i]};
+        uint32_t err = 0;
+#pragma unroll
+        for (int k = 0; k < 17; k++)
+            if (v[k] < 0) err |= 1u << k;
+        if (pup < 0 || A.tlev[i + ld] < 0) err |= 1u << 17;
+        if (err) atomicOr(A.err, err);
+    }
     const R amm = ((R)1. - h2o) * amd + h2o * amw;
-    const R coldry = (A.plev[i] - A.plev[i + ld]) * (R)1.e3 * T->avogad / ((R)1.e2 * T->grav * amm * ((R)1. + h2o));
-    const R summol = A.co2[i] + A.o3[i] + A.n2o[i] + A.ch4[i] + A.o2[i];
+    const R coldry = (pdn - pup) * (R)1.e3 * T->avogad / ((R)1.e2 * T->grav * amm * ((R)1. + h2o));
+    const R summol = co2 + o3 + n2o + ch4 + o2;
     const R wbroad = coldry * ((R)1. - summol);
     const R wv = h2o * coldry;
 
@@ -1399,6 +1455,7 @@ GR_DEV void band_body(const LwArgs<R> &A, const LwDev<R> &Tg, int col, int nclea
             __builtin_amdgcn_sched_barrier(0);   // keep one g-group's table rows in flight at a time
         }
         }
+        err_wave(ta < 0, A.err, 20);      // LW/rrtmg_lw_rad.F90:209-318 on tauaer: every band visits every layer of its columns
         PART(0, lay, dsum);
         if (CLD && ccol) PART(1, lay, dcsum);
     }

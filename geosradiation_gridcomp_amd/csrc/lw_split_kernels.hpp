@@ -82,6 +82,7 @@ GR_DEV void lws_cells_body(const LwArgs<R> &A, const LwDev<R> &T, int col, int n
         Layer<R> L;
         load_layer<R>(A, lay, col, pc, L);
         const R ta = A.tauaer ? ldg(A.tauaer + (size_t)(IB - 1) * nlay * ld, L.ab) : (R)0;
+        err_wave(ta < 0, A.err, 20);      // the input assertion on tauaer (as in band_body, lw_kernels.hpp)
         const bool laycld = CLD && ccol && A.laycloudy[(size_t)lay * n + ucol] != 0;
         Prep<R> P;
         BAND::template prep<R>(T, A, L, P);

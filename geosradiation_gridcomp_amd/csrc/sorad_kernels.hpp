@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(256) k_sorad_class(SoradArgs<R> A, int one_cla
     A.cls[i] = (uint8_t)c;
 }
 
-// stable counting sort of the columns by class (one 1024-thread block; cf. k_partition of the RRTMG solvers)
+// stable counting sort of the columns by class (one 1024-thread block; the RRTMG solvers' two-class k_partition is multi-block)
 static __global__ void __launch_bounds__(1024) k_partition8(int ncol, const uint8_t *__restrict__ cls, int32_t *__restrict__ perm,
                                                      int32_t *__restrict__ off)
 {

@@ -6,8 +6,8 @@
 //
 // Same mapping as the LW path (lane = column, one block per (256-column block, band) on the XCD-aware one-dimensional grid of
 // lw_kernels.hpp band_block, uniform base + 32-bit byte offset addressing):
-//   k_sw_validate : per column  - input asserts, cloudy flags, clearCounts of clear columns
-//   k_sw_setcoef  : per (layer,column) - column amounts + p/T interpolation record shared by all 14 bands
+//   k_sw_validate : per column  - albedo asserts, cloud-top byte, clearCounts of clear columns
+//   k_sw_setcoef  : per (layer,column) - column amounts + p/T interpolation record shared by all 14 bands; the per-layer input asserts
 //   k_mcica<.,2>  : per (column, band) - McICA sub-columns + cldprmc_sw (delta-scaled tau, ssa, g) [mcica_kernels.hpp]
 //   k_sw_bands    : per (column, band) - fused taumol_sw -> delta-scaling -> reftra_sw -> vrtqdr_sw:
 //                   sweep A (surface -> TOA) evaluates the layer R/T and the upward adding recurrences and parks 7 values
@@ -82,47 +82,29 @@ template <typename R> struct SwOut {
 enum SwErr { SWERR_PLEV = 12, SWERR_ALB = 13, SWERR_AER = 14 };
 
 // ---------------------------------------------------------------------------------------------------
+// only what needs a whole column or is per column: the cloud top and the albedo assertions (the per-layer assertions are made by
+// k_sw_setcoef, the aerosol ones by the band kernels)
 template <typename R>
 __global__ void __launch_bounds__(256) k_sw_validate(SwArgs<R> A)
 {
     const int col = blockIdx.x * blockDim.x + threadIdx.x;
     if (col >= A.ncol) return;
     const int ld = A.ld, nlay = A.nlay;
-    uint32_t err = 0;
-    const R *chk[12] = {A.play, A.tlay, A.h2o, A.o3, A.co2, A.ch4, A.o2, A.cld, A.ciwp, A.clwp, A.rei, A.rel};
     int cftop = 0;
-    for (int lay = 0; lay < nlay; lay++) {
-        const size_t i = (size_t)lay * ld + col;
-#pragma unroll
-        for (int k = 0; k < 12; k++)
-            if (chk[k][i] < 0) err |= 1u << k;
-        if (A.plev[i] < 0) err |= 1u << SWERR_PLEV;
-        if (A.cld[i] > 0) cftop = lay + 1;
-    }
-    if (A.plev[(size_t)nlay * ld + col] < 0) err |= 1u << SWERR_PLEV;
-    if (A.asdir[col] < 0 || A.aldir[col] < 0 || A.asdif[col] < 0 || A.aldif[col] < 0) err |= 1u << SWERR_ALB;
+    for (int lay = 0; lay < nlay; lay++)
+        if (A.cld[(size_t)lay * ld + col] > 0) cftop = lay + 1;
     const bool cloudy = cftop > 0;
     A.colcloudy[col] = (uint8_t)cftop;       // 1 + the highest layer with cloud fraction (lw_kernels.hpp k_validate_pwv)
     for (int k = 0; k < 4; k++) A.clearCounts[(size_t)k * ld + col] = cloudy ? 0 : NG_SW;   // rrtmg_sw_rad.F90:1520-1523
-    if (err) atomicOr(A.err, err);
+    if (A.asdir[col] < 0 || A.aldir[col] < 0 || A.asdif[col] < 0 || A.aldif[col] < 0) atomicOr(A.err, 1u << SWERR_ALB);
 }
 
-// aerosol assertions (SW/rrtmg_sw_rad.F90:380-383), one thread per (layer, column) so that the 2 x 14 band planes are read coalesced
-template <typename R>
-__global__ void __launch_bounds__(256) k_sw_validate_aer(SwArgs<R> A)
-{
-    const int col = blockIdx.x * blockDim.x + threadIdx.x;
-    const int lay = blockIdx.y;
-    if (col >= A.ncol) return;
-    bool bad = false;
-    for (int ib = 0; ib < NB_SW; ib++) {
-        const size_t j = ((size_t)ib * A.nlay + lay) * A.ld + col;
-        bad |= A.tauaer[j] < 0 || A.ssaaer[j] < 0;
-    }
-    if (bad) atomicOr(A.err, 1u << SWERR_AER);
-}
+// the aerosol assertions (SW/rrtmg_sw_rad.F90:380-383) of a band kernel on the layer's values it has loaded: a band's sweep visits
+// every layer of every column
+template <typename R> GR_DEV void sw_assert_aer(const SwArgs<R> &A, R ta, R om) { err_wave(ta < 0 || om < 0, A.err, SWERR_AER); }
 
-// SW/rrtmg_sw_rad.F90:1370-1387 (column amounts) + SW/rrtmg_sw_setcoef.F90:89-241
+// SW/rrtmg_sw_rad.F90:1370-1387 (column amounts) + SW/rrtmg_sw_setcoef.F90:89-241; the reference's input assertions on every per-layer
+// array (error bit k: the order of v[] below) and on plev
 template <typename R>
 __global__ void __launch_bounds__(256) k_sw_setcoef(SwArgs<R> A, const SwDev<R> *__restrict__ T)
 {
@@ -133,9 +115,19 @@ __global__ void __launch_bounds__(256) k_sw_setcoef(SwArgs<R> A, const SwDev<R> 
     const size_t i = (size_t)lay * ld + A.perm[col];          // API arrays: original column; workspace: compacted position
     const R amd = (R)28.9660, amw = (R)18.0160, stpfac = (R)296. / (R)1013.;
     const R pavel = A.play[i], tavel = A.tlay[i], h = A.h2o[i];
-    const R coldry = (A.plev[i] - A.plev[i + ld]) * (R)1.e3 * T->avogad /
+    const R pdn = A.plev[i], pup = A.plev[i + ld], co2 = A.co2[i], o3 = A.o3[i], ch4 = A.ch4[i], o2 = A.o2[i];
+    {
+        const R v[12] = {pavel, tavel, h, o3, co2, ch4, o2, A.cld[i], A.ciwp[i], A.clwp[i], A.rei[i], A.rel[i]};
+        uint32_t err = 0;
+#pragma unroll
+        for (int k = 0; k < 12; k++)
+            if (v[k] < 0) err |= 1u << k;
+        if (pdn < 0 || pup < 0) err |= 1u << SWERR_PLEV;
+        if (err) atomicOr(A.err, err);
+    }
+    const R coldry = (pdn - pup) * (R)1.e3 * T->avogad /
                      ((R)1.e2 * T->grav * (((R)1. - h) * amd + h * amw) * ((R)1. + h));
-    R colh2o = coldry * h, colco2 = coldry * A.co2[i], colo3 = coldry * A.o3[i], colch4 = coldry * A.ch4[i], colo2 = coldry * A.o2[i];
+    R colh2o = coldry * h, colco2 = coldry * co2, colo3 = coldry * o3, colch4 = coldry * ch4, colo2 = coldry * o2;
     const R plog = gr_log<R>(pavel);
     const int jp = clampi((int)((R)36. - (R)5 * (plog + (R)0.04)), 1, 58);
     const R fp = (R)5. * (T->preflog[jp - 1] - plog);
@@ -623,6 +615,7 @@ GR_DEV void sw_band_body(const SwArgs<R> &A, const SwDev<R> &T, const SwSolar<R>
             const uint32_t ab = ((uint32_t)lay * (uint32_t)ld + (uint32_t)pc) * (uint32_t)sizeof(R);
             const size_t bo = (size_t)(IBM - 1) * nlay * ld;
             ta = ldg(A.tauaer + bo, ab); om = ldg(A.ssaaer + bo, ab); as = ldg(A.asmaer + bo, ab);
+            sw_assert_aer<R>(A, ta, om);
         }
         const uint32_t cell0 = ((uint32_t)lay * (uint32_t)NG) * (uint32_t)n + ucol;
         const bool laycld = CLD && ccol && ldg(A.laycloudy, (uint32_t)lay * (uint32_t)n + ucol) != 0;

@@ -242,6 +242,7 @@ GR_DEV void swr_body(const SwArgs<R> &A, const SwDev<R> &T, const SwSolar<R> &SV
             __builtin_amdgcn_sched_barrier(0);      // one group's arithmetic at a time
 #endif
         }
+        sw_assert_aer<R>(A, ta, om);      // behind the layer's arithmetic: the values have arrived long ago
     }
 
     // ---- sweep B: TOA -> surface ---------------------------------------------------------------------------------------
