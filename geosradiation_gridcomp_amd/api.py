@@ -174,6 +174,43 @@ class Context:
         self._chk(rc)
         return out
 
+    def rrtmg_lw_na(self, ncol, nlay, psize, dudTs, play, plev, tlay, tlev, tsfc, emis,
+                    h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr,
+                    cldf, ciwp, clwp, rei, rel, iceflglw, liqflglw, tauaer, zm, alat, dyofyr, cloudLM, cloudMH,
+                    band_output=None, out=None):
+        """rrtmg_lw + the aerosol-free fluxes of the same call (geosrad_rrtmg_lw_na): the dict additionally holds
+        uflx_na, dflx_na, uflxc_na, dflxc_na, duflx_dTs_na, duflxc_dTs_na (nlay+1,ncol)."""
+        dt = self.dtype
+        c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=dt)
+        args2 = [c(x) for x in (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr,
+                                cldf, ciwp, clwp, rei, rel)]
+        play, plev, tlay, tlev, tsfc, emis, tauaer, zm, alat = map(c, (play, plev, tlay, tlev, tsfc, emis, tauaer, zm, alat))
+        assert play.shape == (nlay, ncol) and plev.shape == (nlay + 1, ncol)
+        if out is None:
+            out = {k + s: np.zeros((nlay + 1, ncol), dtype=dt) for k in ("uflx", "dflx", "uflxc", "dflxc", "duflx_dTs", "duflxc_dTs")
+                   for s in ("", "_na")}
+            out["clearCounts"] = np.zeros((4, ncol), dtype=np.int32)
+            out["olrb"] = np.zeros((ncol, NBNDLW), dtype=dt)
+            out["dolrb_dTs"] = np.zeros((ncol, NBNDLW), dtype=dt)
+        bo = np.zeros(NBNDLW, dtype=np.int32) if band_output is None else np.ascontiguousarray(band_output, dtype=np.int32)
+        ci = ctypes.c_int
+        o = lambda k: _p(out.get(k))
+        rc = self.L.geosrad_rrtmg_lw_na(
+            self.h, ci(ncol), ci(nlay), ci(psize), ci(1 if dudTs else 0), _p(play), _p(plev), _p(tlay), _p(tlev), _p(tsfc),
+            _p(emis), *[_p(a) for a in args2[:10]], *[_p(a) for a in args2[10:]], ci(iceflglw), ci(liqflglw), _p(tauaer),
+            _p(zm), _p(alat), ci(int(dyofyr)), ci(int(cloudLM)), ci(int(cloudMH)), o("clearCounts"), o("uflx"),
+            o("dflx"), o("uflxc"), o("dflxc"), o("duflx_dTs"), o("duflxc_dTs"), _p(bo), o("olrb"), o("dolrb_dTs"),
+            o("uflx_na"), o("dflx_na"), o("uflxc_na"), o("dflxc_na"), o("duflx_dTs_na"), o("duflxc_dTs_na"))
+        self._chk(rc)
+        return out
+
+    def rrtmg_lw_na_columns(self, inp, psize=4, dudTs=True, iceflg=3, liqflg=1, band_output=None, out=None):
+        """Convenience: `inp` as produced by synth.make_columns."""
+        nlay, ncol = inp["play"].shape
+        return self.rrtmg_lw_na(ncol, nlay, psize, dudTs, inp["play"], inp["plev"], inp["tlay"], inp["tlev"], inp["tsfc"],
+                                inp["emis"], *[inp[k] for k in _IN2D], iceflg, liqflg, inp.get("tauaer"), inp["zm"],
+                                inp["alat"], inp["dyofyr"], inp["cloudLM"], inp["cloudMH"], band_output=band_output, out=out)
+
     def rrtmg_lw_columns(self, inp, psize=4, dudTs=True, iceflg=3, liqflg=1, band_output=None, out=None):
         """Convenience: `inp` as produced by synth.make_columns."""
         nlay, ncol = inp["play"].shape
@@ -425,6 +462,24 @@ class Context:
             ci(len(rg)), _p(rg), v("uflx_rat"), v("dflx_rat"), v("duflx_dTs_rat"))
         self._chk(rc)
 
+    def rrtmg_lw_na_dev(self, stream, ncol, nlay, dudTs, ptr, iceflg, liqflg, dyofyr, cloudLM, cloudMH, rat_gas=(), band_output=None):
+        """rrtmg_lw_rats_dev (`rat_gas` may be empty) + the aerosol-free fluxes of the same call (geosrad_rrtmg_lw_na_dev):
+        ptr["uflx_na"], ["dflx_na"], ["uflxc_na"], ["dflxc_na"], and with dudTs ["duflx_dTs_na"], ["duflxc_dTs_na"] = device arrays
+        [nlay+1][ncol].  A call of the band-partials path throughout, like one with RATS diagnostics."""
+        from . import gridcomp as G
+        bo = np.zeros(NBNDLW, dtype=np.int32) if band_output is None else np.ascontiguousarray(band_output, dtype=np.int32)
+        rg = np.ascontiguousarray([G.RAT_GAS.index(g) if isinstance(g, str) else int(g) for g in rat_gas], dtype=np.int32)
+        v = lambda k: ctypes.c_void_p(ptr[k]) if ptr.get(k) else None
+        ci = ctypes.c_int
+        rc = self.L.geosrad_rrtmg_lw_na_dev(
+            self.h, ctypes.c_void_p(stream), ci(ncol), ci(nlay), ci(4), ci(1 if dudTs else 0), v("play"), v("plev"), v("tlay"),
+            v("tlev"), v("tsfc"), v("emis"), *[v(k) for k in _IN2D[:10]], *[v(k) for k in _IN2D[10:]], ci(iceflg), ci(liqflg),
+            v("tauaer"), v("zm"), v("alat"), ci(int(dyofyr)), ci(int(cloudLM)), ci(int(cloudMH)), v("clearCounts"), v("uflx"),
+            v("dflx"), v("uflxc"), v("dflxc"), v("duflx_dTs"), v("duflxc_dTs"), _p(bo), v("olrb"), v("dolrb_dTs"),
+            ci(len(rg)), _p(rg), v("uflx_rat"), v("dflx_rat"), v("duflx_dTs_rat"),
+            v("uflx_na"), v("dflx_na"), v("uflxc_na"), v("dflxc_na"), v("duflx_dTs_na"), v("duflxc_dTs_na"))
+        self._chk(rc)
+
     # ---- GridComp data path either side of the solvers (device pointers, GEOS layout) ---------------------------------------
     @staticmethod
     def _ptr_array(names, ptr):
@@ -457,6 +512,22 @@ class Context:
             self.h, ctypes.c_void_p(stream), ci(ncol), ci(lm), ci(nb_aer), self._ptr_array(G.LWD_IN, ptr), cs, ci(iceflg), ci(liqflg),
             ci(int(doy)), ci(int(lcldlm)), ci(int(lcldmh)), _p(bo), self._ptr_array(G.LWD_OUT, ptr), ci(len(rg)), _p(rg),
             self._ptr_array(G.LWD_RAT_OUT, ptr)))
+
+    def lw_driver_rrtmg_na_dev(self, stream, ncol, lm, nb_aer, ptr, consts, iceflg, liqflg, doy, lcldlm, lcldmh, na_ptr, rat_gas=(),
+                               band_output=None):
+        """lw_driver_rrtmg_rats_dev (`rat_gas` may be empty) with the aerosol-free INTERNALs of the same solver call
+        (geosrad_lw_driver_rrtmg_na_dev): `na_ptr` = name -> device address for gridcomp.LWNA_OUT ((LM+1, ncol); missing = not
+        associated; None = none of them).  Its DFDTSNA / DFDTSCNA are the real derivatives; ptr["DFDTSNA"] stays the reference's copy.
+        lw_update_flx_dev(rrtmg=False) reads the INTERNALs so filled."""
+        from . import gridcomp as G
+        bo = np.zeros(NBNDLW, dtype=np.int32) if band_output is None else np.ascontiguousarray(band_output, dtype=np.int32)
+        rg = np.ascontiguousarray([G.RAT_GAS.index(g) if isinstance(g, str) else int(g) for g in rat_gas], dtype=np.int32)
+        cs = (ctypes.c_double * len(G.LWD_CONST))(*consts)
+        ci = ctypes.c_int
+        self._chk(self.L.geosrad_lw_driver_rrtmg_na_dev(
+            self.h, ctypes.c_void_p(stream), ci(ncol), ci(lm), ci(nb_aer), self._ptr_array(G.LWD_IN, ptr), cs, ci(iceflg), ci(liqflg),
+            ci(int(doy)), ci(int(lcldlm)), ci(int(lcldmh)), _p(bo), self._ptr_array(G.LWD_OUT, ptr), ci(len(rg)), _p(rg),
+            self._ptr_array(G.LWD_RAT_OUT, ptr), None if na_ptr is None else self._ptr_array(G.LWNA_OUT, na_ptr)))
 
     def lw_update_rats_dev(self, stream, ncol, lm, nrats, ptr):
         """RATS exports of Update_Flx (GEOS_IrradGridComp.F90:4036-4120).  `ptr`: name -> device address for gridcomp.LWR_IN and

@@ -633,7 +633,9 @@ enum ChOutIx { CO_FLXU, CO_FLCU, CO_FLAU, CO_FLXAU, CO_FLXD, CO_FLCD, CO_FLAD, C
 // order of the `in` pointer array of lw_dev / lw_host
 enum LwIn { I_PLAY, I_PLEV, I_TLAY, I_TLEV, I_TSFC, I_EMIS, I_H2O, I_O3, I_CO2, I_CH4, I_N2O, I_O2, I_CFC11, I_CFC12, I_CFC22,
             I_CCL4, I_CLDF, I_CIWP, I_CLWP, I_REI, I_REL, I_TAUAER, I_ZM, I_ALAT, I_NIN };
-enum LwOutIx { O_UFLX, O_DFLX, O_UFLXC, O_DFLXC, O_DUFLX, O_DUFLXC, O_OLRB, O_DOLRB, O_NOUT };
+// O_UFLX_NA ..: the aerosol-free twins of the first six (geosrad_rrtmg_lw_na[_dev]); null from every other entry point
+enum LwOutIx { O_UFLX, O_DFLX, O_UFLXC, O_DFLXC, O_DUFLX, O_DUFLXC, O_OLRB, O_DOLRB, O_UFLX_NA, O_DFLX_NA, O_UFLXC_NA, O_DFLXC_NA,
+               O_DUFLX_NA, O_DUFLXC_NA, O_NOUT };
 
 // Shape of every host array of the pointer lists above, stated here once: Fortran (ncol, rows) of records of `rec` reals, the column
 // index the fastest but for the one inside a record (olrb is (16, ncol): one row of 16-real records; so are the stage dumps).  The
@@ -737,7 +739,7 @@ template <typename R> struct Ctx : geosrad_ctx {
     std::map<std::tuple<int, int, int, int>, PlanEntry> plans;
     // workspace
     DevBuf<> d_ws; int ws_ncol = 0, ws_nlay = 0;
-    DevBuf<> d_zero;      // all-zero (nlay, ncol) plane of the RATS passes
+    DevBuf<> d_zero;      // all-zero (nlay, ncol) plane of the RATS passes, and the second set of band partials they share with the aerosol-free pass
     DevBuf<int> d_bandflags;      // Update_Flx band exports: "band has a non-zero flux somewhere"
     DevBuf<uint32_t> d_err;
     // plain staging of mcica_host, the one host-pointer entry point that does not go through host_pipeline
@@ -917,12 +919,12 @@ template <typename R> struct Ctx : geosrad_ctx {
         return sync_T();
     }
 
-    // not counted: d_ws_swc, d_mc, d_zero, d_xcw, d_tab_so, the fixed-size structs and McICA plans, the pipeline slots
+    // not counted: d_ws_swc, d_mc, d_xcw, d_tab_so, the fixed-size structs and McICA plans, the pipeline slots
     // (d_ws_hb is counted: like the solvers' workspaces it is sized by the chunk, two real planes of nlay x chunk columns)
     size_t workspace_bytes() const override
     {
         size_t t = 0;
-        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_ws_hb, &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
+        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_ws_hb, &d_zero, &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
             t += b->bytes;
         return t;
     }
@@ -1074,8 +1076,8 @@ template <typename R> struct Ctx : geosrad_ctx {
 
     // RRTMG_LW band sweeps of one chunk and the band reduction behind them.  lw_cols: (layer, g-point) intermediates in LDS, fluxes written
     // directly (lw_cols_kernels.hpp), no reduction; with A.dbg_taug the stage-dump instantiation; lw_split; else lw_bands: lane = column
-    // with the parked cells (2-byte Pade indices) in HBM.  allow_cols: false for a call with RATS diagnostics, whose passes need the
-    // per-band partials of the reduction - such a call takes that path throughout.  O.part_alt: the pass's own partials (RATS).
+    // with the parked cells (2-byte Pade indices) in HBM.  allow_cols: false for a call with RATS diagnostics or the aerosol-free fluxes, whose
+    // passes need the per-band partials of the reduction - such a call takes that path throughout.  O.part_alt: the pass's own partials.
     int lw_sweeps(hipStream_t st, const LwArgs<R> &A, const LwOut<R> &O, bool allow_cols)
     {
         const dim3 blk(256);
@@ -1135,22 +1137,27 @@ template <typename R> struct Ctx : geosrad_ctx {
         const int nc_max = chunk_cols(ncol, (long)(0xFFFFFFFFull / ((unsigned long long)nlay * 16ull * sizeof(R2))) & ~255L);
         if (const int rc = ensure_ws(nc_max, nlay)) return rc;
         const int nrats = rats ? rats->n : 0;
+        // the aerosol-free fluxes: requested by their first array (geosrad_rrtmg_lw_na[_dev] have checked the set, the driver passes its own)
+        const bool na = out[O_UFLX_NA] != nullptr;
         R *zero = nullptr, *rat_part = nullptr;
         if (nrats > 0) {
             if (nrats > GEOSRAD_RAT_NGAS || !rats->uflx || !rats->dflx || (dudTs && !rats->duflx_dTs))
                 return fail(GEOSRAD_EINVAL, "RATS: at most 8 gases; uflx_rat / dflx_rat (and duflx_dTs_rat with dudTs) must not be null");
             for (int r = 0; r < nrats; r++)
                 if (rats->gas[r] < 0 || rats->gas[r] >= GEOSRAD_RAT_NGAS) return fail(GEOSRAD_EINVAL, "RATS: unknown gas code");
+        }
+        if (nrats > 0 || na) {
             // an all-zero (nlay, ncol) plane stands for the removed gas's mixing ratio (and for pwvcm of a dry column); behind it
-            // a second set of band partials, so that the main call's stay available to the bands a gas does not touch
+            // a second set of band partials, so that the main call's stay available to the bands a gas does not touch.  The
+            // aerosol-free pass needs the partials alone.
             auto carve = [&](Carve c) {
-                zero = c.take<R>((size_t)nlay * ncol);
+                if (nrats > 0) zero = c.take<R>((size_t)nlay * ncol);
                 rat_part = c.take<R>((size_t)6 * NB_LW * (nlay + 1) * nc_max);
                 return c.off;
             };
             if (d_zero.reserve(carve(Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the RATS workspace failed");
             carve(Carve(d_zero));
-            HIPCHK(hipMemsetAsync(zero, 0, (char *)rat_part - (char *)zero, st));
+            if (zero) HIPCHK(hipMemsetAsync(zero, 0, (char *)rat_part - (char *)zero, st));
         }
 
         return chunk_walk(ncol, nc_max, [&](int c0, int nc) -> int {
@@ -1174,7 +1181,29 @@ template <typename R> struct Ctx : geosrad_ctx {
             O.uflx = Q(O_UFLX); O.dflx = Q(O_DFLX); O.uflxc = Q(O_UFLXC); O.dflxc = Q(O_DFLXC);
             O.duflx_dTs = Q(O_DUFLX); O.duflxc_dTs = Q(O_DUFLXC);
             O.olrb = (R *)out[O_OLRB]; O.dolrb_dTs = (R *)out[O_DOLRB]; O.col0 = c0;
-            if (const int e = lw_sweeps(st, A, O, nrats <= 0)) return e;
+            if (const int e = lw_sweeps(st, A, O, nrats <= 0 && !na)) return e;
+
+            // Aerosol-free fluxes: the reference's RRTMG branch leaves FLXA / FLA undefined (GEOS_IrradGridComp.F90:3552-3556, :3927-3990);
+            // its other two branches compute them.  Nothing the clouds decide depends on the aerosols, and neither does setcoef, whose
+            // output of the main pass is still in the workspace: the fluxes cost the band sweeps with a null aerosol pointer and one
+            // more reduction.  The sweep writes all 16 bands into the second set of partials, which the RATS passes below use after
+            // it: one stream runs the passes in order, so each pass's reduction has read the buffer before the next sweep writes it.
+            // Without aerosols there is nothing to remove: the main pass's partials are reduced once more.
+            if (na) {
+                LwOut<R> ON{};      // band_output all zero: olrb / dolrb_dTs are the main pass's
+                ON.uflx = Q(O_UFLX_NA); ON.dflx = Q(O_DFLX_NA); ON.uflxc = Q(O_UFLXC_NA); ON.dflxc = Q(O_DFLXC_NA);
+                ON.duflx_dTs = Q(O_DUFLX_NA); ON.duflxc_dTs = Q(O_DUFLXC_NA); ON.col0 = c0;
+                if (A.tauaer) {
+                    LwArgs<R> B = A;
+                    B.tauaer = nullptr; B.dbg_taug = nullptr; B.dbg_pfracs = nullptr; B.band_mask = LW_ALL_BANDS;
+                    ON.part_alt = rat_part; ON.alt_mask = LW_ALL_BANDS;
+                    if (const int e = lw_sweeps(st, B, ON, false)) return e;
+                } else {
+                    span_begin(5, st);
+                    hipLaunchKernelGGL(k_lw_reduce<R>, dim3(grid256(nc), nlay + 1), dim3(256), 0, st, A, ON);
+                    span_end(st);
+                }
+            }
 
             // RATS diagnostics (GEOS_IrradGridComp.F90:3405-3468): the reference calls the whole of rrtmg_lw once more per listed
             // gas with that gas's mixing ratio set to zero and keeps the total-sky uflx, dflx, duflx_dTs of each call.  Nothing
@@ -1232,8 +1261,11 @@ template <typename R> struct Ctx : geosrad_ctx {
             if (!in[k] && k != GEOSRAD_LWD_CO2_3D && k != GEOSRAD_LWD_TAUA && k != GEOSRAD_LWD_SSAA) return fail(GEOSRAD_EINVAL, "null input array");
         if ((in[GEOSRAD_LWD_TAUA] == nullptr) != (in[GEOSRAD_LWD_SSAA] == nullptr)) return fail(GEOSRAD_EINVAL, "TAUA and SSAA go together");
         const size_t n = (size_t)ncol, cl = n * lm, cv = n * (lm + 1);
-        R *lay[18], *lev[2], *tsfc, *alat, *emis, *aerp, *flux[6], *olrb, *dolrb, *rat[3];
+        R *lay[18], *lev[2], *tsfc, *alat, *emis, *aerp, *flux[6], *olrb, *dolrb, *rat[3], *flux_na[6];
         int32_t *cc;
+        // the aerosol-free INTERNALs (geosrad_lw_driver_rrtmg_na_dev): without one of them the call is the RATS driver's
+        bool na = false;
+        for (int k = 0; C.na_out && k < GEOSRAD_LWNA_NOUT; k++) na = na || C.na_out[k];
         auto carve = [&](Carve c) {
             for (auto &q : lay) q = c.take<R>(cl);
             for (auto &q : lev) q = c.take<R>(cv);
@@ -1242,6 +1274,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             olrb = c.take<R>(n * 16); dolrb = c.take<R>(n * 16);
             cc = (int32_t *)c.take<R>(n * 4);      // clearCounts (ncol, 4) int32 in 4 n reals: twice the bytes in fp64, kept so that the layout stays as it was
             for (auto &q : rat) q = c.take<R>(cv * (size_t)nrats);
+            for (auto &q : flux_na) q = c.take<R>(na ? cv : 0);      // the solver's six aerosol-free planes
             return c.off;
         };
         if (const int rc = drv_reserve(0, carve(Carve()))) return rc;
@@ -1274,6 +1307,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         void *lout[O_NOUT] = {flux[0], flux[1], flux[2], flux[3], flux[4], flux[5],
                               out[GEOSRAD_LWD_OLRB] ? out[GEOSRAD_LWD_OLRB] : (void *)olrb,
                               out[GEOSRAD_LWD_DOLRB] ? out[GEOSRAD_LWD_DOLRB] : (void *)dolrb};
+        if (na) for (int k = 0; k < 6; k++) lout[O_UFLX_NA + k] = flux_na[k];
         static const int32_t no_bands[16] = {0};
         LwRats RT{};
         RT.n = nrats; RT.uflx = rat[0]; RT.dflx = rat[1]; RT.duflx_dTs = rat[2];
@@ -1292,6 +1326,13 @@ template <typename R> struct Ctx : geosrad_ctx {
         Q.duflxc = flux[5]; Q.clearCounts = cc; Q.emis = A.emis; Q.ts = A.ts;
         bind_out<Fields<LwdPost<R>>>(Q, out);
         hipLaunchKernelGGL((k_lwd_post<R>), dim3(gx, lm + 1), blk, 0, st, Q);
+        if (na) {
+            LwdPostNa<R> N{};
+            N.ncol = ncol; N.lm = lm;
+            N.uflx = flux_na[0]; N.dflx = flux_na[1]; N.uflxc = flux_na[2]; N.dflxc = flux_na[3]; N.duflx = flux_na[4]; N.duflxc = flux_na[5];
+            bind_out<Fields<LwdPostNa<R>>>(N, C.na_out);
+            hipLaunchKernelGGL((k_lwd_post_na<R>), dim3(gx, lm + 1), blk, 0, st, N);
+        }
         HIPCHK(hipGetLastError());
         return GEOSRAD_OK;
     }
@@ -1943,6 +1984,8 @@ template <typename R> struct Ctx : geosrad_ctx {
             if (any_bo && out[k] && (k == O_OLRB || dudTs)) H.add(out[k], out[k], lw_out_shape(k, L), &dout[k]);
         for (int k = 0; k < O_OLRB; k++)
             if (out[k] && (dudTs || (k != O_DUFLX && k != O_DUFLXC))) H.add(nullptr, out[k], lw_out_shape(k, L), &dout[k]);
+        for (int k = O_UFLX_NA; k < O_NOUT; k++)
+            if (out[k] && (dudTs || k < O_DUFLX_NA)) H.add(nullptr, out[k], lw_out_shape(k, L), &dout[k]);
         H.add_clear_counts(clearCounts, &dcc);
         if (taug) { H.add(nullptr, taug, lw_dump_shape(L), &ddump[0]); H.add(nullptr, pfracs, lw_dump_shape(L), &ddump[1]); }
         return host_call(ncol, H, 0, [&](hipStream_t st, int nc) {
@@ -3232,6 +3275,53 @@ int geosrad_rrtmg_lw_rats_dev(geosrad_ctx *c, void *stream, int ncol, int nlay, 
                      band_output, nullptr, nullptr, nrats > 0 ? &RT : nullptr);
 }
 
+// the `out` table of the aerosol-free entry points: all four flux arrays, and with dudTs both derivatives (ignored without)
+#define LW_PACK_OUT_NA()                                                                                                             \
+    if (!uflx_na || !dflx_na || !uflxc_na || !dflxc_na || (dudTs && (!duflx_dTs_na || !duflxc_dTs_na)))                              \
+        return c->fail(GEOSRAD_EINVAL, "aerosol-free fluxes: uflx_na .. dflxc_na (and the two derivatives with dudTs) must not be null"); \
+    void *out[O_NOUT] = {uflx, dflx, uflxc, dflxc, duflx_dTs, duflxc_dTs, olrb, dolrb_dTs, uflx_na, dflx_na, uflxc_na, dflxc_na,    \
+                         dudTs ? duflx_dTs_na : nullptr, dudTs ? duflxc_dTs_na : nullptr}
+
+int geosrad_rrtmg_lw_na(geosrad_ctx *c, int ncol, int nlay, int psize, int dudTs, const void *play, const void *plev, const void *tlay,
+                        const void *tlev, const void *tsfc, const void *emis, const void *h2ovmr, const void *o3vmr, const void *co2vmr,
+                        const void *ch4vmr, const void *n2ovmr, const void *o2vmr, const void *cfc11vmr, const void *cfc12vmr,
+                        const void *cfc22vmr, const void *ccl4vmr, const void *cldf, const void *ciwp, const void *clwp, const void *rei,
+                        const void *rel, int iceflglw, int liqflglw, const void *tauaer, const void *zm, const void *alat, int dyofyr,
+                        int cloudLM, int cloudMH, int32_t *clearCounts, void *uflx, void *dflx, void *uflxc, void *dflxc, void *duflx_dTs,
+                        void *duflxc_dTs, const int32_t *band_output, void *olrb, void *dolrb_dTs, void *uflx_na, void *dflx_na,
+                        void *uflxc_na, void *dflxc_na, void *duflx_dTs_na, void *duflxc_dTs_na)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    (void)psize;
+    LW_PACK_IN();
+    LW_PACK_OUT_NA();
+    return c->lw_host(ncol, nlay, dudTs, in, iceflglw, liqflglw, dyofyr, cloudLM, cloudMH, clearCounts, out, band_output, nullptr, nullptr);
+}
+
+int geosrad_rrtmg_lw_na_dev(geosrad_ctx *c, void *stream, int ncol, int nlay, int psize, int dudTs, const void *play, const void *plev,
+                            const void *tlay, const void *tlev, const void *tsfc, const void *emis, const void *h2ovmr, const void *o3vmr,
+                            const void *co2vmr, const void *ch4vmr, const void *n2ovmr, const void *o2vmr, const void *cfc11vmr,
+                            const void *cfc12vmr, const void *cfc22vmr, const void *ccl4vmr, const void *cldf, const void *ciwp,
+                            const void *clwp, const void *rei, const void *rel, int iceflglw, int liqflglw, const void *tauaer,
+                            const void *zm, const void *alat, int dyofyr, int cloudLM, int cloudMH, int32_t *clearCounts, void *uflx,
+                            void *dflx, void *uflxc, void *dflxc, void *duflx_dTs, void *duflxc_dTs, const int32_t *band_output,
+                            void *olrb, void *dolrb_dTs, int nrats, const int32_t *rat_gas, void *uflx_rat, void *dflx_rat,
+                            void *duflx_dTs_rat, void *uflx_na, void *dflx_na, void *uflxc_na, void *dflxc_na, void *duflx_dTs_na,
+                            void *duflxc_dTs_na)
+{
+    if (!c || !clearCounts) return GEOSRAD_EINVAL;
+    if (nrats < 0 || nrats > GEOSRAD_RAT_NGAS || (nrats > 0 && !rat_gas)) return c->fail(GEOSRAD_EINVAL, "bad RATS arguments");
+    (void)psize;
+    LW_PACK_IN();
+    LW_PACK_OUT_NA();
+    geosrad_ctx::LwRats RT{};
+    RT.n = nrats; RT.uflx = uflx_rat; RT.dflx = dflx_rat; RT.duflx_dTs = duflx_dTs_rat;
+    for (int r = 0; r < nrats; r++) RT.gas[r] = rat_gas[r];
+    return c->lw_dev((hipStream_t)stream, ncol, nlay, dudTs, in, iceflglw, liqflglw, dyofyr, cloudLM, cloudMH, clearCounts, out,
+                     band_output, nullptr, nullptr, nrats > 0 ? &RT : nullptr);
+}
+#undef LW_PACK_OUT_NA
+
 // The drivers with a call record (gridcomp_kernels.hpp): an entry point fills it, its family's one statement passes it on (a tile's through swd_merge).
 static int lwd_call(geosrad_ctx *c, void *st, const LwdCall &C) { return !c || !C.in || !C.consts || !C.out ? GEOSRAD_EINVAL : c->lw_driver_dev((hipStream_t)st, C); }
 #define LWD_COMMON ncol, lm, nb_aer, in, consts, iceflglw, liqflglw, doy, lcldlm, lcldmh, band_output, out
@@ -3246,6 +3336,13 @@ int geosrad_lw_driver_rrtmg_rats_dev(geosrad_ctx *c, void *stream, int ncol, int
                                      void *const *out, int nrats, const int32_t *rat_gas, void *const *rat_out)
 {
     return lwd_call(c, stream, {LWD_COMMON, nrats, rat_gas, rat_out});
+}
+
+int geosrad_lw_driver_rrtmg_na_dev(geosrad_ctx *c, void *stream, int ncol, int lm, int nb_aer, const void *const *in, const double *consts,
+                                   int iceflglw, int liqflglw, int doy, int lcldlm, int lcldmh, const int32_t *band_output,
+                                   void *const *out, int nrats, const int32_t *rat_gas, void *const *rat_out, void *const *na_out)
+{
+    return lwd_call(c, stream, {LWD_COMMON, nrats, rat_gas, rat_out, na_out});
 }
 #undef LWD_COMMON
 static int swd_call(geosrad_ctx *c, void *stream, SwdCall C)

@@ -89,10 +89,11 @@ template <typename R> struct Fields<LwdArgs<R>> { using S = LwdArgs<R>;
     GR_TABLE(in, GEOSRAD_LWD_NIN, &S::ple, &S::pl, &S::t, &S::q, &S::o3, &S::ch4, &S::n2o, &S::co2_3d, &S::cfc11, &S::cfc12, &S::hcfc22, &S::fcld, &S::cwc_liq,
              &S::cwc_ice, &S::reff_liq, &S::reff_ice, &S::taua, &S::ssaa, &S::ts, &S::emis, &S::lats, &S::t2m);
 };
-// geosrad_lw_driver_rrtmg*_dev, as geosrad.h has it (nrats == 0 without the RATS diagnostics)
+// geosrad_lw_driver_rrtmg*_dev, as geosrad.h has it (nrats == 0 without the RATS diagnostics, na_out null without the aerosol-free INTERNALs)
 struct LwdCall {
     int ncol, lm, nb; const void *const *in; const double *consts; int iceflg, liqflg, doy, lcldlm, lcldmh; const int32_t *band_output; void *const *out;
     int nrats; const int32_t *rat_gas; void *const *rat_out;
+    void *const *na_out;
 };
 // interface temperature of model level k (1..LM+1), IRR:3248-3256
 template <typename R> GR_DEV R lwd_tlev(const LwdArgs<R> &A, int k, int ij)
@@ -246,6 +247,34 @@ template <typename R> __global__ void __launch_bounds__(256) k_lwd_post(LwdPost<
         if (P.cldmdlw) P.cldmdlw[ij] = (R)1.0 - (R)P.clearCounts[(size_t)2 * n + ij] / ng;
         if (P.cldlolw) P.cldlolw[ij] = (R)1.0 - (R)P.clearCounts[(size_t)3 * n + ij] / ng;
     }
+}
+
+// Aerosol-free share of the un-flip, with the conventions the reference's other two branches have for these INTERNALs (IRR:3506-3515 signs,
+// :3604-3607 net fluxes): one thread per (column, GEOS level K = 0..LM).  DFDTSNA / DFDTSCNA are the aerosol-free pass's own derivatives.
+template <typename R> struct LwdPostNa {
+    int ncol, lm;
+    const R *uflx, *dflx, *uflxc, *dflxc, *duflx, *duflxc;      // RRTMG without aerosols (ncol, LM+1), 1 = surface
+    R *flxau_int, *flxad_int, *flau_int, *flad_int, *flxa_int, *fla_int, *dfdtsna, *dfdtscna;      // (IM,JM,0:LM); any may be null
+};
+template <typename R> struct Fields<LwdPostNa<R>> { using S = LwdPostNa<R>;
+    GR_TABLE(out, GEOSRAD_LWNA_NOUT, &S::flxau_int, &S::flxad_int, &S::flau_int, &S::flad_int, &S::flxa_int, &S::fla_int, &S::dfdtsna, &S::dfdtscna);
+};
+template <typename R> __global__ void __launch_bounds__(256) k_lwd_post_na(LwdPostNa<R> P)
+{
+#pragma clang fp contract(off)      // the statements below are the reference's, operation by operation
+    const int ij = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ij >= P.ncol) return;
+    const int n = P.ncol, lm = P.lm, K = blockIdx.y, LV = lm - K + 1;
+    const size_t s = (size_t)(LV - 1) * n + ij, o = (size_t)K * n + ij;
+    const R fu = -P.uflx[s], fd = P.dflx[s], cu = -P.uflxc[s], cd = P.dflxc[s];
+    if (P.flxau_int) P.flxau_int[o] = fu;
+    if (P.flxad_int) P.flxad_int[o] = fd;
+    if (P.flau_int) P.flau_int[o] = cu;
+    if (P.flad_int) P.flad_int[o] = cd;
+    if (P.flxa_int) P.flxa_int[o] = fd + fu;
+    if (P.fla_int) P.fla_int[o] = cd + cu;
+    if (P.dfdtsna) P.dfdtsna[o] = -P.duflx[s];
+    if (P.dfdtscna) P.dfdtscna[o] = -P.duflxc[s];
 }
 
 // RATS share of the un-flip (IRR:3522-3530) and of the net fluxes (IRR:3614): one thread per (column, GEOS level K, gas)

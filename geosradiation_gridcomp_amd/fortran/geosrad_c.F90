@@ -7,7 +7,7 @@ module geosrad_c
    private
    public :: geosrad_ctx_handle, geosrad_fail, geosrad_warn, geosrad_data_path, geosrad_load_tables_sw, geosrad_rrtmg_sw, geosrad_rrtmg_sw_radval, geosrad_load_tables_chou_lw, geosrad_load_tables_chou_sw, geosrad_irrad, geosrad_sorad
    public :: geosrad_create, geosrad_destroy, geosrad_last_error, geosrad_load_tables_lw, geosrad_load_inhomogeneity
-   public :: geosrad_set_corr_lengths, geosrad_rrtmg_lw, geosrad_mcica, geosrad_clearcounts, geosrad_read_table
+   public :: geosrad_set_corr_lengths, geosrad_rrtmg_lw, geosrad_rrtmg_lw_na, geosrad_mcica, geosrad_clearcounts, geosrad_read_table
    public :: geosrad_set_overcast, geosrad_get_overcast, GEOSRAD_OVERCAST_IRRAD, GEOSRAD_OVERCAST_SORAD
 
    integer(c_int), parameter :: GEOSRAD_OVERCAST_IRRAD = 1, GEOSRAD_OVERCAST_SORAD = 2     ! geosrad_set_overcast flags
@@ -114,6 +114,20 @@ module geosrad_c
          type(c_ptr), value :: play, plev, tlay, tlev, tsfc, emis, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, &
             cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, cldf, ciwp, clwp, rei, rel, tauaer, zm, alat, clearCounts, &
             uflx, dflx, uflxc, dflxc, duflx_dTs, duflxc_dTs, band_output, olrb, dolrb_dTs
+      end function
+      ! geosrad_rrtmg_lw + the six flux arrays of the same columns without aerosols, from the same call
+      integer(c_int) function geosrad_rrtmg_lw_na(ctx, ncol, nlay, psize, dudTs, play, plev, tlay, tlev, tsfc, emis, &
+            h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, &
+            cldf, ciwp, clwp, rei, rel, iceflglw, liqflglw, tauaer, zm, alat, dyofyr, cloudLM, cloudMH, clearCounts, &
+            uflx, dflx, uflxc, dflxc, duflx_dTs, duflxc_dTs, band_output, olrb, dolrb_dTs, &
+            uflx_na, dflx_na, uflxc_na, dflxc_na, duflx_dTs_na, duflxc_dTs_na) bind(C, name='geosrad_rrtmg_lw_na')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: ncol, nlay, psize, dudTs, iceflglw, liqflglw, dyofyr, cloudLM, cloudMH
+         type(c_ptr), value :: play, plev, tlay, tlev, tsfc, emis, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, &
+            cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, cldf, ciwp, clwp, rei, rel, tauaer, zm, alat, clearCounts, &
+            uflx, dflx, uflxc, dflxc, duflx_dTs, duflxc_dTs, band_output, olrb, dolrb_dTs, &
+            uflx_na, dflx_na, uflxc_na, dflxc_na, duflx_dTs_na, duflxc_dTs_na
       end function
       integer(c_int) function geosrad_mcica(ctx, ncol, nsubcol, nlay, zmid, alat, doy, play, cldfrac, ciwp, clwp, cwp_tiny, &
             seed_order, cldy, ciwp_s, clwp_s) bind(C, name='geosrad_mcica')

@@ -11,6 +11,7 @@ module geosrad_gridcomp
    public :: lw_driver_rrtmg, lw_driver_rrtmg_rats, lw_update_rats, lw_update_bands, sw_update_surface, sw_update_clouds, sw_update_cldhb, sw_driver_rrtmg, sw_driver_chou, lw_driver_chou, lw_chou_post, lw_update_flx, sw_update_export, rad_tendencies
    public :: lit_index, lit_pack, lit_unpack, sw_driver_rrtmg_lit, sw_driver_chou_lit
    public :: sw_update_obio, sw_driver_rrtmg_obio, sw_driver_rrtmg_obio_lit
+   public :: lw_driver_rrtmg_na
    ! ocean-biology coupling (SOLAR_TO_OBIO): the schemes of sw_update_obio (GEOSRAD_OBIO_*) and the number of OBIO bands
    integer, parameter, public :: OBIO_CHOU = 0, OBIO_RRTMG = 1, OBIO_BANDS = 2, NB_OBIO = 33
    public :: dev_alloc, dev_free, dev_put, dev_get, dev_sync
@@ -47,6 +48,9 @@ module geosrad_gridcomp
    integer, parameter, public :: LWR_DOLR = 1, LWR_DLWS = 2, LWR_DFLNS = 3, LWR_DSFCEM = 4, LWR_NETTRAP = 5, LWR_COLTRAP = 6, LWR_FLX = 7, &
       LWR_DFDTS_OUT = 8, LWR_NOUT = 8
    integer, parameter, public :: LWD_FLXU_RAT = 1, LWD_FLXD_RAT = 2, LWD_FLX_RAT = 3, LWD_DFDTS_RAT = 4, LWD_SFCEM_RAT = 5, LWD_NRATOUT = 5
+   ! ---- GEOSRAD_LWNA_* (aerosol-free INTERNALs of the RRTMG branch) ----
+   integer, parameter, public :: LWNA_FLXAU_INT = 1, LWNA_FLXAD_INT = 2, LWNA_FLAU_INT = 3, LWNA_FLAD_INT = 4, LWNA_FLXA_INT = 5, &
+      LWNA_FLA_INT = 6, LWNA_DFDTSNA = 7, LWNA_DFDTSCNA = 8, LWNA_NOUT = 8
    ! ---- GEOSRAD_LWC_* ----
    integer, parameter, public :: LWC_FLXU_INT = 1, LWC_FLCU_INT = 2, LWC_FLAU_INT = 3, LWC_FLXAU_INT = 4, LWC_FLXD_INT = 5, LWC_FLCD_INT = 6, &
       LWC_FLAD_INT = 7, LWC_FLXAD_INT = 8, LWC_DFDTS = 9, LWC_TS = 10, LWC_NIN = 10
@@ -117,6 +121,15 @@ module geosrad_gridcomp
          type(c_ptr), value :: ctx, stream
          integer(c_int), value :: ncol, lm, nb_aer, iceflglw, liqflglw, doy, lcldlm, lcldmh, nrats
          type(c_ptr), intent(in) :: fin(*), fout(*), rat_out(*)
+         real(c_double), intent(in) :: consts(*)
+         integer(c_int), intent(in) :: band_output(*), rat_gas(*)
+      end function
+      integer(c_int) function geosrad_lw_driver_rrtmg_na_dev(ctx, stream, ncol, lm, nb_aer, fin, consts, iceflglw, liqflglw, doy, lcldlm, &
+            lcldmh, band_output, fout, nrats, rat_gas, rat_out, na_out) bind(C, name='geosrad_lw_driver_rrtmg_na_dev')
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: ctx, stream
+         integer(c_int), value :: ncol, lm, nb_aer, iceflglw, liqflglw, doy, lcldlm, lcldmh, nrats
+         type(c_ptr), intent(in) :: fin(*), fout(*), rat_out(*), na_out(*)
          real(c_double), intent(in) :: consts(*)
          integer(c_int), intent(in) :: band_output(*), rat_gas(*)
       end function
@@ -360,8 +373,21 @@ contains
       logical, intent(in) :: band_output(16)
       character(len=*), intent(in) :: nameRATS(nrats)
       integer(c_int) :: bo(16), gas(8)
+      call rat_codes(nrats, nameRATS, gas)
+      bo = merge(1_c_int, 0_c_int, band_output)
+      if (geosrad_lw_driver_rrtmg_rats_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(lm,c_int), int(nb_aer,c_int), fin, &
+            consts, int(iceflglw,c_int), int(liqflglw,c_int), int(doy,c_int), int(lcldlm,c_int), int(lcldmh,c_int), bo, fout, &
+            int(nrats,c_int), gas, rat_out) /= 0) call geosrad_fail('LW_Driver (RRTMG, RATS)')
+   end subroutine
+
+   ! GEOSRAD_RAT_* codes of the names under RATS_DIAGNOSTICS
+   subroutine rat_codes(nrats, nameRATS, gas)
+      integer, intent(in) :: nrats
+      character(len=*), intent(in) :: nameRATS(nrats)
+      integer(c_int), intent(out) :: gas(8)
       integer :: n
       if (nrats > 8) error stop 'LW_Driver (RRTMG): more than 8 RATS'
+      gas = 0
       do n = 1, nrats
          select case (trim(nameRATS(n)))
          case ('H2O');    gas(n) = 0
@@ -375,10 +401,25 @@ contains
          case default;    error stop 'LW_Driver (RRTMG): unknown RAT name'
          end select
       end do
+   end subroutine
+
+   ! the same with the aerosol-free INTERNALs the reference's RRTMG branch leaves undefined (GEOS_IrradGridComp.F90:3552-3556, :3927-3990),
+   ! from the same solver call (nrats may be 0): na_out = FLXAU_INT, FLXAD_INT, FLAU_INT, FLAD_INT, FLXA_INT, FLA_INT and the aerosol-free
+   ! pass's own DFDTSNA, DFDTSCNA (IM,JM,0:LM) on the device, c_null_ptr = not associated.  fout(LWD_DFDTSNA) stays the reference's copy of
+   ! DFDTS.  lw_update_flx with use_rrtmg = .false. then reads them as real fields (FLXA, FLA, OLRA, LWSA ...).
+   subroutine lw_driver_rrtmg_na(ncol, lm, nb_aer, fin, consts, iceflglw, liqflglw, doy, lcldlm, lcldmh, band_output, fout, nrats, &
+         nameRATS, rat_out, nout)
+      integer, intent(in) :: ncol, lm, nb_aer, iceflglw, liqflglw, doy, lcldlm, lcldmh, nrats
+      type(c_ptr), intent(in) :: fin(LWD_NIN), fout(LWD_NOUT), rat_out(LWD_NRATOUT), nout(LWNA_NOUT)
+      real(c_double), intent(in) :: consts(LWD_NCONST)
+      logical, intent(in) :: band_output(16)
+      character(len=*), intent(in) :: nameRATS(nrats)
+      integer(c_int) :: bo(16), gas(8)
+      call rat_codes(nrats, nameRATS, gas)
       bo = merge(1_c_int, 0_c_int, band_output)
-      if (geosrad_lw_driver_rrtmg_rats_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(lm,c_int), int(nb_aer,c_int), fin, &
+      if (geosrad_lw_driver_rrtmg_na_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(lm,c_int), int(nb_aer,c_int), fin, &
             consts, int(iceflglw,c_int), int(liqflglw,c_int), int(doy,c_int), int(lcldlm,c_int), int(lcldmh,c_int), bo, fout, &
-            int(nrats,c_int), gas, rat_out) /= 0) call geosrad_fail('LW_Driver (RRTMG, RATS)')
+            int(nrats,c_int), gas, rat_out, nout) /= 0) call geosrad_fail('LW_Driver (RRTMG, aerosol-free)')
    end subroutine
 
    ! RATS exports of Update_Flx (GEOS_IrradGridComp.F90:4036-4120): fout(LWR_DOLR) = device array (IM,JM,nRATS) whose slice n is the export

@@ -77,7 +77,7 @@ const char *geosrad_last_error(const geosrad_ctx *ctx);
 int geosrad_real_kind(const geosrad_ctx *ctx);
 /* max columns processed per internal batch (bounds the HBM workspace); default 131072 */
 int geosrad_set_chunk(geosrad_ctx *ctx, int max_columns);
-/* bytes of HBM workspace currently held */
+/* bytes of HBM workspace currently held (the second set of RRTMG_LW band partials of the RATS / aerosol-free passes included) */
 size_t geosrad_workspace_bytes(const geosrad_ctx *ctx);
 /* Chou-Suarez cloud mode: the reference's -DOVERCAST build of irrad.F90 / sorad.F90 (a layer is clear or fully cloudy; random overlap of
  * the cloudy layers; sorad's cloud optical thickness not scaled; ict / icb not read).  One flag per scheme (GEOS compiles them in separate
@@ -395,6 +395,44 @@ int geosrad_rrtmg_lw_rats_dev(geosrad_ctx *ctx, void *stream, int ncol, int nlay
                               int nrats, const int32_t *rat_gas /*host, GEOSRAD_RAT_**/, void *uflx_rat, void *dflx_rat,
                               void *duflx_dTs_rat);
 
+/* ---- Aerosol-free RRTMG_LW fluxes -------------------------------------------------------------------------------------------
+ * The INTERNALs FLXAU / FLXAD / FLAU / FLAD (total-sky and clear-sky fluxes without aerosols) are filled by the reference's
+ * Chou-Suarez branch (inside irrad) and by its RRTMGP branch (calc_clrnoa); its RRTMG branch leaves their exports MAPL_UNDEF and copies
+ * DFDTSNA = DFDTS (GEOS_IrradGridComp.F90:3552-3556, :3927-3990).  geosrad_rrtmg_lw_na_dev = geosrad_rrtmg_lw_rats_dev (same
+ * arguments, nrats may be 0) + the six flux arrays of the same columns with tauaer taken away, from the SAME call: uflx_na, dflx_na,
+ * uflxc_na, dflxc_na, duflx_dTs_na, duflxc_dTs_na are (ncol,nlay+1); the first four are required, the two derivatives are required iff
+ * dudTs and ignored otherwise.  Nothing the clouds decide depends on the aerosols (the partition, the overlap, the sub-columns with their
+ * optical depths, clearCounts), and neither does setcoef: the aerosol-free fluxes cost one more band sweep and one more reduction.  They
+ * are bitwise those of a separate call with tauaer == NULL.  With tauaer == NULL there is nothing to remove: no second sweep runs and the
+ * six arrays receive the bits of uflx .. duflxc_dTs.
+ * Like a call with RATS diagnostics, such a call takes the band-partials path THROUGHOUT, its main pass included (the passes share the
+ * per-band partials of the reduction): under GEOSRAD_LW_PATH=cols its with-aerosol outputs have the bits of geosrad_rrtmg_lw_rats_dev,
+ * not those of geosrad_rrtmg_lw_dev.  It holds the second set of partials also with nrats == 0 (geosrad_workspace_bytes counts it) and
+ * honours geosrad_set_chunk; results do not depend on the chunk size.
+ * geosrad_rrtmg_lw_na: geosrad_rrtmg_lw (host pointers, chunked pipeline, sharded by a geosrad_create_multi context) + the same six. */
+int geosrad_rrtmg_lw_na_dev(geosrad_ctx *ctx, void *stream, int ncol, int nlay, int psize, int dudTs,
+                            const void *play, const void *plev, const void *tlay, const void *tlev, const void *tsfc, const void *emis,
+                            const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *n2ovmr,
+                            const void *o2vmr, const void *cfc11vmr, const void *cfc12vmr, const void *cfc22vmr, const void *ccl4vmr,
+                            const void *cldf, const void *ciwp, const void *clwp, const void *rei, const void *rel,
+                            int iceflglw, int liqflglw, const void *tauaer, const void *zm, const void *alat, int dyofyr,
+                            int cloudLM, int cloudMH, int32_t *clearCounts,
+                            void *uflx, void *dflx, void *uflxc, void *dflxc, void *duflx_dTs, void *duflxc_dTs,
+                            const int32_t *band_output, void *olrb, void *dolrb_dTs,
+                            int nrats, const int32_t *rat_gas /*host, GEOSRAD_RAT_**/, void *uflx_rat, void *dflx_rat,
+                            void *duflx_dTs_rat,
+                            void *uflx_na, void *dflx_na, void *uflxc_na, void *dflxc_na, void *duflx_dTs_na, void *duflxc_dTs_na);
+int geosrad_rrtmg_lw_na(geosrad_ctx *ctx, int ncol, int nlay, int psize, int dudTs,
+                        const void *play, const void *plev, const void *tlay, const void *tlev, const void *tsfc, const void *emis,
+                        const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *n2ovmr,
+                        const void *o2vmr, const void *cfc11vmr, const void *cfc12vmr, const void *cfc22vmr, const void *ccl4vmr,
+                        const void *cldf, const void *ciwp, const void *clwp, const void *rei, const void *rel,
+                        int iceflglw, int liqflglw, const void *tauaer, const void *zm, const void *alat, int dyofyr,
+                        int cloudLM, int cloudMH, int32_t *clearCounts,
+                        void *uflx, void *dflx, void *uflxc, void *dflxc, void *duflx_dTs, void *duflxc_dTs,
+                        const int32_t *band_output, void *olrb, void *dolrb_dTs,
+                        void *uflx_na, void *dflx_na, void *uflxc_na, void *dflxc_na, void *duflx_dTs_na, void *duflxc_dTs_na);
+
 /* ---- GridComp data path either side of the solvers -------------------------------------
  * All arrays are DEVICE pointers of the context's real kind in the GEOS layout (IM*JM columns fastest, then the level /
  * layer index in MODEL ordering, 1 = top), asynchronous on `stream`.  A NULL output = Fortran "not associated" (export
@@ -424,6 +462,21 @@ int geosrad_lw_driver_rrtmg_rats_dev(geosrad_ctx *ctx, void *stream, int ncol, i
                                      const double *consts, int iceflglw, int liqflglw, int doy, int lcldlm, int lcldmh,
                                      const int32_t *band_output, void *const *out, int nrats, const int32_t *rat_gas,
                                      void *const *rat_out);
+/* the same with the aerosol-free INTERNALs from geosrad_rrtmg_lw_na_dev (nrats may be 0): na_out = FLXAU_INT, FLXAD_INT, FLAU_INT,
+ * FLAD_INT, FLXA_INT, FLA_INT, DFDTSNA, DFDTSCNA (ncol,0:LM) in model ordering, with the conventions of GEOS_IrradGridComp.F90:3506-3515
+ * and :3604-3607: FLXAU = -uflx_na, FLXAD = dflx_na, FLAU = -uflxc_na, FLAD = dflxc_na, FLXA = FLXAD + FLXAU, FLA = FLAD + FLAU,
+ * DFDTSNA = -duflx_dTs_na, DFDTSCNA = -duflxc_dTs_na - the derivatives of the aerosol-free pass itself.  Any may be NULL; with all eight
+ * NULL, or na_out NULL, the call is geosrad_lw_driver_rrtmg_rats_dev and no second sweep runs.  out[GEOSRAD_LWD_DFDTSNA / _DFDTSCNA] keep
+ * the reference's meaning (copies of DFDTS / DFDTSC, :3560-3565): a caller who wants the real ones in its INTERNAL state passes NULL there
+ * and the field here.  (Without TAUA / SSAA the solver is handed an all-zero tauaer, as by the other two drivers, and sweeps it twice for
+ * equal results.)  An RRTMG caller who has filled these INTERNALs calls geosrad_lw_update_flx_dev with rrtmg = 0, which reads them as real
+ * fields, and GEOSRAD_RT_FLA of geosrad_rad_tendencies_dev then yields RADLWCNA. */
+enum { GEOSRAD_LWNA_FLXAU_INT, GEOSRAD_LWNA_FLXAD_INT, GEOSRAD_LWNA_FLAU_INT, GEOSRAD_LWNA_FLAD_INT, GEOSRAD_LWNA_FLXA_INT,
+       GEOSRAD_LWNA_FLA_INT, GEOSRAD_LWNA_DFDTSNA, GEOSRAD_LWNA_DFDTSCNA, GEOSRAD_LWNA_NOUT };
+int geosrad_lw_driver_rrtmg_na_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm, int nb_aer, const void *const *in,
+                                   const double *consts, int iceflglw, int liqflglw, int doy, int lcldlm, int lcldmh,
+                                   const int32_t *band_output, void *const *out, int nrats, const int32_t *rat_gas,
+                                   void *const *rat_out, void *const *na_out);
 
 /* geosrad_lw_chou_post_dev: what the Chou-Suarez branch of LW_Driver adds after `call IRRAD` (which takes the GEOS fields as they are):
  * DFDTSC = 0, DFDTSNA = DFDTS, DFDTSCNA = 0 (GEOS_IrradGridComp.F90:2101-2108), the four net fluxes FL*_INT = FL*D_INT + FL*U_INT,
@@ -508,6 +561,8 @@ int geosrad_sw_driver_chou_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm,
 
 /* geosrad_lw_update_flx_dev: Update_Flx (GEOS_IrradGridComp.F90:3796-3999), the per-model-step linearisation of the LW fluxes in
  * the surface temperature.  rrtmg != 0: the no-aerosol flavours are `undef` and their internals may be NULL (IRR:3927-3990).
+ * rrtmg = 0 reads FLXA_INT .. DFDTSCNA as real fields (the Chou-Suarez semantics): what an RRTMG caller passes who has filled them with
+ * geosrad_lw_driver_rrtmg_na_dev, for FLXA, FLA, OLRA / OLA, LWSA / LAS, FLNSNA / FLNSA.
  * lev_mid_high / lev_low_mid: the model levels found from PREF (IRR:3811-3829). */
 enum { GEOSRAD_LWU_TSINST, GEOSRAD_LWU_TS_INT, GEOSRAD_LWU_SFCEM_INT, GEOSRAD_LWU_FCLD, GEOSRAD_LWU_FLX_INT, GEOSRAD_LWU_FLXA_INT,
        GEOSRAD_LWU_FLC_INT, GEOSRAD_LWU_FLA_INT, GEOSRAD_LWU_FLXU_INT, GEOSRAD_LWU_FLXAU_INT, GEOSRAD_LWU_FLCU_INT,
