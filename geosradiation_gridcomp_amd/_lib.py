@@ -28,6 +28,7 @@ EXPORTS = [
     "geosrad_sw_driver_rrtmg_lit_dev", "geosrad_sw_driver_chou_lit_dev",
     "geosrad_obio_weights", "geosrad_sw_update_obio_dev", "geosrad_sw_driver_rrtmg_obio_dev", "geosrad_sw_driver_rrtmg_obio_lit_dev",
     "geosrad_rrtmg_lw_na", "geosrad_rrtmg_lw_na_dev", "geosrad_lw_driver_rrtmg_na_dev",
+    "geosrad_sorad_na", "geosrad_sorad_na_dev", "geosrad_sw_driver_chou_na_dev", "geosrad_sw_driver_chou_na_lit_dev",
 ]
 
 _lib = None

@@ -392,6 +392,28 @@ class Context:
     def sorad(self, m, np_, nb, cosz, pl, ta, wa, oa, co2, cwc, fcld, ict, icb, reff, hk_uv, hk_ir, taua, ssaa, asya,
               rsuvbm, rsuvdf, rsirbm, rsirdf, do_drfband=False):
         """sorad (sorad.F90:43).  Returns dict(flx, flc, flxu, flcu (np+1, m); fdiruv ... fdifir (m); flx_sfc_band[, drband, dfband] (8, m))."""
+        return self._sorad_host(m, np_, nb, cosz, pl, ta, wa, oa, co2, cwc, fcld, ict, icb, reff, hk_uv, hk_ir, taua, ssaa, asya,
+                                rsuvbm, rsuvdf, rsirbm, rsirdf, do_drfband, None)
+
+    def sorad_na(self, m, np_, nb, cosz, pl, ta, wa, oa, co2, cwc, fcld, ict, icb, reff, hk_uv, hk_ir, taua, ssaa, asya,
+                 rsuvbm, rsuvdf, rsirbm, rsirdf, do_drfband=False, na=None):
+        """sorad + the aerosol-free fluxes of the same columns from the same call (geosrad_sorad_na): the dict additionally holds
+        flx_na, flc_na, flxu_na, flcu_na (np+1, m) and flx_sfc_band_na (8, m).  `na`: the gridcomp.SONA_OUT names to take (default all;
+        the others are passed as NULL and not returned)."""
+        from . import gridcomp as G
+        return self._sorad_host(m, np_, nb, cosz, pl, ta, wa, oa, co2, cwc, fcld, ict, icb, reff, hk_uv, hk_ir, taua, ssaa, asya,
+                                rsuvbm, rsuvdf, rsirbm, rsirdf, do_drfband, G.SONA_OUT if na is None else list(na))
+
+    def sorad_na_columns(self, cs, do_drfband=False, na=None):
+        """Convenience: `cs` as produced by synth.chou_sw_inputs."""
+        n1, m = cs["pl"].shape
+        return self.sorad_na(m, n1 - 1, cs["nb"], cs["cosz"], cs["pl"], cs["ta"], cs["wa"], cs["oa"], cs["co2"], cs["cwc"], cs["fcld"],
+                             cs["ict"], cs["icb"], cs["reff"], cs["hk_uv"], cs["hk_ir"], cs["taua"], cs["ssaa"], cs["asya"], cs["rsuvbm"],
+                             cs["rsuvdf"], cs["rsirbm"], cs["rsirdf"], do_drfband=do_drfband, na=na)
+
+    def _sorad_host(self, m, np_, nb, cosz, pl, ta, wa, oa, co2, cwc, fcld, ict, icb, reff, hk_uv, hk_ir, taua, ssaa, asya,
+                    rsuvbm, rsuvdf, rsirbm, rsirdf, do_drfband, na):
+        """geosrad_sorad (na None) or geosrad_sorad_na with the gridcomp.SONA_OUT names in `na`"""
         dt = self.dtype
         c = lambda a: np.ascontiguousarray(a, dtype=dt)
         cosz, pl, ta, wa, oa, cwc, fcld, reff, hk_uv, hk_ir, taua, ssaa, asya, rsuvbm, rsuvdf, rsirbm, rsirdf = map(
@@ -404,12 +426,20 @@ class Context:
         if do_drfband:
             out["drband"] = np.zeros((8, m), dtype=dt); out["dfband"] = np.zeros((8, m), dtype=dt)
         ci = ctypes.c_int
-        rc = self.L.geosrad_sorad(
+        args = [
             self.h, ci(m), ci(np_), ci(nb), _p(cosz), _p(pl), _p(ta), _p(wa), _p(oa), ctypes.c_double(co2), _p(cwc), _p(fcld), ci(int(ict)),
             ci(int(icb)), _p(reff), _p(hk_uv), _p(hk_ir), _p(taua), _p(ssaa), _p(asya), _p(rsuvbm), _p(rsuvdf), _p(rsirbm), _p(rsirdf),
             _p(out["flx"]), _p(out["flc"]), _p(out["fdiruv"]), _p(out["fdifuv"]), _p(out["fdirpar"]), _p(out["fdifpar"]), _p(out["fdirir"]),
             _p(out["fdifir"]), _p(out["flxu"]), _p(out["flcu"]), _p(out["flx_sfc_band"]), ci(1 if do_drfband else 0), _p(out.get("drband")),
-            _p(out.get("dfband")))
+            _p(out.get("dfband"))]
+        if na is None:
+            rc = self.L.geosrad_sorad(*args)
+        else:
+            from . import gridcomp as G
+            for k in na:
+                out[k] = np.zeros((8, m) if k == "flx_sfc_band_na" else (np_ + 1, m), dtype=dt)
+            tab = (ctypes.c_void_p * len(G.SONA_OUT))(*[out[k].ctypes.data if k in na else None for k in G.SONA_OUT])
+            rc = self.L.geosrad_sorad_na(*args, tab)
         self._chk(rc)
         return out
 
@@ -431,6 +461,22 @@ class Context:
             v("cwc"), v("fcld"), ci(int(ict)), ci(int(icb)), v("reff"), _p(hu), _p(hi), v("taua"), v("ssaa"), v("asya"), v("rsuvbm"),
             v("rsuvdf"), v("rsirbm"), v("rsirdf"), v("flx"), v("flc"), v("fdiruv"), v("fdifuv"), v("fdirpar"), v("fdifpar"), v("fdirir"),
             v("fdifir"), v("flxu"), v("flcu"), v("flx_sfc_band"), ci(1 if do_drfband else 0), v("drband"), v("dfband"))
+        self._chk(rc)
+
+    def sorad_na_dev(self, stream, m, np_, nb, ptr, co2, ict, icb, hk_uv, hk_ir, do_drfband=False, na_ptr=None):
+        """sorad_dev + the aerosol-free fluxes of the same call (geosrad_sorad_na_dev): `na_ptr` = name -> device address for
+        gridcomp.SONA_OUT ((np+1, m), flx_sfc_band_na (8, m); missing = NULL, left untouched; None = na_out NULL, the plain call)."""
+        from . import gridcomp as G
+        dt = self.dtype
+        v = lambda k: ctypes.c_void_p(ptr[k]) if ptr.get(k) else None
+        hu = np.ascontiguousarray(hk_uv, dtype=dt); hi = np.ascontiguousarray(hk_ir, dtype=dt)
+        ci = ctypes.c_int
+        rc = self.L.geosrad_sorad_na_dev(
+            self.h, ctypes.c_void_p(stream), ci(m), ci(np_), ci(nb), v("cosz"), v("pl"), v("ta"), v("wa"), v("oa"), ctypes.c_double(co2),
+            v("cwc"), v("fcld"), ci(int(ict)), ci(int(icb)), v("reff"), _p(hu), _p(hi), v("taua"), v("ssaa"), v("asya"), v("rsuvbm"),
+            v("rsuvdf"), v("rsirbm"), v("rsirdf"), v("flx"), v("flc"), v("fdiruv"), v("fdifuv"), v("fdirpar"), v("fdifpar"), v("fdirir"),
+            v("fdifir"), v("flxu"), v("flcu"), v("flx_sfc_band"), ci(1 if do_drfband else 0), v("drband"), v("dfband"),
+            None if na_ptr is None else self._ptr_array(G.SONA_OUT, na_ptr))
         self._chk(rc)
 
     # ---- RRTMG_LW, device pointers (bench / drivers that keep data in HBM) -------------------------------------
@@ -604,6 +650,35 @@ class Context:
         self._chk(self.L.geosrad_sw_driver_chou_dev(self.h, ctypes.c_void_p(stream), ci(ncol), ci(lm), self._ptr_array(G.SWC_IN, ptr), cs,
                                                     ci(int(lcldmh)), ci(int(lcldlm)), _p(hu), _p(hi), ci(1 if do_drfband else 0),
                                                     self._ptr_array(G.SWC_OUT, ptr)))
+
+    def sw_driver_chou_na_dev(self, stream, ncol, lm, ptr, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband=False, na_ptr=None):
+        """sw_driver_chou_dev + the aerosol-free internals FSWNA, FSCNA, FSWUNA, FSCUNA, FSWBANDNA from the same prep and the same solver
+        call (geosrad_sw_driver_chou_na_dev; the reference runs SORADCORE a second time, GEOS_SolarGridComp.F90:3249-3259): `na_ptr` =
+        name -> device address for gridcomp.SWCNA_OUT (missing = not associated; None = none of them)."""
+        from . import gridcomp as G
+        ci = ctypes.c_int
+        cs = (ctypes.c_double * len(G.SWC_CONST))(*consts)
+        hu = np.ascontiguousarray(hk_uv, dtype=self.dtype)
+        hi = np.ascontiguousarray(hk_ir, dtype=self.dtype)
+        self._chk(self.L.geosrad_sw_driver_chou_na_dev(self.h, ctypes.c_void_p(stream), ci(ncol), ci(lm), self._ptr_array(G.SWC_IN, ptr), cs,
+                                                       ci(int(lcldmh)), ci(int(lcldlm)), _p(hu), _p(hi), ci(1 if do_drfband else 0),
+                                                       self._ptr_array(G.SWC_OUT, ptr),
+                                                       None if na_ptr is None else self._ptr_array(G.SWCNA_OUT, na_ptr)))
+
+    def sw_driver_chou_na_lit_dev(self, stream, ncol, nlit, lit_index, lit_pos, lm, ptr, consts, lcldmh, lcldlm, hk_uv, hk_ir,
+                                  do_drfband=False, dark=None, keep=(), na_ptr=None, dark_na=None, keep_na=()):
+        """sw_driver_chou_na_dev on the un-packed tile: see sw_driver_chou_lit_dev; dark_na / keep_na by gridcomp.SWCNA_OUT name."""
+        from . import gridcomp as G
+        ci = ctypes.c_int
+        cs = (ctypes.c_double * len(G.SWC_CONST))(*consts)
+        hu = None if hk_uv is None else np.ascontiguousarray(hk_uv, dtype=self.dtype)
+        hi = None if hk_ir is None else np.ascontiguousarray(hk_ir, dtype=self.dtype)
+        li, lp, dk, mask = self._lit_args(G.SWC_OUT, lit_index, lit_pos, dark, keep)
+        _, _, dkn, maskn = self._lit_args(G.SWCNA_OUT, lit_index, lit_pos, dark_na, keep_na)
+        self._chk(self.L.geosrad_sw_driver_chou_na_lit_dev(
+            self.h, ctypes.c_void_p(stream), ci(ncol), ci(nlit), li, lp, ci(lm), self._ptr_array(G.SWC_IN, ptr), cs, ci(int(lcldmh)),
+            ci(int(lcldlm)), _p(hu), _p(hi), ci(1 if do_drfband else 0), dk, mask, self._ptr_array(G.SWC_OUT, ptr), dkn, ci(maskn.value),
+            None if na_ptr is None else self._ptr_array(G.SWCNA_OUT, na_ptr)))
 
     @staticmethod
     def _lit_args(names, lit_index, lit_pos, dark, keep):

@@ -580,9 +580,11 @@ struct geosrad_ctx {
     virtual int set_tables_sw(const void *blob, size_t n) = 0;
     virtual int set_tables_chou_lw(const void *blob, size_t n) = 0;
     virtual int set_tables_chou_sw(const void *blob, size_t n) = 0;
-    virtual int sorad_dev(hipStream_t, int, int, int, In, double, int, int, const void *, const void *, Out, int) { return nodev("geosrad_sorad_dev"); }
+    // na_out: the aerosol-free fluxes of the same call (GEOSRAD_SONA_*), null from the entry points without them
+    virtual int sorad_dev(hipStream_t, int, int, int, In, double, int, int, const void *, const void *, Out, int, Out /*na_out*/)
+    { return nodev("geosrad_sorad_dev"); }
     virtual int sorad_host(int m, int np, int nb, const void *const *in, double co2, int ict, int icb, const void *hk_uv, const void *hk_ir,
-                           void *const *out, int do_drfband) = 0;
+                           void *const *out, int do_drfband, void *const *na_out) = 0;
     virtual int irrad_dev(hipStream_t, int, int, In, double, int, int, int, int, int, int, Out, Out) { return nodev("geosrad_irrad_dev"); }
     virtual int irrad_host(int m, int np, const void *const *in, double co2, int trace, int ict, int icb, int ns, int na, int nb,
                            void *const *aer, void *const *out) = 0;
@@ -624,6 +626,13 @@ enum SoIn { SI_COSZ, SI_PL, SI_TA, SI_WA, SI_OA, SI_CWC, SI_FCLD, SI_REFF, SI_TA
             SI_RSIRDF, SI_NIN };
 enum SoOutIx { SOO_FLX, SOO_FLC, SOO_FDIRUV, SOO_FDIFUV, SOO_FDIRPAR, SOO_FDIFPAR, SOO_FDIRIR, SOO_FDIFIR, SOO_FLXU, SOO_FLCU,
                SOO_SFCBAND, SOO_DRBAND, SOO_DFBAND, SOO_NOUT };
+// the `out` row of which na_out[k] (GEOSRAD_SONA_*) is the aerosol-free twin
+constexpr int SONA_TWIN[GEOSRAD_SONA_NOUT] = {SOO_FLX, SOO_FLC, SOO_FLXU, SOO_FLCU, SOO_SFCBAND};
+static inline bool sona_any(void *const *na_out)
+{
+    for (int k = 0; na_out && k < GEOSRAD_SONA_NOUT; k++) if (na_out[k]) return true;
+    return false;
+}
 
 // irrad: order of the `in` (19) / `aer` (3, in-out) / `out` (11) pointer arrays
 enum ChIn { C_PLE, C_TA, C_WA, C_OA, C_TB, C_N2O, C_CH4, C_CFC11, C_CFC12, C_CFC22, C_CWC, C_FCLD, C_REFF, C_FS, C_TG, C_EG, C_TV, C_EV,
@@ -1550,7 +1559,9 @@ template <typename R> struct Ctx : geosrad_ctx {
 
     // Chou-Suarez branch of SORADCORE: k_swc_prep + sorad_dev.  The prepared arrays live in a buffer of their own (sorad_dev's scratch is
     // sized per chunk, these per call).  On a tile (lit) that buffer also holds, NumLit wide, the imports sorad reads as they are and all its
-    // results, which one k_lit_scatter takes to the tile.
+    // results, which one k_lit_scatter takes to the tile.  With C.na_out the same prep and the same solver call also give the aerosol-free
+    // internals (sorad_dev's na_out); their planes are further rows of the same scatter.  Without aerosol inputs the one pass is the
+    // aerosol-free one: na_out are copies of their twins.
     int sw_driver_chou_dev(hipStream_t st, const SwcCall &C) override
     {
         HIPCHK(hipSetDevice(device));
@@ -1566,16 +1577,31 @@ template <typename R> struct Ctx : geosrad_ctx {
         for (int k = 0; k < GEOSRAD_SWC_NIN; k++)
             if (!in[k] && !(k >= GEOSRAD_SWC_TAUA && k <= GEOSRAD_SWC_ASYA)) return fail(GEOSRAD_EINVAL, "null input field");
         if (lit) if (const char *msg = lit_check(*lit, ncol, out, nres)) return fail(GEOSRAD_EINVAL, msg);
+        void *nao[GEOSRAD_SWCNA_NOUT] = {};      // the aerosol-free outputs requested
+        bool na = false;
+        for (int k = 0; C.na_out && k < GEOSRAD_SWCNA_NOUT; k++) { nao[k] = C.na_out[k]; na = na || nao[k]; }
+        // the tile with the aerosol-free outputs as further rows: outputs, dark values and keep bits of out, then those of na_out
+        void *tout[SWC_NTILE] = {};
+        double tdark[SWC_NTILE] = {};
+        LitTile xl{};
+        if (lit) {
+            const LitTile nl{lit->tile, lit->idx, lit->pos, C.dark_na, (uint64_t)(unsigned)C.keep_na};
+            if (const char *msg = lit_check(nl, ncol, nao, GEOSRAD_SWCNA_NOUT)) return fail(GEOSRAD_EINVAL, msg);
+            for (int k = 0; k < nres; k++) { tout[k] = out[k]; if (lit->dark) tdark[k] = lit->dark[k]; }
+            for (int k = 0; k < GEOSRAD_SWCNA_NOUT; k++) { tout[GEOSRAD_SWC_NOUT + k] = nao[k]; if (C.dark_na) tdark[GEOSRAD_SWC_NOUT + k] = C.dark_na[k]; }
+            const uint64_t low = ((uint64_t)1 << GEOSRAD_SWC_NOUT) - 1;
+            xl = LitTile{lit->tile, lit->idx, lit->pos, tdark, (lit->keep & low) | ((uint64_t)(unsigned)C.keep_na << GEOSRAD_SWC_NOUT)};
+        }
         if (lit) {      // what sorad_dev would reject, before anything is launched
             if (const int rc = sorad_check_options(1, lm, 8, C.lcldmh, C.lcldlm, C.hk_uv, C.hk_ir)) return rc;
             for (int k = 0; k < nres; k++) if (!out[k]) return fail(GEOSRAD_EINVAL, "null output array");
-            if (ncol == 0) return lit_scatter(st, lit_scatter_pack<R>(swc_tile, nres, lm, *lit, 0, out, nullptr));
+            if (ncol == 0) return lit_scatter(st, lit_scatter_pack<R>(swc_tile, SWC_NTILE, lm, xl, 0, tout, nullptr));
         }
         const size_t n = (size_t)ncol, cl = (size_t)lm * ncol;
         SwcLit<R> PL{};
         SwcPrep<R> &P = PL;
         R *zero = nullptr;          // TAUA = SSAA = ASYA = 0 (SOL:4543-4546): one block serves the three
-        R *res[GEOSRAD_SWC_NOUT] = {};
+        R *res[SWC_NTILE] = {};
         auto carve = [&](Carve c) {
             P.plhpa = c.take<R>(cl + ncol); P.o3 = c.take<R>(cl); P.qq3 = c.take<R>(4 * cl); P.rr3 = c.take<R>(4 * cl);
             if (!aer) zero = c.take<R>(8 * cl);
@@ -1584,6 +1610,8 @@ template <typename R> struct Ctx : geosrad_ctx {
                 if (aer) for (auto &q : PL.aer_out) q = c.take<R>(8 * cl);
                 for (auto &q : PL.col_out) q = c.take<R>(n);
                 for (int k = 0; k < nres; k++) res[k] = c.take<R>(n * swc_tile[k].nrows(lm));
+                for (int k = 0; k < GEOSRAD_SWCNA_NOUT; k++)      // without aerosols: the twin's plane
+                    if (nao[k]) res[GEOSRAD_SWC_NOUT + k] = aer ? c.take<R>(n * swc_tile[GEOSRAD_SWC_NOUT + k].nrows(lm)) : res[SWCNA_TWIN[k]];
             }
             return c.off;
         };
@@ -1613,9 +1641,17 @@ template <typename R> struct Ctx : geosrad_ctx {
         so[SOO_FDIRIR] = O(GEOSRAD_SWC_NIRR); so[SOO_FDIFIR] = O(GEOSRAD_SWC_NIRF); so[SOO_FDIRPAR] = O(GEOSRAD_SWC_PARR);
         so[SOO_FDIFPAR] = O(GEOSRAD_SWC_PARF); so[SOO_FDIRUV] = O(GEOSRAD_SWC_UVRR); so[SOO_FDIFUV] = O(GEOSRAD_SWC_UVRF);
         so[SOO_SFCBAND] = O(GEOSRAD_SWC_FSWBAND); so[SOO_DRBAND] = O(GEOSRAD_SWC_DRBAND); so[SOO_DFBAND] = O(GEOSRAD_SWC_DFBAND);
-        if (const int rc = sorad_dev(st, ncol, lm, 8, si, C.consts[GEOSRAD_SWC_C_CO2], C.lcldmh, C.lcldlm, C.hk_uv, C.hk_ir, so, C.do_drfband)) return rc;
-        if (!lit) return GEOSRAD_OK;
-        return lit_scatter(st, lit_scatter_pack<R>(swc_tile, nres, lm, *lit, ncol, out, res));
+        // GEOSRAD_SWCNA_* is GEOSRAD_SONA_*'s order: the second pass only with aerosols to take away
+        void *sna[GEOSRAD_SONA_NOUT] = {};
+        static_assert(GEOSRAD_SONA_NOUT == GEOSRAD_SWCNA_NOUT && (int)GEOSRAD_SONA_SFCBAND == (int)GEOSRAD_SWCNA_FSWBANDNA, "the driver's na_out is the solver's");
+        for (int k = 0; na && aer && k < GEOSRAD_SWCNA_NOUT; k++) sna[k] = lit ? (void *)res[GEOSRAD_SWC_NOUT + k] : nao[k];
+        if (const int rc = sorad_dev(st, ncol, lm, 8, si, C.consts[GEOSRAD_SWC_C_CO2], C.lcldmh, C.lcldlm, C.hk_uv, C.hk_ir, so, C.do_drfband, sna)) return rc;
+        if (!lit) {
+            for (int k = 0; na && !aer && k < GEOSRAD_SWCNA_NOUT; k++)
+                if (nao[k]) HIPCHK(hipMemcpyAsync(nao[k], out[SWCNA_TWIN[k]], n * swc_tile[SWCNA_TWIN[k]].nrows(lm) * sizeof(R), hipMemcpyDeviceToDevice, st));
+            return GEOSRAD_OK;
+        }
+        return lit_scatter(st, lit_scatter_pack<R>(swc_tile, SWC_NTILE, lm, xl, ncol, tout, res));
     }
 
     int lw_update_flx_dev(hipStream_t st, int ncol, int lm, int rrtmg, int lev_mid_high, int lev_low_mid, double undef,
@@ -2541,8 +2577,13 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (!hk_uv || !hk_ir) return fail(GEOSRAD_EINVAL, "hk_uv / hk_ir null");
         return GEOSRAD_OK;
     }
+    // One body for geosrad_sorad_dev (na_out null, or all its members: no second pass) and geosrad_sorad_na_dev.  Per chunk: the
+    // preparation once; `sweep` - the spectral passes over the selectable paths, their sum and the reduction - with the aerosols into `out`
+    // and then, aerosol-free (NA flavour of the same kernels), into na_out.  The second sweep reuses scr, psum and the dynamic LDS: one stream
+    // runs the two in order, and the first reduction has read psum before the second pass rewrites it.  k_sorad_sum / k_sorad_reduce need
+    // all of flx, flc, flxu, flcu: a member of na_out the caller does not take has its place in the workspace.
     int sorad_dev(hipStream_t st, int m, int np, int nb, const void *const *in, double co2, int ict, int icb, const void *hk_uv,
-                  const void *hk_ir, void *const *out, int do_drfband) override
+                  const void *hk_ir, void *const *out, int do_drfband, void *const *na_out) override
     {
         HIPCHK(hipSetDevice(device));
         if (const int rc = sorad_check_options(m, np, nb, ict, icb, hk_uv, hk_ir)) return rc;
@@ -2558,6 +2599,8 @@ template <typename R> struct Ctx : geosrad_ctx {
         // (a layer count whose on-chip arrays exceed the LDS takes the scratch-plane path; so does OVERCAST: k_sorad_col has no OVERCAST
         // variant, the OVERCAST passes are k_sorad_pass_oc whatever GEOSRAD_SORAD_PATH says)
         const bool col_path = !oc && sorad_col_path && K2 <= 256 && sorad_col_lds_reals<R>(np) * sizeof(R) <= (size_t)160 * 1024;
+        const bool na = sona_any(na_out);
+        void *na_arr[GEOSRAD_SONA_NOUT] = {};      // na_out, or the workspace's place for a member not taken (whole call wide, like the caller's)
         SoradArgs<R> W{};      // the workspace planes, the same for every chunk; the gathered aerosol planes and the scratch planes only on the paths that use them
         auto carve = [&](Carve c) {
             W.lay = c.take<R>(4 * K2 * per); W.swh = c.take<R>(K2 * per); W.colv = c.take<R>(8 * per); W.cld = c.take<R>((size_t)SO_NGRP * 4 * K2 * per);
@@ -2565,6 +2608,8 @@ template <typename R> struct Ctx : geosrad_ctx {
             W.aer = col_path || oc ? nullptr : c.take<R>((size_t)3 * SO_NGATHER * np * per);
             W.perm = c.take<int32_t>(per); W.cls = c.take<uint8_t>(per); W.cls_off = c.take<int32_t>(16);
             W.scr = col_path ? nullptr : c.take<R>((size_t)SO_NPASS * SO_NPLANE * K2 * per);
+            for (int k = 0; na && k < GEOSRAD_SONA_NOUT; k++)
+                na_arr[k] = na_out[k] ? na_out[k] : (void *)c.take<R>(so_out_shape(SONA_TWIN[k], np).rows * (size_t)m);
             return c.off;
         };
         const size_t need = carve(Carve());
@@ -2572,6 +2617,7 @@ template <typename R> struct Ctx : geosrad_ctx {
         if (col_path) {
             if (so_lds > so_lds_set) {
                 HIPCHK(hipFuncSetAttribute((const void *)k_sorad_col<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)so_lds));
+                HIPCHK(hipFuncSetAttribute((const void *)k_sorad_col<R, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)so_lds));
                 so_lds_set = so_lds;
             }
         }
@@ -2609,38 +2655,50 @@ template <typename R> struct Ctx : geosrad_ctx {
             O.flx = Q(SOO_FLX); O.flc = Q(SOO_FLC); O.fdiruv = Q(SOO_FDIRUV); O.fdifuv = Q(SOO_FDIFUV); O.fdirpar = Q(SOO_FDIRPAR);
             O.fdifpar = Q(SOO_FDIFPAR); O.fdirir = Q(SOO_FDIRIR); O.fdifir = Q(SOO_FDIFIR); O.flxu = Q(SOO_FLXU); O.flcu = Q(SOO_FLCU);
             O.flx_sfc_band = Q(SOO_SFCBAND); O.drband = Q(SOO_DRBAND); O.dfband = Q(SOO_DFBAND);
-            span_begin(13, st);
-            if (oc) {
-                hipLaunchKernelGGL(k_sorad_pass_oc<R>, dim3(band_grid(nc, SO_NPASS)), blk, 0, st, A, (const SoradDev<R> *)d_O);
-            } else if (col_path) {   // one block per column, lanes = (pass slot, level) (whole wavefronts), all 35 passes on chip
-                const unsigned nthr = (unsigned)sorad_col_threads(np);
-                const unsigned grid = 8u * (unsigned)((nc + 7) / 8);
-                hipLaunchKernelGGL(k_sorad_col<R>, dim3(grid), dim3(nthr), so_lds, st, A, (const SoradDev<R> *)d_O, O);
-            } else {
-                // one instantiation per class, the classes with the most sky situations first; a block without a position of the class
-                // returns at once
-                // one-dimensional XCD-aware grid (band_block): the 35 passes of a position block run together on one XCD and share its layer
-                // inputs from that L2 (8.7 -> 8.1 ms per 100 000 columns against a (block, pass) grid)
-                const dim3 g(band_grid(nc, SO_NPASS));
+            // the spectral passes (slot 13), their sum over the passes and the reduction, into O; NA: the aerosol-free flavour
+            auto sweep = [&](auto na_c, const SoradOut<R> &O) {
+                constexpr bool NA = decltype(na_c)::value;
                 const SoradDev<R> *dO = (const SoradDev<R> *)d_O;
-                hipLaunchKernelGGL((k_sorad_pass<R, 7>), g, blk, 0, st, A, dO);
-                hipLaunchKernelGGL((k_sorad_pass<R, 6>), g, blk, 0, st, A, dO);
-                hipLaunchKernelGGL((k_sorad_pass<R, 5>), g, blk, 0, st, A, dO);
-                hipLaunchKernelGGL((k_sorad_pass<R, 3>), g, blk, 0, st, A, dO);
-                hipLaunchKernelGGL((k_sorad_pass<R, 4>), g, blk, 0, st, A, dO);
-                hipLaunchKernelGGL((k_sorad_pass<R, 2>), g, blk, 0, st, A, dO);
-                hipLaunchKernelGGL((k_sorad_pass<R, 1>), g, blk, 0, st, A, dO);
-                hipLaunchKernelGGL((k_sorad_pass<R, 0>), g, blk, 0, st, A, dO);
+                span_begin(13, st);
+                if (oc) {
+                    hipLaunchKernelGGL((k_sorad_pass_oc<R, NA>), dim3(band_grid(nc, SO_NPASS)), blk, 0, st, A, dO);
+                } else if (col_path) {   // one block per column, lanes = (pass slot, level) (whole wavefronts), all 35 passes on chip
+                    const unsigned nthr = (unsigned)sorad_col_threads(np);
+                    const unsigned grid = 8u * (unsigned)((nc + 7) / 8);
+                    hipLaunchKernelGGL((k_sorad_col<R, NA>), dim3(grid), dim3(nthr), so_lds, st, A, dO, O);
+                } else {
+                    // one instantiation per class, the classes with the most sky situations first; a block without a position of the class
+                    // returns at once
+                    // one-dimensional XCD-aware grid (band_block): the 35 passes of a position block run together on one XCD and share its layer
+                    // inputs from that L2 (8.7 -> 8.1 ms per 100 000 columns against a (block, pass) grid)
+                    const dim3 g(band_grid(nc, SO_NPASS));
+                    hipLaunchKernelGGL((k_sorad_pass<R, 7, NA>), g, blk, 0, st, A, dO);
+                    hipLaunchKernelGGL((k_sorad_pass<R, 6, NA>), g, blk, 0, st, A, dO);
+                    hipLaunchKernelGGL((k_sorad_pass<R, 5, NA>), g, blk, 0, st, A, dO);
+                    hipLaunchKernelGGL((k_sorad_pass<R, 3, NA>), g, blk, 0, st, A, dO);
+                    hipLaunchKernelGGL((k_sorad_pass<R, 4, NA>), g, blk, 0, st, A, dO);
+                    hipLaunchKernelGGL((k_sorad_pass<R, 2, NA>), g, blk, 0, st, A, dO);
+                    hipLaunchKernelGGL((k_sorad_pass<R, 1, NA>), g, blk, 0, st, A, dO);
+                    hipLaunchKernelGGL((k_sorad_pass<R, 0, NA>), g, blk, 0, st, A, dO);
+                }
+                span_end(st);               // the slot times k_sorad_pass alone (= its average duration in a rocprofv3 kernel trace)
+                if (!col_path) hipLaunchKernelGGL(k_sorad_sum<R>, dim3(gx, np + 1), blk, 0, st, A, O);
+                hipLaunchKernelGGL((k_sorad_reduce<R, NA>), dim3(gx), blk, 0, st, A, dO, O);
+            };
+            sweep(std::false_type{}, O);
+            if (na) {
+                SoradOut<R> N{};      // the members the aerosol-free reduction never writes stay null
+                auto QN = [&](int k) { return colp(na_arr[k], c0); };
+                N.flx = QN(GEOSRAD_SONA_FLX); N.flc = QN(GEOSRAD_SONA_FLC); N.flxu = QN(GEOSRAD_SONA_FLXU); N.flcu = QN(GEOSRAD_SONA_FLCU);
+                N.flx_sfc_band = QN(GEOSRAD_SONA_SFCBAND);
+                sweep(std::true_type{}, N);
             }
-            span_end(st);               // the slot times k_sorad_pass alone (= its average duration in a rocprofv3 kernel trace)
-            if (!col_path) hipLaunchKernelGGL(k_sorad_sum<R>, dim3(gx, np + 1), blk, 0, st, A, O);
-            hipLaunchKernelGGL(k_sorad_reduce<R>, dim3(gx), blk, 0, st, A, (const SoradDev<R> *)d_O, O);
             return GEOSRAD_OK;
         });
     }
 
     int sorad_host(int m, int np, int nb, const void *const *in, double co2, int ict, int icb, const void *hk_uv, const void *hk_ir,
-                   void *const *out, int do_drfband) override
+                   void *const *out, int do_drfband, void *const *na_out) override
     {
         // host arrays through the chunk pipeline
         HIPCHK(hipSetDevice(device));
@@ -2653,7 +2711,10 @@ template <typename R> struct Ctx : geosrad_ctx {
         // an output the caller does not take (or drband / dfband without do_drfband) still has its place on the device
         for (int k = 0; k < SOO_NOUT; k++)
             H.add(nullptr, ((k == SOO_DRBAND || k == SOO_DFBAND) && !do_drfband) ? nullptr : out[k], so_out_shape(k, np), &dout[k]);
-        const int rc = host_call(m, H, -1, [&](hipStream_t st, int nc) { return sorad_dev(st, nc, np, nb, din, co2, ict, icb, hk_uv, hk_ir, dout, do_drfband); });
+        // the aerosol-free arrays the caller takes: further per-column records (the others keep their place in sorad_dev's workspace)
+        void *dna[GEOSRAD_SONA_NOUT] = {};
+        for (int k = 0; na_out && k < GEOSRAD_SONA_NOUT; k++) if (na_out[k]) H.add(nullptr, na_out[k], so_out_shape(SONA_TWIN[k], np), &dna[k]);
+        const int rc = host_call(m, H, -1, [&](hipStream_t st, int nc) { return sorad_dev(st, nc, np, nb, din, co2, ict, icb, hk_uv, hk_ir, dout, do_drfband, dna); });
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(stream));      // the Chou schemes have no input assertions (neither has the reference)
         return GEOSRAD_OK;
@@ -2855,13 +2916,14 @@ struct MultiCtx final : geosrad_ctx {
         });
     }
     int sorad_host(int m, int np, int nb, const void *const *in, double co2, int ict, int icb, const void *hk_uv, const void *hk_ir,
-                   void *const *out, int do_drfband) override
+                   void *const *out, int do_drfband, void *const *na_out) override
     {
         return run_shards(m, [&](geosrad_ctx *k, int c0, int nc) {
-            const void *i2[SI_NIN]; void *o2[SOO_NOUT];
+            const void *i2[SI_NIN]; void *o2[SOO_NOUT], *n2[GEOSRAD_SONA_NOUT];
             for (int j = 0; j < SI_NIN; j++) i2[j] = off(in[j], c0, so_in_shape(j, np, nb));
             for (int j = 0; j < SOO_NOUT; j++) o2[j] = off(out[j], c0, so_out_shape(j, np));
-            return k->sorad_host(nc, np, nb, i2, co2, ict, icb, hk_uv, hk_ir, o2, do_drfband);
+            for (int j = 0; j < GEOSRAD_SONA_NOUT; j++) n2[j] = na_out ? off(na_out[j], c0, so_out_shape(SONA_TWIN[j], np)) : nullptr;
+            return k->sorad_host(nc, np, nb, i2, co2, ict, icb, hk_uv, hk_ir, o2, do_drfband, n2);
         });
     }
     int mcica_host(int, int, int, const void *, const void *, int, const void *, const void *, const void *, const void *, double,
@@ -3203,7 +3265,19 @@ int geosrad_sorad(geosrad_ctx *c, int m, int np, int nb, const void *cosz, const
 {
     if (!c) return GEOSRAD_EINVAL;
     SO_PACK();
-    return c->sorad_host(m, np, nb, in, co2, ict, icb, hk_uv, hk_ir, out, do_drfband);
+    return c->sorad_host(m, np, nb, in, co2, ict, icb, hk_uv, hk_ir, out, do_drfband, nullptr);
+}
+
+int geosrad_sorad_na(geosrad_ctx *c, int m, int np, int nb, const void *cosz, const void *pl, const void *ta, const void *wa, const void *oa,
+                     double co2, const void *cwc, const void *fcld, int ict, int icb, const void *reff, const void *hk_uv, const void *hk_ir,
+                     const void *taua, const void *ssaa, const void *asya, const void *rsuvbm, const void *rsuvdf, const void *rsirbm,
+                     const void *rsirdf, void *flx, void *flc, void *fdiruv, void *fdifuv, void *fdirpar, void *fdifpar, void *fdirir,
+                     void *fdifir, void *flxu, void *flcu, void *flx_sfc_band, int do_drfband, void *drband, void *dfband,
+                     void *const *na_out)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    SO_PACK();
+    return c->sorad_host(m, np, nb, in, co2, ict, icb, hk_uv, hk_ir, out, do_drfband, na_out);
 }
 
 int geosrad_sorad_dev(geosrad_ctx *c, void *stream, int m, int np, int nb, const void *cosz, const void *pl, const void *ta, const void *wa,
@@ -3215,7 +3289,19 @@ int geosrad_sorad_dev(geosrad_ctx *c, void *stream, int m, int np, int nb, const
 {
     if (!c) return GEOSRAD_EINVAL;
     SO_PACK();
-    return c->sorad_dev((hipStream_t)stream, m, np, nb, in, co2, ict, icb, hk_uv, hk_ir, out, do_drfband);
+    return c->sorad_dev((hipStream_t)stream, m, np, nb, in, co2, ict, icb, hk_uv, hk_ir, out, do_drfband, nullptr);
+}
+
+int geosrad_sorad_na_dev(geosrad_ctx *c, void *stream, int m, int np, int nb, const void *cosz, const void *pl, const void *ta, const void *wa,
+                         const void *oa, double co2, const void *cwc, const void *fcld, int ict, int icb, const void *reff, const void *hk_uv,
+                         const void *hk_ir, const void *taua, const void *ssaa, const void *asya, const void *rsuvbm, const void *rsuvdf,
+                         const void *rsirbm, const void *rsirdf, void *flx, void *flc, void *fdiruv, void *fdifuv, void *fdirpar,
+                         void *fdifpar, void *fdirir, void *fdifir, void *flxu, void *flcu, void *flx_sfc_band, int do_drfband,
+                         void *drband, void *dfband, void *const *na_out)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    SO_PACK();
+    return c->sorad_dev((hipStream_t)stream, m, np, nb, in, co2, ict, icb, hk_uv, hk_ir, out, do_drfband, na_out);
 }
 
 #define LW_PACK_IN()                                                                                                     \
@@ -3400,6 +3486,21 @@ int geosrad_sw_driver_chou_lit_dev(geosrad_ctx *c, void *stream, int ncol, int n
 {
     const LitTile lit{ncol, lit_index, lit_pos, dark, keep_mask};
     return swc_call(c, stream, {nlit, lm, in, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, out, &lit});
+}
+
+int geosrad_sw_driver_chou_na_dev(geosrad_ctx *c, void *stream, int ncol, int lm, const void *const *in, const double *consts, int lcldmh,
+                                  int lcldlm, const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out, void *const *na_out)
+{
+    return swc_call(c, stream, {ncol, lm, in, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, out, nullptr, na_out});
+}
+
+int geosrad_sw_driver_chou_na_lit_dev(geosrad_ctx *c, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos, int lm,
+                                      const void *const *in, const double *consts, int lcldmh, int lcldlm, const void *hk_uv,
+                                      const void *hk_ir, int do_drfband, const double *dark, uint64_t keep_mask, void *const *out,
+                                      const double *dark_na, int keep_na, void *const *na_out)
+{
+    const LitTile lit{ncol, lit_index, lit_pos, dark, keep_mask};
+    return swc_call(c, stream, {nlit, lm, in, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, out, &lit, na_out, dark_na, keep_na});
 }
 
 int geosrad_lw_driver_chou_dev(geosrad_ctx *c, void *stream, int ncol, int lm, const void *const *in, const double *consts, int trace,

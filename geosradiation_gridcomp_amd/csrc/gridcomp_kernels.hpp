@@ -437,13 +437,21 @@ template <typename R> struct Fields<SwcLit<R>> { using S = SwcLit<R>;
              elem<&S::aer_in, 2>, elem<&S::col_in, 0>, elem<&S::col_in, 1>, elem<&S::col_in, 2>, elem<&S::col_in, 3>, elem<&S::col_in, 4>);
 };
 // geosrad_sw_driver_chou*_dev, as geosrad.h has it; with `lit`, in / out are the un-packed tile's and ncol is NumLit
+// na_out (GEOSRAD_SWCNA_*): the aerosol-free internals of geosrad_sw_driver_chou_na[_lit]_dev, with their dark values and keep bits on a
+// tile; empty from the entry points without them
 struct SwcCall {
     int ncol, lm; const void *const *in; const double *consts; int lcldmh, lcldlm; const void *hk_uv, *hk_ir; int do_drfband; void *const *out; const LitTile *lit;
+    void *const *na_out; const double *dark_na; int keep_na;
 };
-// sorad's results on a tile: each in a plane of its own
+// sorad's results on a tile: each in a plane of its own; the GEOSRAD_SWC_* outputs, then the GEOSRAD_SWCNA_* ones
 constexpr TileOut swc_tile[] = {{0, PLANE, 0}, {0, PLANE, 1}, {0, PLANE, 2}, {0, PLANE, 3}, {1, PLANE, 4}, {1, PLANE, 5}, {1, PLANE, 6}, {1, PLANE, 7},
-                                {1, PLANE, 8}, {1, PLANE, 9}, {8, PLANE, 10}, {8, PLANE, 11}, {8, PLANE, 12}};
-static_assert(std::size(swc_tile) == GEOSRAD_SWC_NOUT && GEOSRAD_SWC_FSCU == 3 && GEOSRAD_SWC_FSWBAND == 10, "one row for each GEOSRAD_SWC_* output");
+                                {1, PLANE, 8}, {1, PLANE, 9}, {8, PLANE, 10}, {8, PLANE, 11}, {8, PLANE, 12},
+                                {0, PLANE, 13}, {0, PLANE, 14}, {0, PLANE, 15}, {0, PLANE, 16}, {8, PLANE, 17}};
+constexpr int SWC_NTILE = GEOSRAD_SWC_NOUT + GEOSRAD_SWCNA_NOUT;
+// the `out` row of which na_out[k] is the aerosol-free twin
+constexpr int SWCNA_TWIN[GEOSRAD_SWCNA_NOUT] = {GEOSRAD_SWC_FSW, GEOSRAD_SWC_FSC, GEOSRAD_SWC_FSWU, GEOSRAD_SWC_FSCU, GEOSRAD_SWC_FSWBAND};
+static_assert(std::size(swc_tile) == SWC_NTILE && GEOSRAD_SWC_FSCU == 3 && GEOSRAD_SWC_FSWBAND == 10 && GEOSRAD_SWCNA_FSWBANDNA == 4,
+              "one row for each GEOSRAD_SWC_* and GEOSRAD_SWCNA_* output");
 template <typename R, bool LIT> using SwcPrepOf = std::conditional_t<LIT, SwcLit<R>, SwcPrep<R>>;
 template <typename R, bool LIT = false> __global__ void __launch_bounds__(256) k_swc_prep(SwcPrepOf<R, LIT> P)
 {

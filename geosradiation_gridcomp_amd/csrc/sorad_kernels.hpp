@@ -19,6 +19,14 @@
 //   k_sorad_col    : per column, lanes = (pass, level), the 35 passes on chip: no scratch (GEOSRAD_SORAD_PATH=col)
 //   k_sorad_reduce : per column   - weighted sum over the passes (hk_uv, hk_ir), flux reductions, surface rescaling
 // Sky situations of zero weight (ct = 0: a cloud group without cloud) are skipped: their contribution is `+ x * 0`.
+//
+// The aerosol-free flavour (template parameter NA of the three pass kernels and of k_sorad_reduce; geosrad_sorad_na[_dev]): what
+// GEOS_SolarGridComp.F90:3249-3259 obtains from a second SORADCORE with zero aerosol arrays (:4541-4551).  The pass kernel's aerosol
+// operands are the constant so_no_aerosol() - nothing is loaded from taua / ssaa / asya, their gathered copies or their LDS copies - and
+// everything else per position (lay, swh, colv, cld, cls, perm, cls_off) is what the with-aerosol pass of the same chunk read.  The
+// arithmetic is that of the with-aerosol flavour fed zeros, operation for operation (x + 0 and 0 * x are not foldable in IEEE
+// arithmetic), so the results are bit for bit those of a call with three arrays of zeros.  It follows the with-aerosol pass, sum and
+// reduction of the chunk on the same stream and reuses scr, psum and the dynamic LDS.
 #pragma once
 #include <type_traits>
 #include "lw_kernels.hpp"
@@ -334,6 +342,8 @@ __global__ void __launch_bounds__(256) k_sorad_cloud(SoradArgs<R> A, const Sorad
 //   26..29: fall, fclr, fupa, fupc (class 0: fall, fupa only - one sky situation of weight 1, the clear-sky fluxes are the same numbers)
 // ---------------------------------------------------------------------------------------------------
 template <typename R> struct SoL5 { R rr, tt, td, rs, ts; };
+// optical thickness, single-scattering albedo x thickness and asymmetry factor x that of a layer's aerosols in the aerosol-free flavour
+template <typename R> GR_DEV constexpr R so_no_aerosol() { return (R)0; }
 
 // the divisions of the adding equations and of the layers' mixed optical properties (~20 per level and pass in a class-7 column): hardware
 // reciprocal (1 ulp) in the fp32 instantiation, v_rcp_f64 + Newton steps (gr_div64) in the fp64 one, instead of the correctly rounded
@@ -362,7 +372,7 @@ template <typename R, bool LOW> GR_DEV void so_add_down(const SoL5<R> &l, R &tda
     tda = tda * l.td; tta = ntta; rsa = nrsa;
 }
 
-template <typename R, int CLS>
+template <typename R, int CLS, bool NA = false>
 __global__ void __launch_bounds__(256) k_sorad_pass(SoradArgs<R> A, const SoradDev<R> *__restrict__ Tp)
 {
     constexpr bool GH = (CLS & 4) != 0, GM = (CLS & 2) != 0, GL = (CLS & 1) != 0;       // groups with cloud
@@ -400,18 +410,24 @@ __global__ void __launch_bounds__(256) k_sorad_pass(SoradArgs<R> A, const SoradD
     // ---- layers: clear and cloudy portion (:436-520, 996-1068) ---------------------------------------------------------
     struct In6 { R dp, wh, oh, ta, sa, as; };
     // aerosols: the three NIR bands are read by ten passes each - from the position-ordered copies (k_sorad_gather); the five UV / PAR
-    // bands by one pass each - from the caller's arrays, through the permutation
+    // bands by one pass each - from the caller's arrays, through the permutation.  NA: none is read
     const size_t aer_rows = (size_t)SO_NGATHER * np;
     const bool from_copy = SO_NGATHER == 8 || !uv;
-    const R *a0 = from_copy ? A.aer + ((size_t)(iv - 1 - (8 - SO_NGATHER)) * np) * m + i : A.taua + ((size_t)(iv - 1) * np) * A.ld + col;
-    const R *a1 = from_copy ? a0 + aer_rows * m : A.ssaa + ((size_t)(iv - 1) * np) * A.ld + col;
-    const R *a2 = from_copy ? a1 + aer_rows * m : A.asya + ((size_t)(iv - 1) * np) * A.ld + col;
+    const R *a0 = nullptr, *a1 = nullptr, *a2 = nullptr;
+    if constexpr (!NA) {
+        a0 = from_copy ? A.aer + ((size_t)(iv - 1 - (8 - SO_NGATHER)) * np) * m + i : A.taua + ((size_t)(iv - 1) * np) * A.ld + col;
+        a1 = from_copy ? a0 + aer_rows * m : A.ssaa + ((size_t)(iv - 1) * np) * A.ld + col;
+        a2 = from_copy ? a1 + aer_rows * m : A.asya + ((size_t)(iv - 1) * np) * A.ld + col;
+    }
     const size_t astr = from_copy ? (size_t)m : (size_t)A.ld;
     auto ldin = [&](int k) {
         In6 v;
         v.dp = A.lay[((size_t)0 * K2 + k) * m + i]; v.wh = A.lay[((size_t)1 * K2 + k) * m + i]; v.oh = A.lay[((size_t)2 * K2 + k) * m + i];
-        const size_t ja = (size_t)(k - 1) * astr;
-        v.ta = a0[ja]; v.sa = a1[ja]; v.as = a2[ja];
+        if constexpr (NA) { v.ta = so_no_aerosol<R>(); v.sa = so_no_aerosol<R>(); v.as = so_no_aerosol<R>(); }
+        else {
+            const size_t ja = (size_t)(k - 1) * astr;
+            v.ta = a0[ja]; v.sa = a1[ja]; v.as = a2[ja];
+        }
         return v;
     };
     struct Cl4 { R tcb, tcf, asyc, ssac; };
@@ -638,7 +654,7 @@ __global__ void __launch_bounds__(256) k_sorad_ident(SoradArgs<R> A)
 // 1004-1068) as in k_sorad_pass, the cloudy portion formed at every layer (with the cloud's unscaled optical thickness, 0 where it has no
 // condensate).  Every step down is written tda * rsa * rr, as the reference's CLDFLXY writes it at every level (CLDFLX: tda * rr * rsa in
 // the low group), so the clear-sky fluxes agree with the default build's to rounding, not bit for bit.
-template <typename R>
+template <typename R, bool NA = false>
 __global__ void __launch_bounds__(256) k_sorad_pass_oc(SoradArgs<R> A, const SoradDev<R> *__restrict__ Tp)
 {
     int bstart, pass;
@@ -664,16 +680,19 @@ __global__ void __launch_bounds__(256) k_sorad_pass_oc(SoradArgs<R> A, const Sor
     const R rb = uv ? A.rsuvbm[i] : A.rsirbm[i], rd = uv ? A.rsuvdf[i] : A.rsirdf[i];
     const R td0 = uv ? gr_exp<R>(-(wvtoa * T.wk_uv[ib - 1] + o3toa * T.zk_uv[ib - 1]) / cz) : gr_exp<R>(-wvtoa * T.xk_ir[ik - 1] / cz);
     const R k_ry = uv ? T.ry_uv[ib - 1] : T.ry_ir[ib - 1], k_zk = uv ? T.zk_uv[ib - 1] : (R)0, k_wk = uv ? T.wk_uv[ib - 1] : T.xk_ir[ik - 1];
-    const R *a0 = A.taua + ((size_t)(iv - 1) * np) * A.ld + i, *a1 = A.ssaa + ((size_t)(iv - 1) * np) * A.ld + i,
-            *a2 = A.asya + ((size_t)(iv - 1) * np) * A.ld + i;
+    const R *a0 = nullptr, *a1 = nullptr, *a2 = nullptr;      // NA: none is read
+    if constexpr (!NA) {
+        a0 = A.taua + ((size_t)(iv - 1) * np) * A.ld + i; a1 = A.ssaa + ((size_t)(iv - 1) * np) * A.ld + i;
+        a2 = A.asya + ((size_t)(iv - 1) * np) * A.ld + i;
+    }
     // ---- sweep U: the layers' clear (1) and cloudy (2) portions, parked for sweep D; composites from the surface --------------------
     {
         R rra[2] = {rb, rb}, rxa[2] = {rd, rd};
         RRAV(np + 1, 0) = rb; RXAV(np + 1, 0) = rd; RRAV(np + 1, 1) = rb; RXAV(np + 1, 1) = rd;
         for (int k = np; k >= 1; k--) {
             const R dp = A.lay[((size_t)0 * K2 + k) * m + i], wh = A.lay[((size_t)1 * K2 + k) * m + i], oh = A.lay[((size_t)2 * K2 + k) * m + i];
-            const size_t ja = (size_t)(k - 1) * A.ld;
-            const R ta_ = a0[ja], sa_ = a1[ja], as_ = a2[ja];
+            R ta_ = so_no_aerosol<R>(), sa_ = so_no_aerosol<R>(), as_ = so_no_aerosol<R>();
+            if constexpr (!NA) { const size_t ja = (size_t)(k - 1) * A.ld; ta_ = a0[ja]; sa_ = a1[ja]; as_ = a2[ja]; }
             const R tcb = A.cld[(((size_t)grp * 4 + 0) * K2 + k) * m + i], tcf = A.cld[(((size_t)grp * 4 + 1) * K2 + k) * m + i];
             const R asyc = A.cld[(((size_t)grp * 4 + 2) * K2 + k) * m + i];
             const R ssac = uv ? (R)1 : A.cld[(((size_t)grp * 4 + 3) * K2 + k) * m + i];
@@ -790,7 +809,7 @@ template <typename R> __host__ __device__ constexpr size_t sorad_col_lds_reals(i
     return (size_t)19 * (np + 2) + (size_t)24 * np + (size_t)sorad_col_q(np) * 50 * (np + 2);
 }
 
-template <typename R>
+template <typename R, bool NA = false>
 __global__ void __launch_bounds__(256) k_sorad_col(SoradArgs<R> A, const SoradDev<R> *__restrict__ Tp, SoradOut<R> O)
 {
     extern __shared__ __align__(16) unsigned char so_lds_raw[];
@@ -811,9 +830,11 @@ __global__ void __launch_bounds__(256) k_sorad_col(SoradArgs<R> A, const SoradDe
     R *const s_lyq = s_cld + 16 * K2;              // [Q][2 portions][5][K2]  rr, tt, td, rs, ts; after phase B: [Q][4][K2] level fluxes of the pass
     R *const s_cpq = s_lyq + (size_t)Q * 10 * K2;  // [Q][8 situations][5][K2] tda, tta, rsa (level = lower boundary of k), rra, rxa
     for (int e = t; e < 3 * K2; e += nt) s_lay[e] = A.lay[(size_t)e * m + i];
-    for (int e = t; e < 8 * np; e += nt) {
-        const size_t ja = (size_t)e * ld + i;
-        s_aer[e] = A.taua[ja]; s_aer[8 * np + e] = A.ssaa[ja]; s_aer[16 * np + e] = A.asya[ja];
+    if constexpr (!NA) {      // NA: the aerosols' part of the LDS stays unused
+        for (int e = t; e < 8 * np; e += nt) {
+            const size_t ja = (size_t)e * ld + i;
+            s_aer[e] = A.taua[ja]; s_aer[8 * np + e] = A.ssaa[ja]; s_aer[16 * np + e] = A.asya[ja];
+        }
     }
     for (int e = t; e < 16 * K2; e += nt) s_cld[e] = A.cld[(size_t)e * m + i];
     const R cz = A.cosz[i], dsm = (R)0.602;
@@ -844,8 +865,8 @@ __global__ void __launch_bounds__(256) k_sorad_col(SoradArgs<R> A, const SoradDe
                 for (int j = 1; j <= 2; j++) { LY(0, j, np + 1) = rb; LY(3, j, np + 1) = rd; LY(2, j, np + 1) = 0; LY(1, j, np + 1) = 0; LY(4, j, np + 1) = 0; }
             } else {
                 const R dp = s_lay[0 * K2 + k], wh = s_lay[1 * K2 + k], oh = s_lay[2 * K2 + k];
-                const int ja = (iv - 1) * np + (k - 1);
-                const R ta_ = s_aer[ja], sa_ = s_aer[8 * np + ja], as_ = s_aer[16 * np + ja];
+                R ta_ = so_no_aerosol<R>(), sa_ = so_no_aerosol<R>(), as_ = so_no_aerosol<R>();
+                if constexpr (!NA) { const int ja = (iv - 1) * np + (k - 1); ta_ = s_aer[ja]; sa_ = s_aer[8 * np + ja]; as_ = s_aer[16 * np + ja]; }
                 R taurs, tausto, ssatau;
                 if (uv) {
                     taurs = T.ry_uv[ib - 1] * dp;
@@ -976,8 +997,10 @@ __global__ void __launch_bounds__(256) k_sorad_col(SoradArgs<R> A, const SoradDe
 
 // ---------------------------------------------------------------------------------------------------
 // k_sorad_reduce: per column -- flux integration over the passes (Eq. 6.1), O2 / CO2 reductions (:1425-1552), surface rescaling
+// NA (the aerosol-free pass; GEOS_SolarGridComp.F90:3997-4016 keeps FSWNAN, FSCNAN, FSWUNAN, FSCUNAN, FSWBANDNAN of it): flx, flc and
+// flx_sfc_band only - neither the direct / diffuse components nor drband / dfband are formed or written
 // ---------------------------------------------------------------------------------------------------
-template <typename R>
+template <typename R, bool NA = false>
 __global__ void __launch_bounds__(256) k_sorad_reduce(SoradArgs<R> A, const SoradDev<R> *__restrict__ Tp, SoradOut<R> O)
 {
     const int pos = blockIdx.x * blockDim.x + threadIdx.x;
@@ -993,7 +1016,9 @@ __global__ void __launch_bounds__(256) k_sorad_reduce(SoradArgs<R> A, const Sora
     for (int p = 0; p < SO_NPASS; p++) {
         const R hk = A.hk[p], fs = A.psum[((size_t)p * 3 + 0) * m + pos], fd = A.psum[((size_t)p * 3 + 1) * m + pos];
         const int b = p < 5 ? p : 5 + (p - 5) / 10;
-        band[b] = band[b] + A.psum[((size_t)p * 3 + 2) * m + pos] * hk; drb[b] = drb[b] + fs * hk; dfb[b] = dfb[b] + fd * hk;
+        band[b] = band[b] + A.psum[((size_t)p * 3 + 2) * m + pos] * hk;
+        if constexpr (NA) continue;
+        drb[b] = drb[b] + fs * hk; dfb[b] = dfb[b] + fd * hk;
         if (p < 4) { fdiruv = fdiruv + fs * hk; fdifuv = fdifuv + fd * hk; }
         else if (p == 4) { fdirpar = fs * hk; fdifpar = fd * hk; }
         else { fdirir = fdirir + fs * hk; fdifir = fdifir + fd * hk; }
@@ -1052,11 +1077,13 @@ __global__ void __launch_bounds__(256) k_sorad_reduce(SoradArgs<R> A, const Sora
     const R eps = sizeof(R) == 4 ? (R)1.1920929e-07 : (R)2.220446049250313e-16;
     if (fabs(xx4) > eps) { xx4 = (R)1.0 - dfsfc / xx4; xx4 = xx4 < 1 ? xx4 : (R)1; xx4 = xx4 > 0 ? xx4 : (R)0; }
     else xx4 = 0;
-    O.fdirir[i] = xx4 * fdirir; O.fdifir[i] = xx4 * fdifir; O.fdiruv[i] = xx4 * fdiruv; O.fdifuv[i] = xx4 * fdifuv;
-    O.fdirpar[i] = xx4 * fdirpar; O.fdifpar[i] = xx4 * fdifpar;
+    if constexpr (!NA) {
+        O.fdirir[i] = xx4 * fdirir; O.fdifir[i] = xx4 * fdifir; O.fdiruv[i] = xx4 * fdiruv; O.fdifuv[i] = xx4 * fdifuv;
+        O.fdirpar[i] = xx4 * fdirpar; O.fdifpar[i] = xx4 * fdifpar;
+    }
     for (int b = 0; b < 8; b++) {
         O.flx_sfc_band[(size_t)b * ld + i] = xx4 * band[b];
-        if (A.do_drfband) { O.drband[(size_t)b * ld + i] = xx4 * drb[b]; O.dfband[(size_t)b * ld + i] = xx4 * dfb[b]; }
+        if (!NA && A.do_drfband) { O.drband[(size_t)b * ld + i] = xx4 * drb[b]; O.dfband[(size_t)b * ld + i] = xx4 * dfb[b]; }
     }
 #undef OUT2
 }

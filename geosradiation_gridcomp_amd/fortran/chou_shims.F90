@@ -69,7 +69,7 @@ module soradmod
    use geosrad_c
    implicit none
    private
-   public :: sorad
+   public :: sorad, sorad_na
    integer, parameter :: nband = 8
    logical, save :: loaded = .false.
 contains
@@ -93,6 +93,59 @@ contains
       real, target :: fdiruv(m),fdifuv(m),fdirpar(m),fdifpar(m),fdirir(m),fdifir(m)
       real, target :: flx_sfc_band(m,nband)
       real, intent(inout), dimension(:,:), pointer :: drband, dfband      ! only touched if (do_drfband), as in the reference
+      type(c_ptr) :: nout(SONA_NOUT)
+      nout = c_null_ptr
+      call sorad_call(m,np,nb,cosz,pl,ta,wa,oa,co2,cwc,fcld,ict,icb,reff,hk_uv,hk_ir,taua,ssaa,asya,rsuvbm,rsuvdf,rsirbm,rsirdf, &
+         flx,flc,fdiruv,fdifuv,fdirpar,fdifpar,fdirir,fdifir,flxu,flcu,flx_sfc_band,do_drfband,drband,dfband,nout)
+   end subroutine sorad
+
+   ! sorad + the aerosol-free fluxes of the same columns from the same call (geosrad_sorad_na; not a name of the reference, which calls
+   ! sorad a second time with zero aerosol arrays, GEOS_SolarGridComp.F90:3249-3259, :4541-4551): flx_na, flc_na, flxu_na, flcu_na
+   ! (m,np+1) and flx_sfc_band_na (m,8) are what that second call returns in flx, flc, flxu, flcu, flx_sfc_band
+   subroutine sorad_na (m,np,nb,cosz,pl,ta,wa,oa,co2,&
+         cwc,fcld,ict,icb,reff,hk_uv,hk_ir,&
+         taua,ssaa,asya,&
+         rsuvbm,rsuvdf,rsirbm,rsirdf,&
+         flx,flc,fdiruv,fdifuv,&
+         fdirpar,fdifpar,fdirir,fdifir,&
+         flxu,flcu,&
+         flx_sfc_band,&
+         do_drfband,drband,dfband,&
+         flx_na,flc_na,flxu_na,flcu_na,flx_sfc_band_na)
+      integer :: m,np,ict,icb,nb
+      real, target :: cosz(m),pl(m,np+1),ta(m,np),wa(m,np),oa(m,np)
+      real :: co2
+      real, target :: cwc(m,np,4),fcld(m,np),reff(m,np,4),hk_uv(5),hk_ir(3,10)
+      real, target :: rsuvbm(m),rsuvdf(m),rsirbm(m),rsirdf(m)
+      real, target :: taua(m,np,nb),ssaa(m,np,nb),asya(m,np,nb)
+      logical, intent(in) :: do_drfband
+      real, target :: flx(m,np+1),flc(m,np+1),flxu(m,np+1),flcu(m,np+1)
+      real, target :: fdiruv(m),fdifuv(m),fdirpar(m),fdifpar(m),fdirir(m),fdifir(m)
+      real, target :: flx_sfc_band(m,nband)
+      real, intent(inout), dimension(:,:), pointer :: drband, dfband
+      real, target :: flx_na(m,np+1),flc_na(m,np+1),flxu_na(m,np+1),flcu_na(m,np+1),flx_sfc_band_na(m,nband)
+      type(c_ptr) :: nout(SONA_NOUT)
+      nout(SONA_FLX) = c_loc(flx_na); nout(SONA_FLC) = c_loc(flc_na); nout(SONA_FLXU) = c_loc(flxu_na); nout(SONA_FLCU) = c_loc(flcu_na)
+      nout(SONA_SFCBAND) = c_loc(flx_sfc_band_na)
+      call sorad_call(m,np,nb,cosz,pl,ta,wa,oa,co2,cwc,fcld,ict,icb,reff,hk_uv,hk_ir,taua,ssaa,asya,rsuvbm,rsuvdf,rsirbm,rsirdf, &
+         flx,flc,fdiruv,fdifuv,fdirpar,fdifpar,fdirir,fdifir,flxu,flcu,flx_sfc_band,do_drfband,drband,dfband,nout)
+   end subroutine sorad_na
+
+   ! the one call behind sorad and sorad_na: nout = the five aerosol-free arrays, all c_null_ptr from sorad, which goes to geosrad_sorad as before
+   subroutine sorad_call (m,np,nb,cosz,pl,ta,wa,oa,co2,cwc,fcld,ict,icb,reff,hk_uv,hk_ir,taua,ssaa,asya,rsuvbm,rsuvdf,rsirbm,rsirdf, &
+         flx,flc,fdiruv,fdifuv,fdirpar,fdifpar,fdirir,fdifir,flxu,flcu,flx_sfc_band,do_drfband,drband,dfband,nout)
+      integer :: m,np,ict,icb,nb
+      real, target :: cosz(m),pl(m,np+1),ta(m,np),wa(m,np),oa(m,np)
+      real :: co2
+      real, target :: cwc(m,np,4),fcld(m,np),reff(m,np,4),hk_uv(5),hk_ir(3,10)
+      real, target :: rsuvbm(m),rsuvdf(m),rsirbm(m),rsirdf(m)
+      real, target :: taua(m,np,nb),ssaa(m,np,nb),asya(m,np,nb)
+      logical, intent(in) :: do_drfband
+      real, target :: flx(m,np+1),flc(m,np+1),flxu(m,np+1),flcu(m,np+1)
+      real, target :: fdiruv(m),fdifuv(m),fdirpar(m),fdifpar(m),fdirir(m),fdifir(m)
+      real, target :: flx_sfc_band(m,nband)
+      real, intent(inout), dimension(:,:), pointer :: drband, dfband      ! only touched if (do_drfband), as in the reference
+      type(c_ptr), intent(in) :: nout(SONA_NOUT)
       integer(c_int) :: rc
       real :: x
       type(c_ptr) :: pdr, pdf
@@ -117,14 +170,22 @@ contains
 #else
       rc = geosrad_set_overcast(geosrad_ctx_handle(), iand(rc, not(GEOSRAD_OVERCAST_SORAD)))
 #endif
-      rc = geosrad_sorad(geosrad_ctx_handle(), int(m,c_int), int(np,c_int), int(nb,c_int), c_loc(cosz), c_loc(pl), c_loc(ta), c_loc(wa), &
-         c_loc(oa), real(co2,c_double), c_loc(cwc), c_loc(fcld), int(ict,c_int), int(icb,c_int), c_loc(reff), c_loc(hk_uv), c_loc(hk_ir), &
-         c_loc(taua), c_loc(ssaa), c_loc(asya), c_loc(rsuvbm), c_loc(rsuvdf), c_loc(rsirbm), c_loc(rsirdf), c_loc(flx), c_loc(flc), &
-         c_loc(fdiruv), c_loc(fdifuv), c_loc(fdirpar), c_loc(fdifpar), c_loc(fdirir), c_loc(fdifir), c_loc(flxu), c_loc(flcu), &
-         c_loc(flx_sfc_band), merge(1_c_int, 0_c_int, do_drfband), pdr, pdf)
+      if (c_associated(nout(SONA_FLX))) then      ! sorad_na passes all five
+         rc = geosrad_sorad_na(geosrad_ctx_handle(), int(m,c_int), int(np,c_int), int(nb,c_int), c_loc(cosz), c_loc(pl), c_loc(ta), c_loc(wa), &
+            c_loc(oa), real(co2,c_double), c_loc(cwc), c_loc(fcld), int(ict,c_int), int(icb,c_int), c_loc(reff), c_loc(hk_uv), c_loc(hk_ir), &
+            c_loc(taua), c_loc(ssaa), c_loc(asya), c_loc(rsuvbm), c_loc(rsuvdf), c_loc(rsirbm), c_loc(rsirdf), c_loc(flx), c_loc(flc), &
+            c_loc(fdiruv), c_loc(fdifuv), c_loc(fdirpar), c_loc(fdifpar), c_loc(fdirir), c_loc(fdifir), c_loc(flxu), c_loc(flcu), &
+            c_loc(flx_sfc_band), merge(1_c_int, 0_c_int, do_drfband), pdr, pdf, nout)
+      else      ! sorad: the entry point it has always called
+         rc = geosrad_sorad(geosrad_ctx_handle(), int(m,c_int), int(np,c_int), int(nb,c_int), c_loc(cosz), c_loc(pl), c_loc(ta), c_loc(wa), &
+            c_loc(oa), real(co2,c_double), c_loc(cwc), c_loc(fcld), int(ict,c_int), int(icb,c_int), c_loc(reff), c_loc(hk_uv), c_loc(hk_ir), &
+            c_loc(taua), c_loc(ssaa), c_loc(asya), c_loc(rsuvbm), c_loc(rsuvdf), c_loc(rsirbm), c_loc(rsirdf), c_loc(flx), c_loc(flc), &
+            c_loc(fdiruv), c_loc(fdifuv), c_loc(fdirpar), c_loc(fdifpar), c_loc(fdirir), c_loc(fdifir), c_loc(flxu), c_loc(flcu), &
+            c_loc(flx_sfc_band), merge(1_c_int, 0_c_int, do_drfband), pdr, pdf)
+      end if
       if (rc /= 0) call geosrad_fail('sorad')
       if (do_drfband) then
          drband(1:m,1:nband) = dr; dfband(1:m,1:nband) = df
       end if
-   end subroutine sorad
+   end subroutine sorad_call
 end module soradmod

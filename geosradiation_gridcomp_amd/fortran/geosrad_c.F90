@@ -9,8 +9,11 @@ module geosrad_c
    public :: geosrad_create, geosrad_destroy, geosrad_last_error, geosrad_load_tables_lw, geosrad_load_inhomogeneity
    public :: geosrad_set_corr_lengths, geosrad_rrtmg_lw, geosrad_rrtmg_lw_na, geosrad_mcica, geosrad_clearcounts, geosrad_read_table
    public :: geosrad_set_overcast, geosrad_get_overcast, GEOSRAD_OVERCAST_IRRAD, GEOSRAD_OVERCAST_SORAD
+   public :: geosrad_sorad_na, geosrad_sorad_na_dev, geosrad_sw_driver_chou_na_dev, geosrad_sw_driver_chou_na_lit_dev
 
    integer(c_int), parameter :: GEOSRAD_OVERCAST_IRRAD = 1, GEOSRAD_OVERCAST_SORAD = 2     ! geosrad_set_overcast flags
+   ! GEOSRAD_SONA_*, 1-based: the aerosol-free arrays of geosrad_sorad_na[_dev]
+   integer, parameter, public :: SONA_FLX = 1, SONA_FLC = 2, SONA_FLXU = 3, SONA_FLCU = 4, SONA_SFCBAND = 5, SONA_NOUT = 5
 
    type(c_ptr), save :: ctx = c_null_ptr
 
@@ -93,6 +96,50 @@ module geosrad_c
          real(c_double), value :: co2
          type(c_ptr), value :: cosz, pl, ta, wa, oa, cwc, fcld, reff, hk_uv, hk_ir, taua, ssaa, asya, rsuvbm, rsuvdf, rsirbm, rsirdf, flx, flc, &
             fdiruv, fdifuv, fdirpar, fdifpar, fdirir, fdifir, flxu, flcu, flx_sfc_band, drband, dfband
+      end function
+      ! geosrad_sorad + the aerosol-free fluxes of the same columns from the same call: na_out(GEOSRAD_SONA_NOUT = 5) = flx, flc, flxu, flcu
+      ! (m,np+1), flx_sfc_band (m,8) without aerosols, c_null_ptr = not taken
+      integer(c_int) function geosrad_sorad_na(ctx, m, np, nb, cosz, pl, ta, wa, oa, co2, cwc, fcld, ict, icb, reff, hk_uv, hk_ir, taua, ssaa, &
+            asya, rsuvbm, rsuvdf, rsirbm, rsirdf, flx, flc, fdiruv, fdifuv, fdirpar, fdifpar, fdirir, fdifir, flxu, flcu, flx_sfc_band, &
+            do_drfband, drband, dfband, na_out) bind(C, name='geosrad_sorad_na')
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: m, np, nb, ict, icb, do_drfband
+         real(c_double), value :: co2
+         type(c_ptr), value :: cosz, pl, ta, wa, oa, cwc, fcld, reff, hk_uv, hk_ir, taua, ssaa, asya, rsuvbm, rsuvdf, rsirbm, rsirdf, flx, flc, &
+            fdiruv, fdifuv, fdirpar, fdifpar, fdirir, fdifir, flxu, flcu, flx_sfc_band, drband, dfband
+         type(c_ptr), intent(in) :: na_out(*)
+      end function
+      integer(c_int) function geosrad_sorad_na_dev(ctx, stream, m, np, nb, cosz, pl, ta, wa, oa, co2, cwc, fcld, ict, icb, reff, hk_uv, hk_ir, &
+            taua, ssaa, asya, rsuvbm, rsuvdf, rsirbm, rsirdf, flx, flc, fdiruv, fdifuv, fdirpar, fdifpar, fdirir, fdifir, flxu, flcu, &
+            flx_sfc_band, do_drfband, drband, dfband, na_out) bind(C, name='geosrad_sorad_na_dev')
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: ctx, stream
+         integer(c_int), value :: m, np, nb, ict, icb, do_drfband
+         real(c_double), value :: co2
+         type(c_ptr), value :: cosz, pl, ta, wa, oa, cwc, fcld, reff, hk_uv, hk_ir, taua, ssaa, asya, rsuvbm, rsuvdf, rsirbm, rsirdf, flx, flc, &
+            fdiruv, fdifuv, fdirpar, fdifpar, fdirir, fdifir, flxu, flcu, flx_sfc_band, drband, dfband
+         type(c_ptr), intent(in) :: na_out(*)
+      end function
+      ! the Chou-Suarez branch of SORADCORE with the aerosol-free internals of the same solver call (module geosrad_gridcomp wraps them)
+      integer(c_int) function geosrad_sw_driver_chou_na_dev(ctx, stream, ncol, lm, fin, consts, lcldmh, lcldlm, hk_uv, hk_ir, do_drfband, fout, &
+            na_out) bind(C, name='geosrad_sw_driver_chou_na_dev')
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: ctx, stream
+         integer(c_int), value :: ncol, lm, lcldmh, lcldlm, do_drfband
+         type(c_ptr), intent(in) :: fin(*), fout(*), na_out(*)
+         real(c_double), intent(in) :: consts(*)
+         real, intent(in) :: hk_uv(*), hk_ir(*)
+      end function
+      integer(c_int) function geosrad_sw_driver_chou_na_lit_dev(ctx, stream, ncol, nlit, lit_index, lit_pos, lm, fin, consts, lcldmh, lcldlm, &
+            hk_uv, hk_ir, do_drfband, dark, keep_mask, fout, dark_na, keep_na, na_out) bind(C, name='geosrad_sw_driver_chou_na_lit_dev')
+         import :: c_int, c_ptr, c_double, c_int64_t
+         type(c_ptr), value :: ctx, stream, lit_index, lit_pos
+         integer(c_int), value :: ncol, nlit, lm, lcldmh, lcldlm, do_drfband, keep_na
+         type(c_ptr), intent(in) :: fin(*), fout(*), na_out(*)
+         real(c_double), intent(in) :: consts(*), dark(*), dark_na(*)
+         real, intent(in) :: hk_uv(*), hk_ir(*)
+         integer(c_int64_t), value :: keep_mask
       end function
       integer(c_int) function geosrad_load_inhomogeneity(ctx, ih, path) bind(C, name='geosrad_load_inhomogeneity')
          import; type(c_ptr), value :: ctx; integer(c_int), value :: ih; character(kind=c_char), intent(in) :: path(*)

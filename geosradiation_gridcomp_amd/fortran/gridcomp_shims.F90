@@ -5,13 +5,14 @@
 ! GridComp needs to keep its INTERNAL state on the device between the full calculation and the heartbeat updates.
 module geosrad_gridcomp
    use iso_c_binding
-   use geosrad_c, only : geosrad_ctx_handle, geosrad_fail, geosrad_data_path, geosrad_load_tables_chou_sw, geosrad_load_tables_chou_lw
+   use geosrad_c, only : geosrad_ctx_handle, geosrad_fail, geosrad_data_path, geosrad_load_tables_chou_sw, geosrad_load_tables_chou_lw, &
+      geosrad_sw_driver_chou_na_dev, geosrad_sw_driver_chou_na_lit_dev
    implicit none
    private
    public :: lw_driver_rrtmg, lw_driver_rrtmg_rats, lw_update_rats, lw_update_bands, sw_update_surface, sw_update_clouds, sw_update_cldhb, sw_driver_rrtmg, sw_driver_chou, lw_driver_chou, lw_chou_post, lw_update_flx, sw_update_export, rad_tendencies
    public :: lit_index, lit_pack, lit_unpack, sw_driver_rrtmg_lit, sw_driver_chou_lit
    public :: sw_update_obio, sw_driver_rrtmg_obio, sw_driver_rrtmg_obio_lit
-   public :: lw_driver_rrtmg_na
+   public :: lw_driver_rrtmg_na, sw_driver_chou_na, sw_driver_chou_na_lit
    ! ocean-biology coupling (SOLAR_TO_OBIO): the schemes of sw_update_obio (GEOSRAD_OBIO_*) and the number of OBIO bands
    integer, parameter, public :: OBIO_CHOU = 0, OBIO_RRTMG = 1, OBIO_BANDS = 2, NB_OBIO = 33
    public :: dev_alloc, dev_free, dev_put, dev_get, dev_sync
@@ -65,6 +66,8 @@ module geosrad_gridcomp
       LWK_FLAD_INT = 7, LWK_FLXAD_INT = 8, LWK_DFDTS = 9, LWK_SFCEM_INT = 10, LWK_FLX_INT = 11, LWK_FLXA_INT = 12, LWK_FLC_INT = 13, &
       LWK_FLA_INT = 14, LWK_DFDTSC = 15, LWK_DFDTSNA = 16, LWK_DFDTSCNA = 17, LWK_TS_INT = 18, LWK_TAUIR = 19, LWK_CLDTMP = 20, &
       LWK_CLDPRS = 21, LWK_TSREFF = 22, LWK_DSFDTS0 = 23, LWK_SFCEM0 = 24, LWK_LWS0 = 25, LWK_T2M = 26, LWK_TAUDIAG = 27, LWK_NOUT = 27
+   ! ---- GEOSRAD_SWCNA_* (aerosol-free internals of the Chou-Suarez branch, from the same call) ----
+   integer, parameter, public :: SWCNA_FSWNA = 1, SWCNA_FSCNA = 2, SWCNA_FSWUNA = 3, SWCNA_FSCUNA = 4, SWCNA_FSWBANDNA = 5, SWCNA_NOUT = 5
    ! ---- GEOSRAD_SWC_* ----
    integer, parameter, public :: SWC_PLE = 1, SWC_T = 2, SWC_Q = 3, SWC_OX = 4, SWC_CL = 5, SWC_QI = 6, SWC_QL = 7, SWC_QR = 8, SWC_QS = 9, &
       SWC_RI = 10, SWC_RL = 11, SWC_RR = 12, SWC_RS = 13, SWC_TAUA = 14, SWC_SSAA = 15, SWC_ASYA = 16, SWC_ZT = 17, SWC_ALBVR = 18, &
@@ -585,6 +588,40 @@ contains
       rc = geosrad_sw_driver_chou_lit_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(NumLit,c_int), d_idx, d_pos, int(lm,c_int), &
             fin, consts, int(lcldmh,c_int), int(lcldlm,c_int), hk_uv_temp, hk_ir_temp, merge(1_c_int, 0_c_int, do_drfband), &
             real(dark,c_double), keep_mask(keep), fout)
+   end subroutine
+   ! sw_driver_chou / sw_driver_chou_lit with the aerosol-free internals FSWNAN, FSCNAN, FSWUNAN, FSCUNAN (IM,JM,0:LM) and FSWBANDNAN
+   ! (IM,JM,8) the GridComp otherwise obtains from a second SORADCORE with include_aerosols = .false. (GEOS_SolarGridComp.F90:3249-3259,
+   ! :3997-4016), from the same preparation and the same solver call: nout(SWCNA_*) on the device, c_null_ptr = not associated.  DRBAND /
+   ! DFBAND keep their do_drfband meaning (:4010-4016).  On the tile dark_na / keep_na are the DEFAULTs and keep flags of nout.
+   subroutine sw_driver_chou_na(ncol, lm, fin, consts, lcldmh, lcldlm, hk_uv_temp, hk_ir_temp, do_drfband, fout, nout, rc)
+      integer, intent(in) :: ncol, lm, lcldmh, lcldlm
+      type(c_ptr), intent(in) :: fin(SWC_NIN), fout(SWC_NOUT), nout(SWCNA_NOUT)
+      real(c_double), intent(in) :: consts(SWC_NCONST)
+      real, intent(in) :: hk_uv_temp(5), hk_ir_temp(3,10)
+      logical, intent(in) :: do_drfband
+      integer, intent(out) :: rc
+      rc = load_chou_sw_tables()
+      if (rc /= 0) return
+      rc = geosrad_sw_driver_chou_na_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(lm,c_int), fin, consts, int(lcldmh,c_int), &
+            int(lcldlm,c_int), hk_uv_temp, hk_ir_temp, merge(1_c_int, 0_c_int, do_drfband), fout, nout)
+   end subroutine
+   subroutine sw_driver_chou_na_lit(ncol, NumLit, d_idx, d_pos, lm, fin, consts, lcldmh, lcldlm, hk_uv_temp, hk_ir_temp, do_drfband, dark, &
+         keep, fout, dark_na, keep_na, nout, rc)
+      integer, intent(in) :: ncol, NumLit, lm, lcldmh, lcldlm
+      type(c_ptr), intent(in) :: d_idx, d_pos
+      type(c_ptr), intent(in) :: fin(SWC_NIN), fout(SWC_NOUT), nout(SWCNA_NOUT)
+      real(c_double), intent(in) :: consts(SWC_NCONST)
+      real, intent(in) :: hk_uv_temp(5), hk_ir_temp(3,10)
+      logical, intent(in) :: do_drfband
+      real, intent(in) :: dark(:), dark_na(SWCNA_NOUT)
+      logical, intent(in) :: keep(:), keep_na(SWCNA_NOUT)
+      integer, intent(out) :: rc
+      if (size(dark) /= SWC_NOUT .or. size(keep) /= SWC_NOUT) error stop 'sw_driver_chou_na_lit: dark and keep have SWC_NOUT entries'
+      rc = load_chou_sw_tables()
+      if (rc /= 0) return
+      rc = geosrad_sw_driver_chou_na_lit_dev(geosrad_ctx_handle(), c_null_ptr, int(ncol,c_int), int(NumLit,c_int), d_idx, d_pos, &
+            int(lm,c_int), fin, consts, int(lcldmh,c_int), int(lcldlm,c_int), hk_uv_temp, hk_ir_temp, merge(1_c_int, 0_c_int, do_drfband), &
+            real(dark,c_double), keep_mask(keep), fout, real(dark_na,c_double), int(keep_mask(keep_na),c_int), nout)
    end subroutine
    ! bit k - 1 of the mask = keep(k)
    pure function keep_mask(keep) result(m)

@@ -45,6 +45,10 @@ SWC_IN = ["PLE", "T", "Q", "OX", "CL", "QI", "QL", "QR", "QS", "RI", "RL", "RR",
           "ALBNR", "ALBNF"]
 SWC_CONST = ["CO2", "O3MW", "AIRMW", "UNDEF"]
 SWC_OUT = ["FSW", "FSC", "FSWU", "FSCU", "NIRR", "NIRF", "PARR", "PARF", "UVRR", "UVRF", "FSWBAND", "DRBAND", "DFBAND"]
+# aerosol-free twins from the same call: geosrad_sorad_na[_dev] (GEOSRAD_SONA_*) and geosrad_sw_driver_chou_na[_lit]_dev (GEOSRAD_SWCNA_*;
+# the internals FSWNAN, FSCNAN, FSWUNAN, FSCUNAN, FSWBANDNAN of SOL:3997-4016)
+SONA_OUT = ["flx_na", "flc_na", "flxu_na", "flcu_na", "flx_sfc_band_na"]
+SWCNA_OUT = ["FSWNA", "FSCNA", "FSWUNA", "FSCUNA", "FSWBANDNA"]
 
 LWU_IN = ["TSINST", "TS_INT", "SFCEM_INT", "FCLD", "FLX_INT", "FLXA_INT", "FLC_INT", "FLA_INT", "FLXU_INT", "FLXAU_INT", "FLCU_INT",
           "FLAU_INT", "FLXD_INT", "FLXAD_INT", "FLCD_INT", "FLAD_INT", "DFDTS", "DFDTSNA", "DFDTSC", "DFDTSCNA"]

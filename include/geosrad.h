@@ -12,6 +12,7 @@
  *   geosrad_set_tables_sw         <- rrtmg_sw_init::rrtmg_sw_ini           .../src/rrtmg_sw_init.F90:23
  *   geosrad_irrad[_dev]           <- irradmod::irrad                       GEOSirrad_GridComp/irrad.F90:27-35
  *   geosrad_sorad[_dev]           <- soradmod::sorad                       GEOSsolar_GridComp/sorad.F90:43-51
+ *   geosrad_sorad_na[_dev]        <- the same + its aerosol-free fluxes    GEOS_SolarGridComp.F90:3249-3259, :3997-4016
  *   geosrad_set_tables_chou_sw    <- sorad_constants / rad_constants (data modules)  GEOSsolar_GridComp/soradconstants.F90
  *   geosrad_set_tables_chou_lw    <- irrad_constants / rad_constants (data modules)  GEOSirrad_GridComp/irradconstants.F90
  *   geosrad_mcica[_dev]           <- cloud_subcol_gen::generate_stochastic_clouds
@@ -355,6 +356,34 @@ int geosrad_sorad_dev(geosrad_ctx *ctx, void *stream, int m, int np, int nb, con
                       void *flx, void *flc, void *fdiruv, void *fdifuv, void *fdirpar, void *fdifpar, void *fdirir, void *fdifir,
                       void *flxu, void *flcu, void *flx_sfc_band, int do_drfband, void *drband, void *dfband);
 
+/* geosrad_sorad_na / geosrad_sorad_na_dev: geosrad_sorad / geosrad_sorad_dev (the same arguments in the same order) + the aerosol-free
+ * fluxes of the same columns from the same call.  The Solar GridComp obtains its aerosol-free internals FSWNAN, FSCNAN, FSWUNAN, FSCUNAN,
+ * FSWBANDNAN by running the whole of SORADCORE a second time with include_aerosols = .false. (GEOS_SolarGridComp.F90:3249-3259 the second
+ * call, :3997-4016 the internals it fills - never DRBANDN / DFBANDN -, :4541-4551 the zero aerosol arrays the Chou-Suarez branch then hands
+ * sorad).  Here the preparation (classes, partition, absorber amounts, cloud optics) runs once, and after the with-aerosol spectral
+ * passes, sum and reduction the 35 passes run once more with no aerosol (nothing is read from taua / ssaa / asya), followed by their own
+ * sum and reduction.
+ *   na_out: HOST array of GEOSRAD_SONA_NOUT pointers (host arrays for geosrad_sorad_na, device arrays for geosrad_sorad_na_dev), indexed
+ *   by GEOSRAD_SONA_*: the twins of flx, flc, flxu, flcu (m,np+1) and of flx_sfc_band (m,8).  Each is bit for bit what geosrad_sorad[_dev]
+ *   returns in its twin for the same columns with three aerosol arrays of zeros.  Any member may be NULL: it is left untouched.  na_out
+ *   NULL, or all its members NULL: the plain call, no second pass runs.
+ * The 13 regular outputs are bit for bit those of geosrad_sorad[_dev]; the aerosol-free pass has no direct / diffuse components and no
+ * drband / dfband (do_drfband keeps its meaning for the with-aerosol pass).  The workspace is that of the plain call (the second pass reuses
+ * it) plus the place of every member of na_out that is NULL.  Errors as geosrad_sorad[_dev], nothing launched. */
+enum { GEOSRAD_SONA_FLX, GEOSRAD_SONA_FLC, GEOSRAD_SONA_FLXU, GEOSRAD_SONA_FLCU, GEOSRAD_SONA_SFCBAND /*(m,8)*/, GEOSRAD_SONA_NOUT };
+int geosrad_sorad_na(geosrad_ctx *ctx, int m, int np, int nb, const void *cosz, const void *pl, const void *ta, const void *wa,
+                     const void *oa, double co2, const void *cwc, const void *fcld, int ict, int icb, const void *reff,
+                     const void *hk_uv, const void *hk_ir, const void *taua, const void *ssaa, const void *asya,
+                     const void *rsuvbm, const void *rsuvdf, const void *rsirbm, const void *rsirdf,
+                     void *flx, void *flc, void *fdiruv, void *fdifuv, void *fdirpar, void *fdifpar, void *fdirir, void *fdifir,
+                     void *flxu, void *flcu, void *flx_sfc_band, int do_drfband, void *drband, void *dfband, void *const *na_out);
+int geosrad_sorad_na_dev(geosrad_ctx *ctx, void *stream, int m, int np, int nb, const void *cosz, const void *pl, const void *ta,
+                         const void *wa, const void *oa, double co2, const void *cwc, const void *fcld, int ict, int icb,
+                         const void *reff, const void *hk_uv, const void *hk_ir, const void *taua, const void *ssaa, const void *asya,
+                         const void *rsuvbm, const void *rsuvdf, const void *rsirbm, const void *rsirdf,
+                         void *flx, void *flc, void *fdiruv, void *fdifuv, void *fdirpar, void *fdifpar, void *fdirir, void *fdifir,
+                         void *flxu, void *flcu, void *flx_sfc_band, int do_drfband, void *drband, void *dfband, void *const *na_out);
+
 /* ---- McICA ------------------------------------------------------------------------------------------
  * generate_stochastic_clouds (cloud_subcol_gen.F90:132): profile inputs Fortran (nlay,dncol) there; here
  * the solver-API layout (ncol,nlay) is used for the inputs (what rrtmg_lw receives), outputs are
@@ -559,6 +588,20 @@ enum { GEOSRAD_SWC_FSW, GEOSRAD_SWC_FSC, GEOSRAD_SWC_FSWU, GEOSRAD_SWC_FSCU, GEO
 int geosrad_sw_driver_chou_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm, const void *const *in, const double *consts,
                                int lcldmh, int lcldlm, const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out);
 
+/* geosrad_sw_driver_chou_na_dev: geosrad_sw_driver_chou_dev + the aerosol-free internals FSWNAN, FSCNAN, FSWUNAN, FSCUNAN, FSWBANDNAN the
+ * GridComp obtains from a second SORADCORE with include_aerosols = .false. (GEOS_SolarGridComp.F90:3249-3259, :3997-4016, :4541-4551),
+ * from one k_swc_prep and one shared solver call (geosrad_sorad_na_dev).
+ *   na_out: HOST array of GEOSRAD_SWCNA_NOUT device pointers: FSWNA, FSCNA, FSWUNA, FSCUNA (ncol,LM+1), FSWBANDNA (ncol,8), each bit for
+ *   bit the FSW, FSC, FSWU, FSCU, FSWBAND of geosrad_sw_driver_chou_dev called with TAUA = SSAA = ASYA = NULL.  Any member may be NULL
+ *   (left untouched); na_out NULL or all members NULL: the plain driver.
+ * With the aerosol inputs NULL no second pass runs: the aerosol-free outputs are copies of their twins in `out`.  DRBAND / DFBAND keep their
+ * do_drfband meaning and are never produced by the aerosol-free pass (:4010-4016).  `out` is bit for bit the plain driver's. */
+enum { GEOSRAD_SWCNA_FSWNA, GEOSRAD_SWCNA_FSCNA, GEOSRAD_SWCNA_FSWUNA, GEOSRAD_SWCNA_FSCUNA, GEOSRAD_SWCNA_FSWBANDNA /*(ncol,8)*/,
+       GEOSRAD_SWCNA_NOUT };
+int geosrad_sw_driver_chou_na_dev(geosrad_ctx *ctx, void *stream, int ncol, int lm, const void *const *in, const double *consts,
+                                  int lcldmh, int lcldlm, const void *hk_uv, const void *hk_ir, int do_drfband, void *const *out,
+                                  void *const *na_out);
+
 /* geosrad_lw_update_flx_dev: Update_Flx (GEOS_IrradGridComp.F90:3796-3999), the per-model-step linearisation of the LW fluxes in
  * the surface temperature.  rrtmg != 0: the no-aerosol flavours are `undef` and their internals may be NULL (IRR:3927-3990).
  * rrtmg = 0 reads FLXA_INT .. DFDTSCNA as real fields (the Chou-Suarez semantics): what an RRTMG caller passes who has filled them with
@@ -745,6 +788,17 @@ int geosrad_sw_driver_chou_lit_dev(geosrad_ctx *ctx, void *stream, int ncol, int
                                    int lm, const void *const *in, const double *consts, int lcldmh, int lcldlm, const void *hk_uv,
                                    const void *hk_ir, int do_drfband, const double *dark /*[GEOSRAD_SWC_NOUT]*/, uint64_t keep_mask,
                                    void *const *out);
+
+/* geosrad_sw_driver_chou_na_lit_dev: geosrad_sw_driver_chou_lit_dev + the aerosol-free internals of geosrad_sw_driver_chou_na_dev on the
+ * un-packed tile.  na_out (GEOSRAD_SWCNA_* order) are fields of the whole tile like `out`; on a lit column each is bit for bit what the
+ * pack / geosrad_sw_driver_chou_na_dev / unpack route gives, and they ride the same un-packing kernel as `out`.  On a dark column
+ * na_out[k] receives dark_na[k] (host array [GEOSRAD_SWCNA_NOUT]: UnPackIt's DEFAULT of FSWNAN ..., :6534) unless bit k of keep_na is
+ * set.  nlit == 0: the dark values of `out` and na_out are written and nothing else runs.  GEOSRAD_EINVAL, nothing launched: what
+ * geosrad_sw_driver_chou_lit_dev rejects; lit_pos or dark_na NULL while a requested (non-NULL) member of na_out has its keep bit clear. */
+int geosrad_sw_driver_chou_na_lit_dev(geosrad_ctx *ctx, void *stream, int ncol, int nlit, const int32_t *lit_index, const int32_t *lit_pos,
+                                      int lm, const void *const *in, const double *consts, int lcldmh, int lcldlm, const void *hk_uv,
+                                      const void *hk_ir, int do_drfband, const double *dark /*[GEOSRAD_SWC_NOUT]*/, uint64_t keep_mask,
+                                      void *const *out, const double *dark_na /*[GEOSRAD_SWCNA_NOUT]*/, int keep_na, void *const *na_out);
 
 /* geosrad_sw_driver_rrtmg_obio_dev / geosrad_sw_driver_rrtmg_obio_lit_dev: geosrad_sw_driver_rrtmg_dev / geosrad_sw_driver_rrtmg_lit_dev
  * with the per-band surface beam and diffuse fluxes a coupled ocean biology needs, the internals DRBANDN / DFBANDN
