@@ -4,13 +4,16 @@ The product has no CPU path: if libgeosrad.so cannot be loaded, or no HIP device
 here raises.  (oracle/ is test infrastructure and is never imported from this package.)
 """
 import ctypes
+import functools
 import os
+import re
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.environ.get("GEOSRAD_LIB") or os.path.join(CSRC, "libgeosrad.so")   # override only for A/B kernel experiments
 DATA = os.path.join(HERE, "data")
+HEADER = os.path.join(os.path.dirname(HERE), "include", "geosrad.h")    # the one statement of every entry point's argument order and types
 
 EXPORTS = [
     "geosrad_create", "geosrad_create_multi", "geosrad_pick_device", "geosrad_destroy", "geosrad_last_error", "geosrad_real_kind", "geosrad_set_chunk",
@@ -38,10 +41,9 @@ def build(force=False):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU).  Objects (compiled in parallel, each rebuilt only when one of
     the files it includes is newer): geosrad.hip three times - fp32 kernels, fp64 kernels, the extern "C" layer - and lw_cols.hip (the
     on-chip RRTMG_LW band sweeps) and sw_reform.hip (the default RRTMG_SW band sweeps) twice each - fp32, fp64."""
-    inc = os.path.join(os.path.dirname(HERE), "include", "geosrad.h")
     hpp = {f: os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")}
     cols_only = {"lw_cols_kernels.hpp", "sw_reform_kernels.hpp", "lw_split_kernels.hpp"}      # headers geosrad.hip does not include
-    deps_main = [os.path.join(CSRC, "geosrad.hip"), inc] + [p for f, p in hpp.items() if f not in cols_only]
+    deps_main = [os.path.join(CSRC, "geosrad.hip"), HEADER] + [p for f, p in hpp.items() if f not in cols_only]
     deps_cols = [os.path.join(CSRC, "lw_cols.hip")] + [hpp[f] for f in ("lw_cols_kernels.hpp", "lw_cols.hpp", "lw_kernels.hpp", "lw_device.hpp")]
     deps_split = [os.path.join(CSRC, "lw_split.hip")] + [hpp[f] for f in ("lw_split_kernels.hpp", "lw_split.hpp", "lw_kernels.hpp", "lw_device.hpp")]
     deps_swq = [os.path.join(CSRC, "sw_reform.hip")] + [hpp[f] for f in ("sw_reform_kernels.hpp", "sw_reform.hpp", "sw_kernels.hpp", "lw_kernels.hpp", "lw_device.hpp")]
@@ -69,12 +71,52 @@ def build(force=False):
     return SO
 
 
+_CTYPES = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "uint64_t": ctypes.c_uint64, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+
+
+def parse_header(text):
+    """{name: (restype, [(ctype, parameter name), ...])} of every `type geosrad_x(args);` in the text of include/geosrad.h.  A pointer or
+    array is c_void_p (`const char *`: c_char_p), the rest as _CTYPES says; a parameter without a name or of another type raises TypeError."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*|^[ \t]*#[^\n]*", "", text, flags=re.S | re.M)            # comments, preprocessor lines
+
+    def ctype(fn, decl):            # decl: a type with its `*` and `[n]`, without the name
+        decl = " ".join(decl.replace("*", " * ").split())
+        if "*" in decl or "[" in decl:
+            return ctypes.c_char_p if decl == "const char *" else ctypes.c_void_p
+        if decl not in _CTYPES:
+            raise TypeError(f"{fn}: no ctypes type for `{decl}`")
+        return _CTYPES[decl]
+
+    protos = {}
+    for ret, fn, args in re.findall(r"([\w \t*]+?)\b(geosrad_\w+)\s*\(([^;{}()]*)\)\s*;", text):
+        params = []
+        for arg in args.split(","):
+            m = re.fullmatch(r"(.*[\s*])(\w+)\s*((?:\[\w*\])?)\s*", arg, flags=re.S)
+            if not m or not m.group(1).strip():
+                raise TypeError(f"{fn}: parameter `{arg.strip()}` has no name")
+            params.append((ctype(fn, m.group(1) + m.group(3)), m.group(2)))
+        protos[fn] = (ctype(fn, ret), params)
+    return protos
+
+
+@functools.lru_cache(maxsize=None)
+def prototypes():
+    """parse_header of include/geosrad.h, read once; its names are those of EXPORTS"""
+    if not os.path.exists(HEADER):
+        raise RuntimeError(f"{HEADER} is missing: the binding takes every entry point's argument order and types from it")
+    protos = parse_header(open(HEADER).read())
+    if set(protos) != set(EXPORTS):
+        raise RuntimeError(f"{HEADER} and _lib.EXPORTS differ: {sorted(set(protos) ^ set(EXPORTS))}")
+    return protos
+
+
 def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(SO):
             raise RuntimeError(f"{SO} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(there is no CPU fallback)")
+        protos = prototypes()
         # PyTorch ships its own copy of the HIP runtime; when it is going to be used in this process (device tensors and streams
         # handed to the `_dev` entry points) it has to be the one this library binds to, so it is loaded first.
         try:
@@ -82,15 +124,8 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(SO)
-        L.geosrad_last_error.restype = ctypes.c_char_p
-        L.geosrad_last_error.argtypes = [ctypes.c_void_p]
-        L.geosrad_workspace_bytes.restype = ctypes.c_size_t
-        L.geosrad_workspace_bytes.argtypes = [ctypes.c_void_p]
-        L.geosrad_kernel_name.restype = ctypes.c_char_p
-        L.geosrad_kernel_label.restype = ctypes.c_char_p
-        L.geosrad_kernel_label.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.geosrad_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int]
-        L.geosrad_create_multi.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int]
-        L.geosrad_pick_device.argtypes = [ctypes.c_int]
+        for name, (restype, params) in protos.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, [t for t, _ in params]
         _lib = L
     return _lib
