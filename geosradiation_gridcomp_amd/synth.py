@@ -42,11 +42,17 @@ def _n(seed, col, stream, n=1):
     return np.sqrt(-2.0 * np.log(1.0 - u1)) * np.cos(2.0 * np.pi * u2)
 
 
-def make_columns(ncol, nlay=72, seed=SEED, start=0, cloudy_frac=0.0, aerosol=False, lit=True):
+def make_columns(ncol, nlay=72, seed=SEED, start=0, cloudy_frac=0.0, aerosol=False, lit=True, emis_bands=False, distinct_albedos=False):
     """Return a dict of float32/int32 arrays (C-order, column index fastest).
 
-    cloudy_frac : fraction of columns that get 1-3 cloud decks (SURVEY 8(d) cfg 3/4)
-    aerosol     : fill tauaer (LW absorption tau) / SW tau, ssa, g per band
+    cloudy_frac      : fraction of columns that get 1-3 cloud decks (SURVEY 8(d) cfg 3/4)
+    aerosol          : fill tauaer (LW absorption tau) / SW tau, ssa, g per band
+    emis_bands       : emis[b, col] ~ U(0.80, 1.00) independently per LW band and column (default: 0.98 in every band), so that a
+                       wrong band row of the surface emission / reflection (rrtmg_lw_rtrnmc.F90:319-333) changes every column
+    distinct_albedos : asdir, aldif, asdif, aldir drawn independently per column from the pairwise disjoint ranges [0.03, 0.12],
+                       [0.15, 0.28], [0.35, 0.55], [0.62, 0.80] (default: asdir == asdif, aldir == aldif), so that any swap of two of
+                       the four changes every column
+    The defaults leave every array bit-identical to what the generator returned before these switches existed.
     """
     col = np.arange(start, start + ncol)
     f32 = np.float32
@@ -89,6 +95,8 @@ def make_columns(ncol, nlay=72, seed=SEED, start=0, cloudy_frac=0.0, aerosol=Fal
         cfc22vmr=(2e-10 * ones).astype(f32), ccl4vmr=(1.105e-10 * ones).astype(f32),
         emis=np.full((NBNDLW, ncol), 0.98, dtype=f32),
     )
+    if emis_bands:
+        out["emis"] = (0.80 + 0.20 * _u(seed, col, 400, NBNDLW)).astype(f32)
 
     # ---- mid-layer heights (IRR:3343-3351): ZM(1)=0, dz = R T/g * dp/p -----------------------------
     rgas, grav = 287.04, 9.80665
@@ -143,6 +151,9 @@ def make_columns(ncol, nlay=72, seed=SEED, start=0, cloudy_frac=0.0, aerosol=Fal
     a_vis = 0.05 + 0.25 * _u(seed, col, 200)[0]
     a_nir = 0.10 + 0.40 * _u(seed, col, 201)[0]
     out.update(asdir=a_vis.astype(f32), asdif=a_vis.astype(f32), aldir=a_nir.astype(f32), aldif=a_nir.astype(f32))
+    if distinct_albedos:
+        out.update(asdir=(0.03 + 0.09 * _u(seed, col, 410)[0]).astype(f32), aldif=(0.15 + 0.13 * _u(seed, col, 411)[0]).astype(f32),
+                   asdif=(0.35 + 0.20 * _u(seed, col, 412)[0]).astype(f32), aldir=(0.62 + 0.18 * _u(seed, col, 413)[0]).astype(f32))
     cz = 0.05 + 0.95 * _u(seed, col, 202)[0]
     out["coszen"] = cz.astype(f32) if lit else np.where(_u(seed, col, 203)[0] < 0.5, cz, 0.0).astype(f32)
     if aerosol:
@@ -162,11 +173,46 @@ def make_columns(ncol, nlay=72, seed=SEED, start=0, cloudy_frac=0.0, aerosol=Fal
     return out
 
 
-def chou_lw_inputs(inp, aerosol=False):
+def _tiled_surface(tsfc, ns, vegetated):
+    """ns, fs, tg, tv, eg, ev, rv of a tiled irrad surface (see chou_lw_inputs).  The counter of the hash is the bit pattern of the
+    column's surface temperature (the inputs carry neither seed nor column number), so a column keeps its tiling in any batch."""
+    f32 = np.float32
+    m = tsfc.shape[0]
+    col = np.ascontiguousarray(tsfc, dtype=f32).view(np.uint32).astype(np.int64)
+    # fractions: ns positive integers that sum to 64 (cut points drawn one after the other from what is left)
+    left = np.full(m, 64, dtype=np.int64)
+    parts = np.zeros((ns, m), dtype=np.int64)
+    for s in range(ns - 1):
+        room = left - (ns - 1 - s)                                   # every later sub-surface keeps at least 1/64
+        parts[s] = 1 + np.floor(_u(SEED, col, 420 + s)[0] * room).astype(np.int64)
+        left -= parts[s]
+    parts[ns - 1] = left
+    assert (parts >= 1).all() and (parts.sum(axis=0) == 64).all()
+    tsf = tsfc.astype(np.float64)[None, :]
+    tg = tsf - 5.0 + 10.0 * _u(SEED, col, 430, ns)
+    dtv = 0.5 + 2.0 * _u(SEED, col, 431, ns)                          # |tv - tg| in [0.5, 2.5] K, towards tsfc: stays within 5 K
+    tv = np.where(tg > tsf, tg - dtv, tg + dtv)
+    eg = 0.8 + 0.2 * _u(SEED, col, 432, 10 * ns).reshape(10, ns, m)
+    ev = np.zeros((10, ns, m)); rv = np.zeros((10, ns, m))
+    if vegetated:
+        ev[:, 0] = 0.2 + 0.4 * _u(SEED, col, 433, 10)
+        rv[:, 0] = 0.02 + 0.18 * _u(SEED, col, 434, 10)
+    return dict(ns=ns, fs=(parts / 64.0).astype(f32), tg=tg.astype(f32), tv=tv.astype(f32), eg=eg.astype(f32), ev=ev.astype(f32),
+                rv=rv.astype(f32))
+
+
+def chou_lw_inputs(inp, aerosol=False, ns=1, vegetated=False):
     """Inputs of the Chou-Suarez `irrad` for the columns of `make_columns` (the unit conversions and the vertical flip that
     GEOS_IrradGridComp does before the call, GEOS_IrradGridComp.F90:1870-2101): layers from the TOP down, pressure in Pa,
     specific humidity, O3 mass mixing ratio, hydrometeor mixing ratios of the 4 species (ice, liquid, rain, snow).
-    Arrays are numpy C-order with the reversed Fortran shape, e.g. ple (np+1, m), cwc (4, np, m), eg (10, ns, m)."""
+    Arrays are numpy C-order with the reversed Fortran shape, e.g. ple (np+1, m), cwc (4, np, m), eg (10, ns, m).
+
+    ns > 1 or vegetated: a tiled surface for `sfcflux` (irrad.F90:2653-2720) instead of GEOS's single bare one.  `ns` sub-surfaces
+    whose fractions `fs` are multiples of 1/64 (exact in fp32) and sum to exactly 1; per sub-surface a ground temperature `tg` and a
+    vegetation temperature `tv` within 5 K of tsfc with tv != tg; ground emissivity eg ~ U(0.8, 1.0) per band.  With `vegetated`, the
+    first sub-surface has ev ~ U(0.2, 0.6) and rv ~ U(0.02, 0.2), both above sfcflux's 1e-4 threshold, and the others stay bare:
+    sfcflux chooses its arm by the first sub-surface, so its vegetated loop then also walks bare sub-surfaces (ev = rv = 0); with
+    ns > 1 and not `vegetated` its bare loop runs.  The defaults return the same bits as before."""
     f32 = np.float32
     nlay, m = inp["play"].shape
     flip = lambda a: np.ascontiguousarray(a[::-1])
@@ -199,6 +245,8 @@ def chou_lw_inputs(inp, aerosol=False):
     out["ev"] = np.zeros((10, 1, m), dtype=f32)
     out["rv"] = np.zeros((10, 1, m), dtype=f32)
     out["nb"] = 10
+    if ns != 1 or vegetated:
+        out.update(_tiled_surface(inp["tsfc"], ns, vegetated))
     if aerosol and "tauaer_sw" in inp:
         tau = inp["tauaer_sw"][:10, ::-1].astype(np.float64)
         ssa = inp["ssaaer_sw"][:10, ::-1].astype(np.float64)

@@ -174,6 +174,25 @@ def main_iceflags():
     print("lw_iceflags_72", os.path.getsize(os.path.join(HERE, "lw_iceflags_72.npz")))
 
 
+# rtrnmc's per-band surface emission and reflection (rrtmg_lw_rtrnmc.F90:319-333): a different emissivity in every band and column
+# (every other case carries 0.98 throughout, which cannot tell one band row from another).  Fluxes and band outputs only: the
+# McICA and taumol intermediates do not depend on emis and the other files hold them.
+EMIS_KW = dict(ncol=16, nlay=72, aerosol=True, cloudy_frac=0.8, start=8800, emis_bands=True)
+
+
+def main_emis():
+    inp = synth.make_columns(**EMIS_KW)
+    out = {"kw_json": np.array(repr(EMIS_KW)), "ih": np.int32(1)}
+    for kind in ("r4", "r8"):
+        reflib.set_inhomogeneity(1, kind)
+        r = reflib.rrtmg_lw(inp, kind, band_output=np.ones(16, dtype=np.int32))
+        reflib.set_inhomogeneity(0, kind)
+        for k in FLUX + ("clearCounts", "olrb", "dolrb_dTs"):
+            out[f"{kind}_{k}"] = r[k]
+    np.savez_compressed(os.path.join(HERE, "lw_emis_bands_72.npz"), **out)
+    print("lw_emis_bands_72", os.path.getsize(os.path.join(HERE, "lw_emis_bands_72.npz")))
+
+
 def main():
     for name, (kw, ih, bo) in CASES.items():
         inp = synth.make_columns(**kw)
@@ -210,6 +229,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if "nrlssi2" in sys.argv[1:]:
         main_nrlssi2()
+        sys.exit(0)
+    if "emis" in sys.argv[1:]:
+        main_emis()
         sys.exit(0)
     if "sw" not in sys.argv[1:]:
         main()

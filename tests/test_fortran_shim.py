@@ -13,7 +13,7 @@ ORDER = ["play", "plev", "tlay", "tlev", "tsfc", "emis", "h2ovmr", "o3vmr", "co2
          "cfc12vmr", "cfc22vmr", "ccl4vmr", "cldf", "ciwp", "clwp", "rei", "rel", "tauaer", "zm", "alat"]
 
 
-@pytest.mark.parametrize("name", ["lw_aer_72", "lw_cloudy_ih1_72"])
+@pytest.mark.parametrize("name", ["lw_aer_72", "lw_cloudy_ih1_72", "lw_emis_bands_72"])
 @pytest.mark.parametrize("kind", ["r8", "r4"])
 def test_fortran_caller_gets_reference_fluxes(tmp_path, name, kind):
     exe = os.path.join(FDIR, "bin", f"lw_driver_{kind}")
@@ -52,7 +52,7 @@ def test_fortran_sw_caller_matches_oracle(tmp_path, kind):
     if not os.path.exists(exe):
         subprocess.check_call(["make", "-s", "-C", FDIR])
     ncol, nlay, ih = 40, 72, 1
-    inp = synth.make_columns(ncol, nlay, start=606, aerosol=True, cloudy_frac=0.6)
+    inp = synth.make_columns(ncol, nlay, start=606, aerosol=True, cloudy_frac=0.6, distinct_albedos=True)
     fin, fout = tmp_path / "in.bin", tmp_path / "out.bin"
 
     def run(isolvar, scon, solcycfrac=None):
@@ -182,7 +182,7 @@ def test_fortran_chou_caller_matches_oracle(tmp_path, kind):
     if not os.path.exists(exe):
         subprocess.check_call(["make", "-s", "-C", FDIR])
     m, nlay = 24, 72
-    inp = synth.make_columns(m, nlay, start=808, aerosol=True, cloudy_frac=0.6)
+    inp = synth.make_columns(m, nlay, start=808, aerosol=True, cloudy_frac=0.6, distinct_albedos=True)
     ch = synth.chou_lw_inputs(inp, aerosol=True)
     cs = synth.chou_sw_inputs(inp, aerosol=True)
     fin, fout = tmp_path / "in.bin", tmp_path / "out.bin"

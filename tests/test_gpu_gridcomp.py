@@ -95,7 +95,7 @@ def test_sw_driver_equals_oracle_prep_gpu_solver_oracle_post(gpu_ctx, rk):
     from oracle import clib
     ctx = gpu_ctx[rk]; dt = ctx.dtype; prec = PREC[rk]
     ncol, lm = 300, 72
-    inp = synth.make_columns(ncol, lm, start=5000, cloudy_frac=0.6, aerosol=True)
+    inp = synth.make_columns(ncol, lm, start=5000, cloudy_frac=0.6, aerosol=True, distinct_albedos=True)
     f = synth.geos_sw_fields(inp)
     consts = G.swd_consts()
     ctx.set_inhomogeneity(1)
@@ -210,7 +210,7 @@ def test_sw_driver_no_aerosol_flavour_shares_the_cloud_generator(gpu_ctx, rk):
     == a separate call of the driver without aerosols, which is what the GridComp does (GEOS_SolarGridComp.F90:3249-3259)"""
     ctx = gpu_ctx[rk]; dt = ctx.dtype
     ncol, lm = 200, 72
-    inp = synth.make_columns(ncol, lm, start=777, cloudy_frac=0.6, aerosol=True)
+    inp = synth.make_columns(ncol, lm, start=777, cloudy_frac=0.6, aerosol=True, distinct_albedos=True)
     f = synth.geos_sw_fields(inp)
     consts = G.swd_consts()
     ctx.set_inhomogeneity(1)
@@ -261,7 +261,7 @@ def test_sw_driver_no_aerosol_pass_through_ragged_chunks(gpu_ctx, sw_bands_ctx, 
     bits of the unchunked call, under either mapping of the band sweeps; and FSWBANDNA is FSWBAND of a call without aerosols"""
     ctx = (gpu_ctx if path == "reform" else sw_bands_ctx)[rk]; dt = ctx.dtype
     ncol, lm = 150, 72
-    inp = synth.make_columns(ncol, lm, start=2718, cloudy_frac=0.6, aerosol=True)
+    inp = synth.make_columns(ncol, lm, start=2718, cloudy_frac=0.6, aerosol=True, distinct_albedos=True)
     f = synth.geos_sw_fields(inp)
     consts = G.swd_consts()
     shapes = {k: (ncol,) for k in G.SWD_OUT}
@@ -576,7 +576,7 @@ def test_lit_column_compaction_roundtrip_and_sw_on_packed_columns(gpu_ctx, rk):
     ctx = gpu_ctx[rk]
     tdt = torch.float32 if rk == 4 else torch.float64
     n, nlay = 1500, 72
-    inp = synth.make_columns(n, nlay, start=12_000, aerosol=True, cloudy_frac=0.5)
+    inp = synth.make_columns(n, nlay, start=12_000, aerosol=True, cloudy_frac=0.5, distinct_albedos=True)
     rng = np.random.default_rng(3)
     day = rng.uniform(size=n) < 0.47
     zth = np.where(day, inp["coszen"], -rng.uniform(0.0, 1.0, n)).astype(ctx.dtype)      # night: cos(zenith) <= 0
@@ -646,7 +646,7 @@ def test_chou_branch_of_soradcore(gpu_ctx, rk, aer):
     import torch
     from oracle import clib
     ctx = gpu_ctx[rk]; prec = PREC[rk]; dt = np.float32 if rk == 4 else np.float64
-    inp = synth.make_columns(300, 72, start=8080, cloudy_frac=0.6, aerosol=True)
+    inp = synth.make_columns(300, 72, start=8080, cloudy_frac=0.6, aerosol=True, distinct_albedos=True)
     f = synth.geos_chou_sw_fields(inp, aerosol=aer)
     assert (f["PLE"][:3] < 100.0).all()                       # the odd-oxygen scaling above 1 hPa is exercised
     lm, m = f["T"].shape

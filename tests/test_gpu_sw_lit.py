@@ -107,7 +107,7 @@ class Tile:
 # ---- RRTMG ---------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def swd_case():
-    inp = synth.make_columns(N, LM, start=31_000, cloudy_frac=0.6, aerosol=True)
+    inp = synth.make_columns(N, LM, start=31_000, cloudy_frac=0.6, aerosol=True, distinct_albedos=True)
     f = synth.geos_sw_fields(inp)
     zth, day = make_zth(f["ZT"])
     f["ZT"] = zth.copy()
@@ -278,7 +278,7 @@ def test_rrtmg_no_lit_column(gpu_ctx, swd_case, rk):
 # ---- Chou-Suarez ---------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def swc_case():
-    inp = synth.make_columns(N, LM, start=47_000, cloudy_frac=0.6, aerosol=True)
+    inp = synth.make_columns(N, LM, start=47_000, cloudy_frac=0.6, aerosol=True, distinct_albedos=True)
     f = synth.geos_chou_sw_fields(inp, aerosol=True)
     zth, day = make_zth(f["ZT"], seed=12)
     f["ZT"] = zth.copy()
