@@ -14,6 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 SO = os.environ.get("GEOSRAD_LIB") or os.path.join(CSRC, "libgeosrad.so")   # override only for A/B kernel experiments
 DATA = os.path.join(HERE, "data")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "geosrad.h")    # the one statement of every entry point's argument order and types
+HEADER_GETTAU = os.path.join(os.path.dirname(HERE), "include", "geosrad_gettau.h")      # gettau.F90 as batched entry points: a second public header
 
 EXPORTS = [
     "geosrad_create", "geosrad_create_multi", "geosrad_pick_device", "geosrad_destroy", "geosrad_last_error", "geosrad_real_kind", "geosrad_set_chunk",
@@ -34,16 +35,25 @@ EXPORTS = [
     "geosrad_sorad_na", "geosrad_sorad_na_dev", "geosrad_sw_driver_chou_na_dev", "geosrad_sw_driver_chou_na_lit_dev",
 ]
 
+# the entry points of include/geosrad_gettau.h
+EXPORTS_GETTAU = [
+    "geosrad_getvistau", "geosrad_getvistau_dev", "geosrad_getnirtau", "geosrad_getnirtau_dev", "geosrad_getirtau", "geosrad_getirtau_dev",
+    "geosrad_lw_cloud_diag_dev",
+]
+HEADERS = [(HEADER, EXPORTS), (HEADER_GETTAU, EXPORTS_GETTAU)]      # every public header with the names it must declare
+
 _lib = None
 
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU).  Objects (compiled in parallel, each rebuilt only when one of
-    the files it includes is newer): geosrad.hip three times - fp32 kernels, fp64 kernels, the extern "C" layer - and lw_cols.hip (the
+    the files it includes is newer): geosrad.hip three times - fp32 kernels, fp64 kernels, the extern "C" layer of both public headers; it
+    includes gettau_kernels.hpp like every solver's kernels - and lw_cols.hip (the
     on-chip RRTMG_LW band sweeps) and sw_reform.hip (the default RRTMG_SW band sweeps) twice each - fp32, fp64."""
     hpp = {f: os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")}
     cols_only = {"lw_cols_kernels.hpp", "sw_reform_kernels.hpp", "lw_split_kernels.hpp"}      # headers geosrad.hip does not include
-    deps_main = [os.path.join(CSRC, "geosrad.hip"), HEADER] + [p for f, p in hpp.items() if f not in cols_only]
+    # geosrad.hip includes both public headers and gettau_kernels.hpp (with every other .hpp but cols_only): an edit of either rebuilds it
+    deps_main = [os.path.join(CSRC, "geosrad.hip"), HEADER, HEADER_GETTAU] + [p for f, p in hpp.items() if f not in cols_only]
     deps_cols = [os.path.join(CSRC, "lw_cols.hip")] + [hpp[f] for f in ("lw_cols_kernels.hpp", "lw_cols.hpp", "lw_kernels.hpp", "lw_device.hpp")]
     deps_split = [os.path.join(CSRC, "lw_split.hip")] + [hpp[f] for f in ("lw_split_kernels.hpp", "lw_split.hpp", "lw_kernels.hpp", "lw_device.hpp")]
     deps_swq = [os.path.join(CSRC, "sw_reform.hip")] + [hpp[f] for f in ("sw_reform_kernels.hpp", "sw_reform.hpp", "sw_kernels.hpp", "lw_kernels.hpp", "lw_device.hpp")]
@@ -110,13 +120,27 @@ def prototypes():
     return protos
 
 
+@functools.lru_cache(maxsize=None)
+def all_prototypes():
+    """prototypes() plus the prototypes of every further header of HEADERS, each held to its own export list"""
+    protos = dict(prototypes())
+    for path, exports in HEADERS[1:]:
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} is missing: the binding takes every entry point's argument order and types from it")
+        more = parse_header(open(path).read())
+        if set(more) != set(exports):
+            raise RuntimeError(f"{path} and its export list differ: {sorted(set(more) ^ set(exports))}")
+        protos.update(more)
+    return protos
+
+
 def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(SO):
             raise RuntimeError(f"{SO} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(there is no CPU fallback)")
-        protos = prototypes()
+        protos = all_prototypes()
         # PyTorch ships its own copy of the HIP runtime; when it is going to be used in this process (device tensors and streams
         # handed to the `_dev` entry points) it has to be the one this library binds to, so it is loaded first.
         try:

@@ -63,7 +63,7 @@ class GeosradInputError(GeosradError):
 @functools.lru_cache(maxsize=None)
 def _params(name):
     """((parameter, int | float for a scalar, None for a pointer), ...) of the library function `name`, in the order of include/geosrad.h"""
-    return tuple((p, _SCALAR.get(t)) for t, p in _lib.prototypes()[name][1])
+    return tuple((p, _SCALAR.get(t)) for t, p in _lib.all_prototypes()[name][1])
 
 
 def _args(name, vals):
@@ -399,6 +399,56 @@ class Context:
     def irrad_dev(self, stream, m, np_, ptr, co2, trace, ict, icb, ns, na, nb):
         """`ptr`: dict name -> device address for every array argument of irrad (inputs, in-out aerosols, outputs)."""
         self._dev("geosrad_irrad_dev", ptr, stream=stream, m=m, np=np_, co2=co2, trace=trace, ict=ict, icb=icb, ns=ns, na=na, nb=nb)
+
+    # ---- gettau (include/geosrad_gettau.h): the cloud optics of GEOS_RadiationShared/gettau.F90 over a batch of columns ---------
+    def _gettau_host(self, name, a, shapes, want):
+        """the host-array call `name`: `a` = the caller's arguments by parameter name, `shapes` = [(output, shape)] of which `want` are
+        allocated, passed and returned (the others go as NULL: neither computed nor written)"""
+        unknown = set(want) - {k for k, _ in shapes}
+        if unknown:
+            raise TypeError(f"{name}: no output {sorted(unknown)}")
+        out = self._zeros([(k, s) for k, s in shapes if k in want])
+        self._host(name, a, out)
+        return out
+
+    def getvistau(self, ncol, nlevs, cosz, dp, fcld, reff, hydromets, ict, icb, grav=G.MAPL["GRAV"], want=("taubeam", "taudiff", "asycl")):
+        """getvistau (gettau.F90:33) for ncol columns: cosz (ncol); dp [Pa], fcld (nlevs, ncol); reff [microns], hydromets [kg/kg]
+        (4, nlevs, ncol); ict = 0: in-cloud optical thicknesses, else scaled for the overlap of the super-layers split at ict / icb.
+        Returns dict(taubeam, taudiff (4, nlevs, ncol); asycl (nlevs, ncol)) of the names in `want`."""
+        a = locals()
+        return self._gettau_host("geosrad_getvistau", a, [("taubeam", (4, nlevs, ncol)), ("taudiff", (4, nlevs, ncol)), ("asycl", (nlevs, ncol))], want)
+
+    def getnirtau(self, ib, ncol, nlevs, cosz, dp, fcld, reff, hydromets, ict, icb, grav=G.MAPL["GRAV"],
+                  want=("taubeam", "taudiff", "asycl", "ssacl")):
+        """getnirtau (gettau.F90:102) for NIR band ib = 1..3: as getvistau, plus ssacl (nlevs, ncol)."""
+        a = locals()
+        return self._gettau_host("geosrad_getnirtau", a, [("taubeam", (4, nlevs, ncol)), ("taudiff", (4, nlevs, ncol)), ("asycl", (nlevs, ncol)),
+                                                        ("ssacl", (nlevs, ncol))], want)
+
+    def getirtau(self, ib, ncol, nlevs, dp, fcld, reff, hydromets, grav=G.MAPL["GRAV"], want=("taudiag", "tcldlyr", "enn")):
+        """getirtau (gettau.F90:173) for IR band ib = 1..10.  Returns dict(taudiag (4, nlevs, ncol); tcldlyr, enn (nlevs + 1, ncol), level
+        0 = 1 / 0) of the names in `want`."""
+        a = locals()
+        return self._gettau_host("geosrad_getirtau", a, [("taudiag", (4, nlevs, ncol)), ("tcldlyr", (nlevs + 1, ncol)), ("enn", (nlevs + 1, ncol))], want)
+
+    def getvistau_dev(self, stream, ncol, nlevs, ptr, ict, icb, grav=G.MAPL["GRAV"]):
+        """`ptr`: name -> device address of cosz, dp, fcld, reff, hydromets and of the wanted outputs taubeam, taudiff, asycl (missing = NULL)."""
+        self._dev("geosrad_getvistau_dev", ptr, stream=stream, ncol=ncol, nlevs=nlevs, ict=ict, icb=icb, grav=grav)
+
+    def getnirtau_dev(self, stream, ib, ncol, nlevs, ptr, ict, icb, grav=G.MAPL["GRAV"]):
+        """`ptr` as for getvistau_dev, plus ssacl."""
+        self._dev("geosrad_getnirtau_dev", ptr, stream=stream, ib=ib, ncol=ncol, nlevs=nlevs, ict=ict, icb=icb, grav=grav)
+
+    def getirtau_dev(self, stream, ib, ncol, nlevs, ptr, grav=G.MAPL["GRAV"]):
+        """`ptr`: name -> device address of dp, fcld, reff, hydromets and of the wanted outputs taudiag, tcldlyr, enn (missing = NULL)."""
+        self._dev("geosrad_getirtau_dev", ptr, stream=stream, ib=ib, ncol=ncol, nlevs=nlevs, grav=grav)
+
+    def lw_cloud_diag_dev(self, stream, ncol, lm, ptr, taucrit=0.30, grav=G.MAPL["GRAV"], undef=G.MAPL["UNDEF"]):
+        """TAUIR / CLDTMP / CLDPRS of LW_Driver for any LW scheme (GEOS_IrradGridComp.F90:1898-1912, :3626-3650): `ptr` = name -> device
+        address of the GEOS fields PLE, T, FCLD, QI QL QR QS, RI RL RR RS (model ordering) and of the wanted exports TAUIR (lm, ncol), CLDTMP,
+        CLDPRS (ncol); taucrit = the TAUCRIT: resource of the Irrad GridComp."""
+        self._dev("geosrad_lw_cloud_diag_dev", ptr, {p: p.upper() for p, _ in _params("geosrad_lw_cloud_diag_dev")}, stream=stream, ncol=ncol, lm=lm,
+                  grav=grav, undef=undef, taucrit=taucrit)
 
     # ---- Chou-Suarez SW, host arrays ---------------------------------------------------------------------
     def sorad(self, m, np_, nb, cosz, pl, ta, wa, oa, co2, cwc, fcld, ict, icb, reff, hk_uv, hk_ir, taua, ssaa, asya,

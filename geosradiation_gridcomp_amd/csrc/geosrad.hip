@@ -23,6 +23,7 @@
 #include <cstddef>
 #include <cstdint>
 #include "../../include/geosrad.h"
+#include "../../include/geosrad_gettau.h"
 #include "dev_buf.hpp"
 #include "lw_device.hpp"
 #include "lw_kernels.hpp"
@@ -32,6 +33,7 @@
 #include "chou_kernels.hpp"
 #include "sorad_kernels.hpp"
 #include "gridcomp_kernels.hpp"
+#include "gettau_kernels.hpp"
 #include "lw_cols.hpp"
 #include "lw_split.hpp"
 #include "sw_reform.hpp"
@@ -613,6 +615,32 @@ struct geosrad_ctx {
     virtual int lit_index_dev(hipStream_t, int, const void *, int32_t *, int32_t *, int32_t *, int *) { return nodev("geosrad_lit_index_dev"); }
     virtual int lit_pack_dev(hipStream_t, int, int, int, const int32_t *, const int32_t *, const void *, void *) { return nodev("geosrad_lit_pack_dev"); }
     virtual int lit_unpack_dev(hipStream_t, int, int, int, const int32_t *, const void *, void *, int, double) { return nodev("geosrad_lit_unpack_dev"); }
+    // gettau (include/geosrad_gettau.h): one record for the three routines, shared by the `_dev` and the host-pointer variant
+    struct GtCall {
+        int kind;                       // 0 getvistau, 1 getnirtau, 2 getirtau
+        int ib, ncol, nlevs, ict, icb;
+        double grav;
+        const void *cosz, *dp, *fcld, *reff, *hyd;
+        void *out[4];                   // taubeam, taudiff, asycl, ssacl | taudiag, tcldlyr, enn, -
+        const char *name() const { return kind == 0 ? "geosrad_getvistau" : kind == 1 ? "geosrad_getnirtau" : "geosrad_getirtau"; }
+    };
+    // the argument rules of include/geosrad_gettau.h, the same for every kind of context
+    int gettau_check(const GtCall &C)
+    {
+        const std::string who = C.name();
+        if (C.ncol <= 0 || C.nlevs < 1) return fail(GEOSRAD_EINVAL, who + ": ncol must be positive and nlevs at least 1");
+        if (C.kind == 1 && (C.ib < 1 || C.ib > 3)) return fail(GEOSRAD_EINVAL, who + ": ib must be in 1..3");
+        if (C.kind == 2 && (C.ib < 1 || C.ib > 10)) return fail(GEOSRAD_EINVAL, who + ": ib must be in 1..10");
+        if (C.kind != 2 && C.ict != 0 && !(1 <= C.ict && C.ict <= C.icb && C.icb <= C.nlevs + 1))
+            return fail(GEOSRAD_EINVAL, who + ": ict / icb must satisfy 1 <= ict <= icb <= nlevs + 1 (or ict = 0: the in-cloud mode)");
+        if (!C.out[0] && !C.out[1] && !C.out[2] && !C.out[3]) return fail(GEOSRAD_EINVAL, who + ": every output is NULL");
+        if (!C.dp || !C.fcld || !C.reff || !C.hyd) return fail(GEOSRAD_EINVAL, who + ": null input array");
+        if (C.kind != 2 && C.ict != 0 && C.out[0] && !C.cosz) return fail(GEOSRAD_EINVAL, who + ": taubeam of the overlap mode needs cosz");
+        return GEOSRAD_OK;
+    }
+    virtual int gettau_dev(hipStream_t, const GtCall &C) { return nodev(C.name()); }
+    virtual int gettau_host(const GtCall &C) = 0;
+    virtual int lw_cloud_diag_dev(hipStream_t, int, int, double, double, double, In, Out) { return nodev("geosrad_lw_cloud_diag_dev"); }
 };
 
 // order of the `in` / `out` pointer arrays of sw_dev / sw_host
@@ -681,6 +709,10 @@ static inline ArrShape so_out_shape(int k, size_t L)
 {
     return {(k == SOO_FLX || k == SOO_FLC || k == SOO_FLXU || k == SOO_FLCU) ? L + 1 : (k == SOO_SFCBAND || k == SOO_DRBAND || k == SOO_DFBAND) ? 8 : 1, 1};
 }
+
+// gettau: inputs cosz, dp, fcld, reff, hydromets; outputs of GtCall::out by kind
+static inline ArrShape gt_in_shape(int k, size_t L) { return {k == 0 ? 1 : k <= 2 ? L : 4 * L, 1}; }
+static inline ArrShape gt_out_shape(int kind, int k, size_t L) { return {kind == 2 ? (k == 0 ? 4 * L : L + 1) : (k <= 1 ? 4 * L : L), 1}; }
 
 // The arrays of one host-pointer call, added in host_pipeline's order (copied in only, both ways, back only).  src: copied in, dst:
 // copied back (null: the array only has its place on the device).  *at receives the array's device address before the solver is
@@ -2720,6 +2752,75 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 
+    // =====================================================================================================
+    // gettau (include/geosrad_gettau.h; gettau_kernels.hpp)
+    // =====================================================================================================
+    DevBuf<> d_ws_gt;      // (ncol,3) super-layer cloud maxima of the overlap mode
+    int gettau_dev(hipStream_t st, const GtCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = gettau_check(C)) return rc;
+        if (C.kind == 2 ? !have_chou : !have_sorad)
+            return fail(GEOSRAD_EINVAL, C.kind == 2 ? "Chou-Suarez LW tables not set: call geosrad_load_tables_chou_lw first"
+                                                    : "Chou-Suarez SW tables not set: call geosrad_load_tables_chou_sw first");
+        GtArgs<R> A{};
+        A.ncol = C.ncol; A.nlevs = C.nlevs; A.ib = C.ib; A.ict = C.kind == 2 ? 0 : C.ict; A.icb = C.icb; A.grav = (R)C.grav;
+        A.cosz = (const R *)C.cosz; A.dp = (const R *)C.dp; A.fcld = (const R *)C.fcld; A.reff = (const R *)C.reff; A.hyd = (const R *)C.hyd;
+        const dim3 grid(grid256(C.ncol), (unsigned)((C.nlevs + GT_LC - 1) / GT_LC));
+        if (C.kind == 2) {
+            A.taudiag = (R *)C.out[0]; A.tcldlyr = (R *)C.out[1]; A.enn = (R *)C.out[2];
+            hipLaunchKernelGGL((k_getirtau<R>), grid, dim3(256), 0, st, A, (const ChouDev<R> *)d_C);
+        } else {
+            A.taubeam = (R *)C.out[0]; A.taudiff = (R *)C.out[1]; A.asycl = (R *)C.out[2]; A.ssacl = C.kind == 1 ? (R *)C.out[3] : nullptr;
+            if (A.ict != 0 && (A.taubeam || A.taudiff)) {
+                if (d_ws_gt.reserve((size_t)3 * C.ncol * sizeof(R)) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the gettau workspace failed");
+                A.cc = (const R *)d_ws_gt.p;
+                hipLaunchKernelGGL((k_gettau_cc<R>), dim3(grid256(C.ncol)), dim3(256), 0, st, C.ncol, C.nlevs, A.ict, A.icb, A.fcld, (R *)d_ws_gt.p);
+            }
+            if (C.kind == 0) hipLaunchKernelGGL((k_getvistau<R>), grid, dim3(256), 0, st, A, (const SoradDev<R> *)d_O);
+            else hipLaunchKernelGGL((k_getnirtau<R>), grid, dim3(256), 0, st, A, (const SoradDev<R> *)d_O);
+        }
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+
+    int gettau_host(const GtCall &C) override
+    {
+        // host arrays through the chunk pipeline; an output the caller does not take has no place on the device either
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = gettau_check(C)) return rc;
+        HostArrs H(sizeof(R));
+        GtCall D = C;
+        const void *in[5] = {C.cosz, C.dp, C.fcld, C.reff, C.hyd};
+        const void **din[5] = {&D.cosz, &D.dp, &D.fcld, &D.reff, &D.hyd};
+        for (int k = 0; k < 5; k++) { *din[k] = nullptr; if (in[k] && !(k == 0 && C.kind == 2)) H.add(in[k], nullptr, gt_in_shape(k, C.nlevs), din[k]); }
+        for (int k = 0; k < 4; k++) { D.out[k] = nullptr; if (C.out[k]) H.add(nullptr, C.out[k], gt_out_shape(C.kind, k, C.nlevs), &D.out[k]); }
+        const int rc = host_call(C.ncol, H, -1, [&](hipStream_t st, int nc) { D.ncol = nc; return gettau_dev(st, D); });
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(stream));
+        return GEOSRAD_OK;
+    }
+
+    // in: ple, t, fcld, qi, ql, qr, qs, ri, rl, rr, rs; out: tauir, cldtmp, cldprs
+    int lw_cloud_diag_dev(hipStream_t st, int ncol, int lm, double grav, double undef, double taucrit, const void *const *in,
+                          void *const *out) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (ncol <= 0 || lm < 1) return fail(GEOSRAD_EINVAL, "geosrad_lw_cloud_diag_dev: ncol must be positive and lm at least 1");
+        if (!have_chou) return fail(GEOSRAD_EINVAL, "Chou-Suarez LW tables not set: call geosrad_load_tables_chou_lw first");
+        if (!out[0] && !out[1] && !out[2]) return fail(GEOSRAD_EINVAL, "geosrad_lw_cloud_diag_dev: every output is NULL");
+        for (int k = 0; k < 11; k++)
+            if (!in[k] && k != 2 && k != 9 && !(k == 1 && !out[1])) return fail(GEOSRAD_EINVAL, "geosrad_lw_cloud_diag_dev: null input field");
+        LwCldDiag<R> D{};
+        D.ncol = ncol; D.lm = lm; D.grav = (R)grav; D.undef = (R)undef; D.taucrit = (R)taucrit / (R)2.13;
+        D.ple = (const R *)in[0]; D.t = (const R *)in[1];
+        for (int s = 0; s < 4; s++) { D.q[s] = (const R *)in[3 + s]; D.r[s] = (const R *)in[7 + s]; }
+        D.tauir = (R *)out[0]; D.cldtmp = (R *)out[1]; D.cldprs = (R *)out[2];
+        hipLaunchKernelGGL((k_lw_cloud_diag<R>), dim3(grid256(ncol)), dim3(256), 0, st, D, (const ChouDev<R> *)d_C);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+
     // ---- stand-alone McICA generator ---------------------------------------------------------------------------------
     DevBuf<> d_mc;      // alpha / rcorr scratch of the stand-alone generator
     std::map<std::tuple<int, int, int>, DevBuf<KissJump>> sa_jumps;      // (nsubcol, nlay, inhomogeneous?) -> jump to every sub-column
@@ -2924,6 +3025,17 @@ struct MultiCtx final : geosrad_ctx {
             for (int j = 0; j < SOO_NOUT; j++) o2[j] = off(out[j], c0, so_out_shape(j, np));
             for (int j = 0; j < GEOSRAD_SONA_NOUT; j++) n2[j] = na_out ? off(na_out[j], c0, so_out_shape(SONA_TWIN[j], np)) : nullptr;
             return k->sorad_host(nc, np, nb, i2, co2, ict, icb, hk_uv, hk_ir, o2, do_drfband, n2);
+        });
+    }
+    int gettau_host(const GtCall &C) override
+    {
+        if (const int rc = gettau_check(C)) return rc;
+        return run_shards(C.ncol, [&](geosrad_ctx *k, int c0, int nc) {
+            GtCall S = C;
+            S.ncol = nc;
+            S.cosz = off(C.cosz, c0); S.dp = off(C.dp, c0); S.fcld = off(C.fcld, c0); S.reff = off(C.reff, c0); S.hyd = off(C.hyd, c0);
+            for (int j = 0; j < 4; j++) S.out[j] = off(C.out[j], c0);
+            return k->gettau_host(S);
         });
     }
     int mcica_host(int, int, int, const void *, const void *, int, const void *, const void *, const void *, const void *, double,
@@ -3614,6 +3726,53 @@ int geosrad_lit_unpack_dev(geosrad_ctx *c, void *stream, int pdim, int udim, int
                            void *unpacked, int use_default, double dflt)
 {
     return c ? c->lit_unpack_dev((hipStream_t)stream, pdim, udim, nlev, lit_pos, packed, unpacked, use_default, dflt) : GEOSRAD_EINVAL;
+}
+
+// ---- include/geosrad_gettau.h ------------------------------------------------------------------------------------------------
+static int gt_call(geosrad_ctx *c, void *stream, bool dev, const geosrad_ctx::GtCall &C)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    return dev ? c->gettau_dev((hipStream_t)stream, C) : c->gettau_host(C);
+}
+int geosrad_getvistau(geosrad_ctx *c, int ncol, int nlevs, const void *cosz, const void *dp, const void *fcld, const void *reff,
+                      const void *hydromets, int ict, int icb, double grav, void *taubeam, void *taudiff, void *asycl)
+{
+    return gt_call(c, nullptr, false, {0, 0, ncol, nlevs, ict, icb, grav, cosz, dp, fcld, reff, hydromets, {taubeam, taudiff, asycl, nullptr}});
+}
+int geosrad_getvistau_dev(geosrad_ctx *c, void *stream, int ncol, int nlevs, const void *cosz, const void *dp, const void *fcld,
+                          const void *reff, const void *hydromets, int ict, int icb, double grav, void *taubeam, void *taudiff, void *asycl)
+{
+    return gt_call(c, stream, true, {0, 0, ncol, nlevs, ict, icb, grav, cosz, dp, fcld, reff, hydromets, {taubeam, taudiff, asycl, nullptr}});
+}
+int geosrad_getnirtau(geosrad_ctx *c, int ib, int ncol, int nlevs, const void *cosz, const void *dp, const void *fcld, const void *reff,
+                      const void *hydromets, int ict, int icb, double grav, void *taubeam, void *taudiff, void *asycl, void *ssacl)
+{
+    return gt_call(c, nullptr, false, {1, ib, ncol, nlevs, ict, icb, grav, cosz, dp, fcld, reff, hydromets, {taubeam, taudiff, asycl, ssacl}});
+}
+int geosrad_getnirtau_dev(geosrad_ctx *c, void *stream, int ib, int ncol, int nlevs, const void *cosz, const void *dp, const void *fcld,
+                          const void *reff, const void *hydromets, int ict, int icb, double grav, void *taubeam, void *taudiff, void *asycl,
+                          void *ssacl)
+{
+    return gt_call(c, stream, true, {1, ib, ncol, nlevs, ict, icb, grav, cosz, dp, fcld, reff, hydromets, {taubeam, taudiff, asycl, ssacl}});
+}
+int geosrad_getirtau(geosrad_ctx *c, int ib, int ncol, int nlevs, const void *dp, const void *fcld, const void *reff, const void *hydromets,
+                     double grav, void *taudiag, void *tcldlyr, void *enn)
+{
+    return gt_call(c, nullptr, false, {2, ib, ncol, nlevs, 0, 0, grav, nullptr, dp, fcld, reff, hydromets, {taudiag, tcldlyr, enn, nullptr}});
+}
+int geosrad_getirtau_dev(geosrad_ctx *c, void *stream, int ib, int ncol, int nlevs, const void *dp, const void *fcld, const void *reff,
+                         const void *hydromets, double grav, void *taudiag, void *tcldlyr, void *enn)
+{
+    return gt_call(c, stream, true, {2, ib, ncol, nlevs, 0, 0, grav, nullptr, dp, fcld, reff, hydromets, {taudiag, tcldlyr, enn, nullptr}});
+}
+int geosrad_lw_cloud_diag_dev(geosrad_ctx *c, void *stream, int ncol, int lm, double grav, double undef, double taucrit, const void *ple,
+                              const void *t, const void *fcld, const void *qi, const void *ql, const void *qr, const void *qs, const void *ri,
+                              const void *rl, const void *rr, const void *rs, void *tauir, void *cldtmp, void *cldprs)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    const void *in[11] = {ple, t, fcld, qi, ql, qr, qs, ri, rl, rr, rs};
+    void *out[3] = {tauir, cldtmp, cldprs};
+    return c->lw_cloud_diag_dev((hipStream_t)stream, ncol, lm, grav, undef, taucrit, in, out);
 }
 
 int geosrad_profile(geosrad_ctx *c, int enable)

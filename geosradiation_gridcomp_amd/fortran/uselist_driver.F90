@@ -5,8 +5,8 @@
 !    sol_uses  : GEOS_SolarGridComp.F90:175-183, 3346-3348, 6678-6679
 !    rad_uses  : GEOS_RadiationGridComp.F90:481-484
 ! `sorad_constants` is the reference's own data module (no MAPL dependency): it stays in a GEOS build and is compiled here from the
-! reference tree when that is present (-DHAVE_SORAD_CONSTANTS); `gettau::getvistau` (GEOS_SolarGridComp.F90:177) stays in a GEOS
-! build as well but needs MAPL_ConstantsMod, which this image lacks, so its line is the one import not exercised here.
+! reference tree when that is present (-DHAVE_SORAD_CONSTANTS); `gettau::getvistau` (GEOS_SolarGridComp.F90:177) comes from the drop-in
+! module of gettau_shims.F90 (gettau_driver.F90 makes the call).
 !
 ! sol_uses then calls rrtmg_sw the two ways SORADCORE does (GEOS_SolarGridComp.F90:6331-6387): with DRBAND / DFBAND disassociated
 ! and do_drfband false (every run without SOLAR_TO_OBIO), and with them pointing at the non-contiguous section ptr2(1:Num2do,:)
@@ -102,6 +102,7 @@ subroutine sol_uses()
 #ifdef HAVE_SORAD_CONSTANTS
    use sorad_constants, only : HK_IR_OLD, HK_UV_OLD
 #endif
+   use gettau, only: getvistau
    use rrtmg_sw_rad, only: rrtmg_sw
    use rrtmg_sw_init, only: rrtmg_sw_ini
    use parrrsw, only: ngptsw
