@@ -40,20 +40,29 @@ EXPORTS_GETTAU = [
     "geosrad_getvistau", "geosrad_getvistau_dev", "geosrad_getnirtau", "geosrad_getnirtau_dev", "geosrad_getirtau", "geosrad_getirtau_dev",
     "geosrad_lw_cloud_diag_dev",
 ]
-HEADERS = [(HEADER, EXPORTS), (HEADER_GETTAU, EXPORTS_GETTAU)]      # every public header with the names it must declare
+HEADERS = [(HEADER, EXPORTS), (HEADER_GETTAU, EXPORTS_GETTAU)]      # the radiation headers with the names they must declare
+
+# the satellite simulator's ISCCP path: the third public header, include/geosrad_satsim.h, with its entry points.  It is bound beside
+# HEADERS / all_prototypes (satsim_prototypes, HEADERS_ALL; api._params looks in both) and not inside them, because tests/test_gettau_binding.py
+# pins HEADERS to the two radiation headers and all_prototypes to their names, and existing tests stay as they are
+HEADER_SATSIM = os.path.join(os.path.dirname(HERE), "include", "geosrad_satsim.h")
+EXPORTS_SATSIM = [
+    "geosrad_scops", "geosrad_scops_dev", "geosrad_icarus", "geosrad_icarus_dev", "geosrad_cosp_seeds_dev", "geosrad_isccp_dev",
+]
+HEADERS_ALL = HEADERS + [(HEADER_SATSIM, EXPORTS_SATSIM)]      # every public header
 
 _lib = None
 
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU).  Objects (compiled in parallel, each rebuilt only when one of
-    the files it includes is newer): geosrad.hip three times - fp32 kernels, fp64 kernels, the extern "C" layer of both public headers; it
-    includes gettau_kernels.hpp like every solver's kernels - and lw_cols.hip (the
+    the files it includes is newer): geosrad.hip three times - fp32 kernels, fp64 kernels, the extern "C" layer of the three public headers; it
+    includes gettau_kernels.hpp and satsim_kernels.hpp like every solver's kernels - and lw_cols.hip (the
     on-chip RRTMG_LW band sweeps) and sw_reform.hip (the default RRTMG_SW band sweeps) twice each - fp32, fp64."""
     hpp = {f: os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")}
     cols_only = {"lw_cols_kernels.hpp", "sw_reform_kernels.hpp", "lw_split_kernels.hpp"}      # headers geosrad.hip does not include
-    # geosrad.hip includes both public headers and gettau_kernels.hpp (with every other .hpp but cols_only): an edit of either rebuilds it
-    deps_main = [os.path.join(CSRC, "geosrad.hip"), HEADER, HEADER_GETTAU] + [p for f, p in hpp.items() if f not in cols_only]
+    # geosrad.hip includes the three public headers and gettau_kernels.hpp, satsim_kernels.hpp (with every other .hpp but cols_only): an edit of either rebuilds it
+    deps_main = [os.path.join(CSRC, "geosrad.hip"), HEADER, HEADER_GETTAU, HEADER_SATSIM] + [p for f, p in hpp.items() if f not in cols_only]
     deps_cols = [os.path.join(CSRC, "lw_cols.hip")] + [hpp[f] for f in ("lw_cols_kernels.hpp", "lw_cols.hpp", "lw_kernels.hpp", "lw_device.hpp")]
     deps_split = [os.path.join(CSRC, "lw_split.hip")] + [hpp[f] for f in ("lw_split_kernels.hpp", "lw_split.hpp", "lw_kernels.hpp", "lw_device.hpp")]
     deps_swq = [os.path.join(CSRC, "sw_reform.hip")] + [hpp[f] for f in ("sw_reform_kernels.hpp", "sw_reform.hpp", "sw_kernels.hpp", "lw_kernels.hpp", "lw_device.hpp")]
@@ -134,13 +143,24 @@ def all_prototypes():
     return protos
 
 
+@functools.lru_cache(maxsize=None)
+def satsim_prototypes():
+    """the prototypes of include/geosrad_satsim.h, held to EXPORTS_SATSIM"""
+    if not os.path.exists(HEADER_SATSIM):
+        raise RuntimeError(f"{HEADER_SATSIM} is missing: the binding takes every entry point's argument order and types from it")
+    protos = parse_header(open(HEADER_SATSIM).read())
+    if set(protos) != set(EXPORTS_SATSIM):
+        raise RuntimeError(f"{HEADER_SATSIM} and its export list differ: {sorted(set(protos) ^ set(EXPORTS_SATSIM))}")
+    return protos
+
+
 def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(SO):
             raise RuntimeError(f"{SO} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(there is no CPU fallback)")
-        protos = all_prototypes()
+        protos = {**all_prototypes(), **satsim_prototypes()}
         # PyTorch ships its own copy of the HIP runtime; when it is going to be used in this process (device tensors and streams
         # handed to the `_dev` entry points) it has to be the one this library binds to, so it is loaded first.
         try:

@@ -63,7 +63,8 @@ class GeosradInputError(GeosradError):
 @functools.lru_cache(maxsize=None)
 def _params(name):
     """((parameter, int | float for a scalar, None for a pointer), ...) of the library function `name`, in the order of include/geosrad.h"""
-    return tuple((p, _SCALAR.get(t)) for t, p in _lib.all_prototypes()[name][1])
+    protos = _lib.all_prototypes()
+    return tuple((p, _SCALAR.get(t)) for t, p in (protos[name] if name in protos else _lib.satsim_prototypes()[name])[1])
 
 
 def _args(name, vals):
@@ -449,6 +450,53 @@ class Context:
         CLDPRS (ncol); taucrit = the TAUCRIT: resource of the Irrad GridComp."""
         self._dev("geosrad_lw_cloud_diag_dev", ptr, {p: p.upper() for p, _ in _params("geosrad_lw_cloud_diag_dev")}, stream=stream, ncol=ncol, lm=lm,
                   grav=grav, undef=undef, taucrit=taucrit)
+
+    # ---- the satellite simulator's ISCCP path (include/geosrad_satsim.h): SCOPS, ICARUS, the COSP wrapper ------------------------
+    ICARUS_OUT = ("fq_isccp", "totalcldarea", "meanptop", "meantaucld", "meanalbedocld", "meantb", "meantbclr", "boxtau", "boxptop")
+
+    def scops(self, npoints, nlev, ncol, seed, cc, conv, overlap):
+        """scops (scops.f) for npoints points: seed int32 (npoints), one CONG stream each; cc, conv (nlev, npoints), TOA first.  Returns
+        (frac_out (nlev, ncol, npoints) in the real kind: 0 clear, 1 stratiform, 2 convective; the seeds as the routine leaves them)."""
+        seed = np.array(seed, dtype=np.int32, order="C", copy=True)
+        a = dict(npoints=npoints, nlev=nlev, ncol=ncol, cc=cc, conv=conv, overlap=overlap)
+        out = self._zeros([("frac_out", (nlev, ncol, npoints))])
+        self._host("geosrad_scops", a, out, seed=seed)
+        return out["frac_out"], seed
+
+    def scops_dev(self, stream, npoints, nlev, ncol, ptr, overlap):
+        """`ptr`: name -> device address of seed (int32, in/out), cc, conv and frac_out_u8 (one byte per cell)."""
+        self._dev("geosrad_scops_dev", ptr, stream=stream, npoints=npoints, nlev=nlev, ncol=ncol, overlap=overlap)
+
+    def icarus(self, npoints, sunlit, nlev, ncol, pfull, phalf, qv, cc, conv, dtau_s, dtau_c, top_height, top_height_direction, overlap,
+               frac_out, skt, emsfc_lw, at, dem_s, dem_c, want=ICARUS_OUT):
+        """icarus (icarus.f) in its own argument order, minus debug / debugcol: arrays (nlev, npoints) TOA first, phalf (nlev + 1, npoints),
+        frac_out (nlev, ncol, npoints) in the real kind, sunlit int32 (npoints).  Returns dict(fq_isccp (7 pressure, 7 tau, npoints);
+        totalcldarea ... meantbclr (npoints); boxtau, boxptop (ncol, npoints)) of the names in `want`; -1.E+30 = the reference's missing value."""
+        a = {k: v for k, v in locals().items() if k not in ("self", "want", "sunlit")}
+        unknown = set(want) - set(self.ICARUS_OUT)
+        if unknown:
+            raise TypeError(f"geosrad_icarus: no output {sorted(unknown)}")
+        shapes = {"fq_isccp": (7, 7, npoints), "boxtau": (ncol, npoints), "boxptop": (ncol, npoints)}
+        out = self._zeros([(k, shapes.get(k, (npoints,))) for k in self.ICARUS_OUT if k in want])
+        self._host("geosrad_icarus", a, out, sunlit=np.ascontiguousarray(sunlit, dtype=np.int32))
+        return out
+
+    def icarus_dev(self, stream, npoints, nlev, ncol, ptr, top_height, top_height_direction, overlap, emsfc_lw):
+        """`ptr`: name -> device address of sunlit (int32), pfull ... dem_c, frac_out_u8 and of the wanted outputs (missing = NULL)."""
+        self._dev("geosrad_icarus_dev", ptr, stream=stream, npoints=npoints, nlev=nlev, ncol=ncol, top_height=top_height,
+                  top_height_direction=top_height_direction, overlap=overlap, emsfc_lw=emsfc_lw)
+
+    def cosp_seeds_dev(self, stream, npoints, ptr):
+        """cosp.F90:167-174: `ptr` = device addresses of psfc (npoints) and seed (int32, npoints)."""
+        self._dev("geosrad_cosp_seeds_dev", ptr, stream=stream, npoints=npoints)
+
+    def isccp_dev(self, stream, npoints, lm, ncol, ptr, overlap=3, top_height=1, top_height_direction=2, emsfc_lw=0.999):
+        """The COSP ISCCP path on GEOS fields in model order (defaults: GEOS_SatsimGridComp.F90:3360-3362, :3462): `ptr` = name -> device
+        address of T, QV, FCLD, CCA, PLE, PLO, DTAU_S, EMISS, DTAU_C, DEM_C, TS (CCA, DTAU_C, DEM_C may be missing = zero), sunlit and seed
+        (int32) and of the wanted outputs fq_isccp ... boxptop, SGFCLD (lm, npoints)."""
+        up = ("T", "QV", "FCLD", "CCA", "PLE", "PLO", "DTAU_S", "EMISS", "DTAU_C", "DEM_C", "TS", "SGFCLD")
+        self._dev("geosrad_isccp_dev", ptr, {k.lower(): k for k in up}, stream=stream, npoints=npoints, lm=lm, ncol=ncol, overlap=overlap,
+                  top_height=top_height, top_height_direction=top_height_direction, emsfc_lw=emsfc_lw)
 
     # ---- Chou-Suarez SW, host arrays ---------------------------------------------------------------------
     def sorad(self, m, np_, nb, cosz, pl, ta, wa, oa, co2, cwc, fcld, ict, icb, reff, hk_uv, hk_ir, taua, ssaa, asya,

@@ -24,6 +24,7 @@
 #include <cstdint>
 #include "../../include/geosrad.h"
 #include "../../include/geosrad_gettau.h"
+#include "../../include/geosrad_satsim.h"
 #include "dev_buf.hpp"
 #include "lw_device.hpp"
 #include "lw_kernels.hpp"
@@ -34,6 +35,7 @@
 #include "sorad_kernels.hpp"
 #include "gridcomp_kernels.hpp"
 #include "gettau_kernels.hpp"
+#include "satsim_kernels.hpp"
 #include "lw_cols.hpp"
 #include "lw_split.hpp"
 #include "sw_reform.hpp"
@@ -641,6 +643,61 @@ struct geosrad_ctx {
     virtual int gettau_dev(hipStream_t, const GtCall &C) { return nodev(C.name()); }
     virtual int gettau_host(const GtCall &C) = 0;
     virtual int lw_cloud_diag_dev(hipStream_t, int, int, double, double, double, In, Out) { return nodev("geosrad_lw_cloud_diag_dev"); }
+    // the satellite simulator's ISCCP path (include/geosrad_satsim.h): one record per routine, shared by the `_dev` and the host variant
+    struct ScopsCall {
+        int npoints, nlev, ncol, overlap;
+        int32_t *seed;
+        const void *cc, *conv;
+        void *frac_out;                 // bytes (`_dev`) or reals (host)
+    };
+    enum IcIn { IC_PFULL, IC_PHALF, IC_QV, IC_CC, IC_CONV, IC_DTAU_S, IC_DTAU_C, IC_SKT, IC_AT, IC_DEM_S, IC_DEM_C, IC_NIN };
+    enum IcOut { ICO_FQ, ICO_TCA, ICO_PTOP, ICO_TAU, ICO_ALB, ICO_TB, ICO_TBCLR, ICO_BOXTAU, ICO_BOXPTOP, ICO_NOUT };
+    struct IcarusCall {
+        int npoints, nlev, ncol, top_height, top_height_direction, overlap;
+        double emsfc_lw;
+        const int32_t *sunlit;
+        const void *in[IC_NIN];
+        const void *frac_out;           // bytes (`_dev`) or reals (host)
+        void *out[ICO_NOUT];
+        // geosrad_isccp_dev only: the fields are GEOS's (FCLD / CCA unscaled, in[IC_PHALF] = PLE(0:LM), CCA / DTAU_C / DEM_C may be null),
+        // SCOPS runs first on the unscaled fractions into the context's mask with `seed`, the outputs are COSP's, SGFCLD on request
+        bool cosp = false;
+        int32_t *seed = nullptr;
+        void *sgfcld = nullptr;
+    };
+    // the argument rules of include/geosrad_satsim.h, the same for every kind of context
+    int satsim_check(const char *who, int npoints, int nlev, int ncol, int overlap, int top_height, int top_height_direction)
+    {
+        const std::string w = who;
+        if (npoints < 1) return fail(GEOSRAD_EINVAL, w + ": npoints must be positive");
+        if (nlev < 2) return fail(GEOSRAD_EINVAL, w + ": nlev must be at least 2");
+        // k_icarus_stats counts a point's sub-columns per cloud type in 16 bits (GEOS: Ncolumns <= 30, GEOS_SatsimGridComp.F90:3057)
+        if (ncol < 1 || ncol > 65535) return fail(GEOSRAD_EINVAL, w + ": ncol must be in 1..65535");
+        if (overlap < 1 || overlap > 3) return fail(GEOSRAD_EINVAL, w + ": overlap must be 1, 2 or 3");
+        if (top_height < 1 || top_height > 3) return fail(GEOSRAD_EINVAL, w + ": top_height must be 1, 2 or 3");
+        if (top_height_direction < 1 || top_height_direction > 2) return fail(GEOSRAD_EINVAL, w + ": top_height_direction must be 1 or 2");
+        return GEOSRAD_OK;
+    }
+    int scops_check(const ScopsCall &C)
+    {
+        if (const int rc = satsim_check("geosrad_scops", C.npoints, C.nlev, C.ncol, C.overlap, 1, 1)) return rc;
+        if (!C.seed || !C.cc || !C.conv || !C.frac_out) return fail(GEOSRAD_EINVAL, "geosrad_scops: null array");
+        return GEOSRAD_OK;
+    }
+    int icarus_check(const IcarusCall &C)
+    {
+        const char *who = C.cosp ? "geosrad_isccp_dev" : "geosrad_icarus";
+        if (const int rc = satsim_check(who, C.npoints, C.nlev, C.ncol, C.overlap, C.top_height, C.top_height_direction)) return rc;
+        for (int k = 0; k < IC_NIN; k++)
+            if (!C.in[k] && !(C.cosp && (k == IC_CONV || k == IC_DTAU_C || k == IC_DEM_C))) return fail(GEOSRAD_EINVAL, std::string(who) + ": null input array");
+        if (!C.sunlit || (C.cosp ? !C.seed : !C.frac_out)) return fail(GEOSRAD_EINVAL, std::string(who) + ": null input array");
+        return GEOSRAD_OK;
+    }
+    virtual int scops_dev(hipStream_t, const ScopsCall &) { return nodev("geosrad_scops_dev"); }
+    virtual int scops_host(const ScopsCall &) = 0;
+    virtual int icarus_dev(hipStream_t, const IcarusCall &C) { return nodev(C.cosp ? "geosrad_isccp_dev" : "geosrad_icarus_dev"); }
+    virtual int icarus_host(const IcarusCall &) = 0;
+    virtual int cosp_seeds_dev(hipStream_t, int, const void *, int32_t *) { return nodev("geosrad_cosp_seeds_dev"); }
 };
 
 // order of the `in` / `out` pointer arrays of sw_dev / sw_host
@@ -713,6 +770,9 @@ static inline ArrShape so_out_shape(int k, size_t L)
 // gettau: inputs cosz, dp, fcld, reff, hydromets; outputs of GtCall::out by kind
 static inline ArrShape gt_in_shape(int k, size_t L) { return {k == 0 ? 1 : k <= 2 ? L : 4 * L, 1}; }
 static inline ArrShape gt_out_shape(int kind, int k, size_t L) { return {kind == 2 ? (k == 0 ? 4 * L : L + 1) : (k <= 1 ? 4 * L : L), 1}; }
+// icarus: the inputs of IcIn, the outputs of IcOut (L levels, S sub-columns); frac_out is (S * L) rows
+static inline ArrShape ic_in_shape(int k, size_t L) { return {k == geosrad_ctx::IC_PHALF ? L + 1 : k == geosrad_ctx::IC_SKT ? 1 : L, 1}; }
+static inline ArrShape ic_out_shape(int k, size_t S) { return {k == geosrad_ctx::ICO_FQ ? 49 : k >= geosrad_ctx::ICO_BOXTAU ? S : 1, 1}; }
 
 // The arrays of one host-pointer call, added in host_pipeline's order (copied in only, both ways, back only).  src: copied in, dst:
 // copied back (null: the array only has its place on the device).  *at receives the array's device address before the solver is
@@ -965,7 +1025,7 @@ template <typename R> struct Ctx : geosrad_ctx {
     size_t workspace_bytes() const override
     {
         size_t t = 0;
-        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_ws_hb, &d_zero, &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
+        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_ws_hb, &d_ws_ss, &d_zero, &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
             t += b->bytes;
         return t;
     }
@@ -1977,18 +2037,26 @@ template <typename R> struct Ctx : geosrad_ctx {
     {
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamSynchronize(st));
-        uint32_t e2[2] = {0, 0};
-        HIPCHK(hipMemcpy(e2, d_err, 8, hipMemcpyDeviceToHost));
+        uint32_t e2[4] = {0, 0, 0, 0};
+        HIPCHK(hipMemcpy(e2, d_err, 16, hipMemcpyDeviceToHost));
         // slot 0 = RRTMG_LW (+ McICA), slot 1 = RRTMG_SW; the Chou schemes have no input assertions (neither has the reference).
         // The host-pointer entry points look at their own solver's slot only (a flag left by an unchecked `_dev` call of the other
         // solver is that call's to report); geosrad_check reports either.  Only the slot that is reported is cleared - with the two
         // solvers on two streams the other one's flag stays up for the check of its own stream - and it is cleared in stream order
         // on `st`, so a kernel of the other solver running on another stream cannot lose a bit to it.
-        if (which == 0) e2[1] = 0;
-        if (which == 1) e2[0] = 0;
-        if (!e2[0] && !e2[1]) return GEOSRAD_OK;
-        HIPCHK(hipMemsetAsync(d_err + (e2[1] ? 1 : 0), 0, 4, st));
+        // slot 3 = the range check of ICARUS (icarus.f:403-455), reported last
+        if (which == 0) e2[1] = e2[3] = 0;
+        if (which == 1) e2[0] = e2[3] = 0;
+        if (which == 3) e2[0] = e2[1] = 0;
+        if (!e2[0] && !e2[1] && !e2[3]) return GEOSRAD_OK;
+        HIPCHK(hipMemsetAsync(d_err + (e2[1] ? 1 : e2[0] ? 0 : 3), 0, 4, st));
         HIPCHK(hipStreamSynchronize(st));
+        if (!e2[0] && !e2[1]) {
+            static const char *IC_NAMES[6] = {"cc", "conv", "dtau_s", "dtau_c", "dem_s", "dem_c"};
+            for (int k = 0; k < 6; k++)
+                if (e2[3] & (1u << k)) return fail(GEOSRAD_EINPUT, std::string("Input variable out of range: ") + IC_NAMES[k]);
+            return fail(GEOSRAD_EINPUT, "device-side input check failed (icarus)");
+        }
         if (e2[1]) {   // RRTMG_SW input assertions (SW/rrtmg_sw_rad.F90:365-383)
             static const char *SW_NEG_NAMES[12] = {"play", "tlay", "h2ovmr", "o3vmr", "co2vmr", "ch4vmr", "o2vmr", "cld", "ciwp", "clwp", "rei", "rel"};
             for (int k = 0; k < 12; k++)
@@ -2801,6 +2869,150 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 
+    // =====================================================================================================
+    // the satellite simulator's ISCCP path (include/geosrad_satsim.h; satsim_kernels.hpp)
+    // =====================================================================================================
+    DevBuf<> d_ws_ss;
+    struct SsWs { int32_t *seed0, *itrop; uint8_t *mask, *bin; R *dem_wv, *bb, *pt, *tbb, *ptop, *alb, *mm; };
+    // the workspace of one call: on Carve() the bytes it takes, on Carve(d_ws_ss) its planes.  mask: the byte mask is the context's too
+    size_t ss_layout(int np, int nlev, int ncol, bool mask, SsWs &w, Carve c) const
+    {
+        const size_t pl = (size_t)np * nlev, ps = (size_t)np * ncol;
+        w.seed0 = c.take<int32_t>(np); w.itrop = c.take<int32_t>(np); w.mm = c.take<R>(2);
+        w.dem_wv = c.take<R>(pl); w.bb = c.take<R>(pl); w.pt = c.take<R>((size_t)SS_NPT * np);
+        w.tbb = c.take<R>(ps); w.ptop = c.take<R>(ps); w.alb = c.take<R>(ps); w.bin = c.take<uint8_t>(ps);
+        w.mask = c.take<uint8_t>(mask ? ps * nlev : 0);
+        return c.off;
+    }
+    // the planes of a call; a larger request than any before re-allocates (as every workspace here: not inside a graph capture)
+    int ss_workspace(int np, int nlev, int ncol, bool mask, SsWs &w)
+    {
+        // the mask, once taken, stays part of the layout, so that calls with and without it do not move the other planes about
+        ss_mask |= mask;
+        if (d_ws_ss.reserve(ss_layout(np, nlev, ncol, ss_mask, w, Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the satellite simulator's workspace failed");
+        ss_layout(np, nlev, ncol, ss_mask, w, Carve(d_ws_ss.p));
+        return GEOSRAD_OK;
+    }
+    bool ss_mask = false;
+
+    int scops_launch(hipStream_t st, const ScopsCall &C, int32_t *seed0)
+    {
+        ScopsArgs<R> A{};
+        A.npoints = C.npoints; A.nlev = C.nlev; A.ncol = C.ncol; A.overlap = C.overlap;
+        // ncol draws on: x -> a x + c composed ncol times; the inverse multiplier by Newton's iteration (exact mod 2^32, so mod 2^30)
+        uint32_t jA = 1, jC = 0;
+        for (int k = 0; k < C.ncol; k++) { jC = jC * SS_A + SS_C; jA = jA * SS_A; }
+        uint32_t inv = SS_A;
+        for (int k = 0; k < 5; k++) inv *= 2u - SS_A * inv;
+        A.jA = jA; A.jC = jC; A.ainv = inv;
+        A.seed_in = seed0; A.seed = C.seed; A.cc = (const R *)C.cc; A.conv = (const R *)C.conv; A.frac_out = (uint8_t *)C.frac_out;
+        HIPCHK(hipMemcpyAsync(seed0, C.seed, (size_t)C.npoints * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL((k_scops<R>), dim3(grid256((size_t)C.npoints * C.ncol)), dim3(256), 0, st, A);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+    int scops_dev(hipStream_t st, const ScopsCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = scops_check(C)) return rc;
+        SsWs w;
+        if (const int rc = ss_workspace(C.npoints, C.nlev, C.ncol, false, w)) return rc;
+        return scops_launch(st, C, w.seed0);
+    }
+    int icarus_dev(hipStream_t st, const IcarusCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = icarus_check(C)) return rc;
+        SsWs w;
+        if (const int rc = ss_workspace(C.npoints, C.nlev, C.ncol, C.cosp, w)) return rc;
+        const int np = C.npoints;
+        if (C.cosp) {
+            const ScopsCall S{np, C.nlev, C.ncol, C.overlap, C.seed, C.in[IC_CC], C.in[IC_CONV], w.mask};
+            // SCOPS takes FCLD / CCA as they are (cosp.F90:392-397); the 0.999999 of cosp_isccp_simulator.F90:65-66 is on icarus' arguments only
+            if (const int rc = scops_launch(st, S, w.seed0)) return rc;
+            if (C.sgfcld) hipLaunchKernelGGL((k_sgfcld<R>), dim3(grid256(np), C.nlev), dim3(256), 0, st, np, C.ncol, (const uint8_t *)w.mask, (R *)C.sgfcld);
+        }
+        IcArgs<R> A{};
+        A.npoints = np; A.nlev = C.nlev; A.ncol = C.ncol; A.top_height = C.top_height; A.top_height_direction = C.top_height_direction;
+        A.ple_shift = C.cosp; A.scaled = C.cosp; A.cosp_out = C.cosp; A.emsfc_lw = (R)C.emsfc_lw;
+        A.sunlit = C.sunlit;
+        auto I = [&](int k) { return (const R *)C.in[k]; };
+        A.pfull = I(IC_PFULL); A.phalf = I(IC_PHALF); A.qv = I(IC_QV); A.cc = I(IC_CC); A.conv = I(IC_CONV); A.dtau_s = I(IC_DTAU_S);
+        A.dtau_c = I(IC_DTAU_C); A.skt = I(IC_SKT); A.at = I(IC_AT); A.dem_s = I(IC_DEM_S); A.dem_c = I(IC_DEM_C);
+        A.frac = C.cosp ? w.mask : (const uint8_t *)C.frac_out;
+        A.dem_wv = w.dem_wv; A.bb = w.bb; A.pt = w.pt; A.itrop = w.itrop; A.tbb = w.tbb; A.ptop = w.ptop; A.alb = w.alb; A.bin = w.bin;
+        A.err = d_err + 3;
+        auto O = [&](int k) { return (R *)C.out[k]; };
+        A.fq = O(ICO_FQ); A.totalcldarea = O(ICO_TCA); A.meanptop = O(ICO_PTOP); A.meantaucld = O(ICO_TAU); A.meanalbedocld = O(ICO_ALB);
+        A.meantb = O(ICO_TB); A.meantbclr = O(ICO_TBCLR); A.boxtau = O(ICO_BOXTAU); A.boxptop = O(ICO_BOXPTOP);
+        hipLaunchKernelGGL((k_icarus_point<R>), dim3(grid256(np)), dim3(256), 0, st, A);
+        hipLaunchKernelGGL((k_icarus_box<R>), dim3(grid256((size_t)np * C.ncol)), dim3(256), 0, st, A);
+        hipLaunchKernelGGL((k_icarus_stats<R>), dim3((unsigned)((np + SS_STATS_T - 1) / SS_STATS_T)), dim3(SS_STATS_T), 0, st, A);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+    int cosp_seeds_dev(hipStream_t st, int npoints, const void *psfc, int32_t *seed) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (npoints < 1 || !psfc || !seed) return fail(GEOSRAD_EINVAL, "geosrad_cosp_seeds_dev: npoints must be positive, psfc and seed given");
+        SsWs w;
+        if (const int rc = ss_workspace(npoints, 2, 1, false, w)) return rc;
+        if (npoints > 1) hipLaunchKernelGGL((k_cosp_minmax<R>), dim3(1), dim3(1024), 0, st, npoints, (const R *)psfc, w.mm);
+        hipLaunchKernelGGL((k_cosp_seeds<R>), dim3(grid256(npoints)), dim3(256), 0, st, npoints, (const R *)psfc, (const R *)w.mm, seed);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+    // host arrays through the chunk pipeline: chunks split the points, a point's stream stays in one chunk.  The real mask of the caller
+    // and the byte mask of the kernels are two arrays of the slot, converted on the device
+    int scops_host(const ScopsCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = scops_check(C)) return rc;
+        HostArrs H(sizeof(R));
+        ScopsCall D = C;
+        // the seeds go in as one array and come back as another, so that the byte mask between them is transferred in neither direction
+        const void *seed_in = nullptr, *seed_at = nullptr, *frac_at = nullptr, *u8_at = nullptr;
+        const size_t cells = (size_t)C.ncol * C.nlev;
+        H.add(C.cc, nullptr, {(size_t)C.nlev, 1}, &D.cc);
+        H.add(C.conv, nullptr, {(size_t)C.nlev, 1}, &D.conv);
+        H.add(C.seed, nullptr, {1, 1}, &seed_in, sizeof(int32_t));
+        H.add(nullptr, nullptr, {cells, 1}, &u8_at, 1);
+        H.add(nullptr, C.seed, {1, 1}, &seed_at, sizeof(int32_t));
+        H.add(nullptr, C.frac_out, {cells, 1}, &frac_at);
+        const int rc = host_call(C.npoints, H, -1, [&](hipStream_t st, int nc) {
+            D.npoints = nc; D.seed = (int32_t *)seed_at; D.frac_out = (void *)u8_at;
+            if (const int r = hip_rc("hipMemcpyAsync", hipMemcpyAsync((void *)seed_at, seed_in, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToDevice, st))) return r;
+            if (const int r = scops_dev(st, D)) return r;
+            const size_t nn = cells * nc;
+            hipLaunchKernelGGL((k_mask_to_real<R>), dim3(grid256(nn)), dim3(256), 0, st, nn, (const uint8_t *)u8_at, (R *)frac_at);
+            return hip_rc("k_mask_to_real", hipGetLastError());
+        });
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(stream));
+        return GEOSRAD_OK;
+    }
+    int icarus_host(const IcarusCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (C.cosp) return fail(GEOSRAD_EINVAL, "geosrad_isccp_dev has no host variant");
+        if (const int rc = icarus_check(C)) return rc;
+        HostArrs H(sizeof(R));
+        IcarusCall D = C;
+        const void *sun_at = nullptr, *frac_at = nullptr, *u8_at = nullptr;
+        const size_t cells = (size_t)C.ncol * C.nlev;
+        for (int k = 0; k < IC_NIN; k++) H.add(C.in[k], nullptr, ic_in_shape(k, C.nlev), &D.in[k]);
+        H.add(C.sunlit, nullptr, {1, 1}, &sun_at, sizeof(int32_t));
+        H.add(C.frac_out, nullptr, {cells, 1}, &frac_at);
+        H.add(nullptr, nullptr, {cells, 1}, &u8_at, 1);
+        for (int k = 0; k < ICO_NOUT; k++) { D.out[k] = nullptr; if (C.out[k]) H.add(nullptr, C.out[k], ic_out_shape(k, C.ncol), &D.out[k]); }
+        return host_call(C.npoints, H, 3, [&](hipStream_t st, int nc) {
+            D.npoints = nc; D.sunlit = (const int32_t *)sun_at; D.frac_out = u8_at;
+            const size_t nn = cells * nc;
+            hipLaunchKernelGGL((k_real_to_mask<R>), dim3(grid256(nn)), dim3(256), 0, st, nn, (const R *)frac_at, (uint8_t *)u8_at);
+            return icarus_dev(st, D);
+        });
+    }
+
     // in: ple, t, fcld, qi, ql, qr, qs, ri, rl, rr, rs; out: tauir, cldtmp, cldprs
     int lw_cloud_diag_dev(hipStream_t st, int ncol, int lm, double grav, double undef, double taucrit, const void *const *in,
                           void *const *out) override
@@ -3036,6 +3248,26 @@ struct MultiCtx final : geosrad_ctx {
             S.cosz = off(C.cosz, c0); S.dp = off(C.dp, c0); S.fcld = off(C.fcld, c0); S.reff = off(C.reff, c0); S.hyd = off(C.hyd, c0);
             for (int j = 0; j < 4; j++) S.out[j] = off(C.out[j], c0);
             return k->gettau_host(S);
+        });
+    }
+    int scops_host(const ScopsCall &C) override
+    {
+        if (const int rc = scops_check(C)) return rc;
+        return run_shards(C.npoints, [&](geosrad_ctx *k, int c0, int nc) {
+            ScopsCall S = C;
+            S.npoints = nc; S.seed = C.seed + c0; S.cc = off(C.cc, c0); S.conv = off(C.conv, c0); S.frac_out = off(C.frac_out, c0);
+            return k->scops_host(S);
+        });
+    }
+    int icarus_host(const IcarusCall &C) override
+    {
+        if (const int rc = icarus_check(C)) return rc;
+        return run_shards(C.npoints, [&](geosrad_ctx *k, int c0, int nc) {
+            IcarusCall S = C;
+            S.npoints = nc; S.sunlit = C.sunlit + c0; S.frac_out = off(C.frac_out, c0);
+            for (int j = 0; j < IC_NIN; j++) S.in[j] = off(C.in[j], c0);
+            for (int j = 0; j < ICO_NOUT; j++) S.out[j] = off(C.out[j], c0);
+            return k->icarus_host(S);
         });
     }
     int mcica_host(int, int, int, const void *, const void *, int, const void *, const void *, const void *, const void *, double,
@@ -3774,6 +4006,58 @@ int geosrad_lw_cloud_diag_dev(geosrad_ctx *c, void *stream, int ncol, int lm, do
     void *out[3] = {tauir, cldtmp, cldprs};
     return c->lw_cloud_diag_dev((hipStream_t)stream, ncol, lm, grav, undef, taucrit, in, out);
 }
+
+// ---- include/geosrad_satsim.h ------------------------------------------------------------------------------------------------
+int geosrad_scops(geosrad_ctx *c, int npoints, int nlev, int ncol, int32_t *seed, const void *cc, const void *conv, int overlap, void *frac_out)
+{
+    return c ? c->scops_host({npoints, nlev, ncol, overlap, seed, cc, conv, frac_out}) : GEOSRAD_EINVAL;
+}
+int geosrad_scops_dev(geosrad_ctx *c, void *stream, int npoints, int nlev, int ncol, int32_t *seed, const void *cc, const void *conv, int overlap,
+                      void *frac_out_u8)
+{
+    return c ? c->scops_dev((hipStream_t)stream, {npoints, nlev, ncol, overlap, seed, cc, conv, frac_out_u8}) : GEOSRAD_EINVAL;
+}
+#define IC_CALL(frac) geosrad_ctx::IcarusCall C{npoints, nlev, ncol, top_height, top_height_direction, overlap, emsfc_lw, sunlit,          \
+        {pfull, phalf, qv, cc, conv, dtau_s, dtau_c, skt, at, dem_s, dem_c}, frac,                                                       \
+        {fq_isccp, totalcldarea, meanptop, meantaucld, meanalbedocld, meantb, meantbclr, boxtau, boxptop}}
+int geosrad_icarus(geosrad_ctx *c, int npoints, const int32_t *sunlit, int nlev, int ncol, const void *pfull, const void *phalf, const void *qv,
+                   const void *cc, const void *conv, const void *dtau_s, const void *dtau_c, int top_height, int top_height_direction, int overlap,
+                   const void *frac_out, const void *skt, double emsfc_lw, const void *at, const void *dem_s, const void *dem_c, void *fq_isccp,
+                   void *totalcldarea, void *meanptop, void *meantaucld, void *meanalbedocld, void *meantb, void *meantbclr, void *boxtau,
+                   void *boxptop)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    IC_CALL(frac_out);
+    return c->icarus_host(C);
+}
+int geosrad_icarus_dev(geosrad_ctx *c, void *stream, int npoints, const int32_t *sunlit, int nlev, int ncol, const void *pfull, const void *phalf,
+                       const void *qv, const void *cc, const void *conv, const void *dtau_s, const void *dtau_c, int top_height,
+                       int top_height_direction, int overlap, const void *frac_out_u8, const void *skt, double emsfc_lw, const void *at,
+                       const void *dem_s, const void *dem_c, void *fq_isccp, void *totalcldarea, void *meanptop, void *meantaucld,
+                       void *meanalbedocld, void *meantb, void *meantbclr, void *boxtau, void *boxptop)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    IC_CALL(frac_out_u8);
+    return c->icarus_dev((hipStream_t)stream, C);
+}
+int geosrad_cosp_seeds_dev(geosrad_ctx *c, void *stream, int npoints, const void *psfc, int32_t *seed)
+{
+    return c ? c->cosp_seeds_dev((hipStream_t)stream, npoints, psfc, seed) : GEOSRAD_EINVAL;
+}
+int geosrad_isccp_dev(geosrad_ctx *c, void *stream, int npoints, int lm, int ncol, const void *t, const void *qv, const void *fcld, const void *cca,
+                      const void *ple, const void *plo, const void *dtau_s, const void *emiss, const void *dtau_c, const void *dem_c, const void *ts,
+                      const int32_t *sunlit, int32_t *seed, int overlap, int top_height, int top_height_direction, double emsfc_lw, void *fq_isccp,
+                      void *totalcldarea, void *meanptop, void *meantaucld, void *meanalbedocld, void *meantb, void *meantbclr, void *boxtau,
+                      void *boxptop, void *sgfcld)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    const int nlev = lm;
+    const void *pfull = plo, *phalf = ple, *cc = fcld, *conv = cca, *skt = ts, *at = t, *dem_s = emiss;
+    IC_CALL(nullptr);
+    C.cosp = true; C.seed = seed; C.sgfcld = sgfcld;
+    return c->icarus_dev((hipStream_t)stream, C);
+}
+#undef IC_CALL
 
 int geosrad_profile(geosrad_ctx *c, int enable)
 {
