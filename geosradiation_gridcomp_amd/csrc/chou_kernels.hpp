@@ -57,10 +57,6 @@ template <typename R> struct ChouGeos {
     int binary;                            // RADLW_BINARY_CLOUDS: FCLD = 1 where FCLD > 0
 };
 
-template <typename R> GR_DEV R gr_log10(R x);
-template <> GR_DEV float gr_log10<float>(float x) { return log10f(x); }
-template <> GR_DEV double gr_log10<double>(double x) { return log10(x); }
-
 // ---------------------------------------------------------------------------------------------------
 // k_chou_prep: lane = column; absorber amounts and scaled quantities of every layer (irrad.F90:381-453), written as the
 // column's record.  (Like the reference, irrad has no input assertions.)

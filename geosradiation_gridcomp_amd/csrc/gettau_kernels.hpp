@@ -1,7 +1,9 @@
 // gettau_kernels.hpp -- GEOS_RadiationShared/gettau.F90 (getvistau :33, getnirtau :102, getirtau :173; bodies getvistau.code,
 // getnirtau.code, getirtau.code) over a batch of columns, per species, and the infrared cloud exports of LW_Driver for any LW scheme
-// (GEOS_IrradGridComp.F90:1898-1912, :3626-3650).  The same arithmetic runs fused in k_sorad_cloud (species summed), k_chou_bands
-// (taudiag only) and k_sw_update_clouds (taudiff only); those kernels are not touched.
+// (GEOS_IrradGridComp.F90:1898-1912, :3626-3650).  getvistau / getnirtau are stated beside their tables, as so_cld_tau, so_cld_index,
+// so_caib_scale, so_caif_scale and so_cld_asy (sorad_kernels.hpp): gt_swtau uses all five, k_sw_update_clouds the first, second and fourth
+// for its taudiff, bit for bit getvistau's.  k_sorad_cloud (species summed; contraction on) and k_chou_bands (getirtau inside its hand-tuned
+// band body) keep their own statements: sharing changes the one's rounding, the other's stream (profiles/r16_chou_physics_once.md).
 //
 // Arrays in the solver-API layout, the column index fastest: dp, fcld (ncol,nlevs); reff, hydromets and the per-species outputs
 // (ncol,nlevs,4); tcldlyr, enn (ncol,0:nlevs).  A null output is neither computed nor written.
@@ -16,7 +18,7 @@
 // its 256 x GT_LC cells (1 188 reals = 0.6 per cell), only in the overlap mode and only the one whose output is wanted.
 #pragma once
 #include "sorad_kernels.hpp"     // SoradDev: the Chou-Suarez SW tables
-#include "chou_kernels.hpp"      // ChouDev: aib_ir ...; ch_pow, ch_exp, gr_log10
+#include "chou_kernels.hpp"      // ChouDev: aib_ir ...; ch_pow, ch_exp
 
 namespace geosrad {
 
@@ -71,15 +73,11 @@ template <typename R, bool NIR> GR_DEV void gt_swtau(const GtArgs<R> &A, const S
     if (i >= A.ncol) return;
     const int n = A.ncol, np = A.nlevs, ib = A.ib, ict = A.ict, icb = A.icb;
     const size_t sp = (size_t)np * n;      // one species' plane
-    const R dm = (R)0.1, dt = (R)0.30103, da = (R)0.1, t1 = (R)-0.9031;
     const R grav = A.grav;
     const bool want_tau = A.taubeam || A.taudiff, want_g = A.asycl || (NIR && A.ssacl);
     const R cosz = scaled && A.taubeam ? A.cosz[i] : (R)0;
     R cc[4] = {0, 0, 0, 0};
     if (scaled && want_tau) { cc[1] = A.cc[i]; cc[2] = A.cc[(size_t)n + i]; cc[3] = A.cc[2 * (size_t)n + i]; }
-#define CAIB(a, b, c) s_caib[(((c) - 1) * 9 + ((b) - 1)) * 11 + ((a) - 1)]
-#define CAIF(a, b) s_caif[((b) - 1) * 9 + ((a) - 1)]
-#define N2(tab, j) tab[((j) - 1) * 3 + (ib - 1)]
     const int kb = (int)blockIdx.y * GT_LC, ke = kb + GT_LC < np ? kb + GT_LC : np;      // 0-based layers [kb, ke)
     for (int k0 = kb; k0 < ke; k0 += GT_NB) {
         R dpv[GT_NB], f[GT_NB], re[4][GT_NB], h[4][GT_NB];
@@ -101,22 +99,9 @@ template <typename R, bool NIR> GR_DEV void gt_swtau(const GtArgs<R> &A, const S
             if (k > ke) break;
             const size_t o = (size_t)(k - 1) * n + i;
             const R wp = (dpv[j] * (R)1.0e3) / grav;
-            const R r1 = re[0][j], r2 = re[1][j], r4 = re[3][j];
-            const R h1 = h[0][j], h2 = h[1][j], h3 = h[2][j], h4 = h[3][j];
-            const R fc = f[j];
-            const R rs = r4 < (R)112.0 ? r4 : (R)112.0;      // reff_snow = min(reff(k,4),112.0)
-            R tc1, tc2, tc3, tc4;
-            if (!NIR) {
-                tc1 = r1 <= 0 ? (R)0 : (wp * h1) * T.aib_uv / r1;
-                tc2 = r2 <= 0 ? (R)0 : (wp * h2) * (T.awb_uv[0] + T.awb_uv[1] / r2);
-                tc3 = (wp * h3) * T.arb_uv[0];
-                tc4 = rs <= 0 ? (R)0 : (wp * h4) * T.aib_uv / rs;
-            } else {
-                tc1 = r1 <= 0 ? (R)0 : (wp * h1) * T.aib_nir / r1;
-                tc2 = r2 <= 0 ? (R)0 : (wp * h2) * (N2(T.awb_nir, 1) + N2(T.awb_nir, 2) / r2);
-                tc3 = (wp * h3) * N2(T.arb_nir, 1);
-                tc4 = rs <= 0 ? (R)0 : (wp * h4) * T.aib_nir / rs;
-            }
+            const R r1 = re[0][j], r2 = re[1][j], r4 = re[3][j], fc = f[j];
+            R tc1, tc2, tc3, tc4, rs;      // rs: reff_snow = min(reff(k,4),112.0)
+            so_cld_tau<R, NIR>(T, ib, wp, r1, r2, r4, h[0][j], h[1][j], h[2][j], h[3][j], tc1, tc2, tc3, tc4, rs);
             const R tauc = tc1 + tc2 + tc3 + tc4;
             const bool cloudy = tauc > (R)0.02 && fc > (R)0.01;
             if (want_tau) {
@@ -126,34 +111,10 @@ template <typename R, bool NIR> GR_DEV void gt_swtau(const GtArgs<R> &A, const S
                     if (cloudy) {
                         const int kk = k < ict ? 1 : (k < icb ? 2 : 3);
                         R fa = NIR ? (cc[kk] != 0 ? fc / cc[kk] : (R)0) : fc / cc[kk];      // getnirtau guards, getvistau divides
-                        const R tcap = tauc < (R)32. ? tauc : (R)32.;
-                        R ft = (gr_log10<R>(tcap) - t1) / dt;
-                        fa = fa / da;
-                        int it = (int)(ft + (R)1.5), ia = (int)(fa + (R)1.5);
-                        it = it > 2 ? it : 2; ia = ia > 2 ? ia : 2;
-                        it = it < 8 ? it : 8; ia = ia < 10 ? ia : 10;
-                        ft = ft - (R)(it - 1); fa = fa - (R)(ia - 1);
-                        if (A.taubeam) {
-                            R fm = cosz / dm;
-                            int im = (int)(fm + (R)1.5);
-                            im = im > 2 ? im : 2; im = im < 10 ? im : 10;
-                            fm = fm - (R)(im - 1);
-                            const R c0 = CAIB(im, it, ia);
-                            R xai = (-CAIB(im - 1, it, ia) * ((R)1. - fm) + CAIB(im + 1, it, ia) * ((R)1. + fm)) * fm * (R).5 + c0 * ((R)1. - fm * fm);
-                            xai = xai + (-CAIB(im, it - 1, ia) * ((R)1. - ft) + CAIB(im, it + 1, ia) * ((R)1. + ft)) * ft * (R).5 + c0 * ((R)1. - ft * ft);
-                            xai = xai + (-CAIB(im, it, ia - 1) * ((R)1. - fa) + CAIB(im, it, ia + 1) * ((R)1. + fa)) * fa * (R).5 + c0 * ((R)1. - fa * fa);
-                            xai = xai - (R)2. * c0;
-                            xai = xai > 0 ? xai : (R)0; xai = xai < 1 ? xai : (R)1;
-                            xb = xai;
-                        }
-                        if (A.taudiff) {
-                            const R f0 = CAIF(it, ia);
-                            R xai = (-CAIF(it - 1, ia) * ((R)1. - ft) + CAIF(it + 1, ia) * ((R)1. + ft)) * ft * (R).5 + f0 * ((R)1. - ft * ft);
-                            xai = xai + (-CAIF(it, ia - 1) * ((R)1. - fa) + CAIF(it, ia + 1) * ((R)1. + fa)) * fa * (R).5 + f0 * ((R)1. - fa * fa);
-                            xai = xai - f0;
-                            xai = xai > 0 ? xai : (R)0; xai = xai < 1 ? xai : (R)1;
-                            xf = xai;
-                        }
+                        int it, ia; R ft;
+                        so_cld_index<R>(tauc, fa, it, ia, ft);
+                        if (A.taubeam) xb = so_caib_scale<R>(s_caib, cosz, it, ia, ft, fa);
+                        if (A.taudiff) xf = so_caif_scale<R>(s_caif, it, ia, ft, fa);
                     }
                 }
                 const bool zero = scaled && !cloudy;      // written as the reference's 0., not as 0 * tc (an infinite tc stays a zero)
@@ -168,34 +129,12 @@ template <typename R, bool NIR> GR_DEV void gt_swtau(const GtArgs<R> &A, const S
             }
             if (want_g) {
                 R asy = 1, ssa = (R)0.99999;
-                if (cloudy) {
-                    if (!NIR) {
-                        const R g1 = (T.aig_uv[0] + (T.aig_uv[1] + T.aig_uv[2] * r1) * r1) * tc1;
-                        const R g2 = (T.awg_uv[0] + (T.awg_uv[1] + T.awg_uv[2] * r2) * r2) * tc2;
-                        const R g3 = T.arg_uv[0] * tc3;
-                        const R g4 = (T.aig_uv[0] + (T.aig_uv[1] + T.aig_uv[2] * rs) * rs) * tc4;
-                        asy = (g1 + g2 + g3 + g4) / tauc;
-                    } else {
-                        const R w1 = ((R)1. - (N2(T.aia_nir, 1) + (N2(T.aia_nir, 2) + N2(T.aia_nir, 3) * r1) * r1)) * tc1;
-                        const R w2 = ((R)1. - (N2(T.awa_nir, 1) + (N2(T.awa_nir, 2) + N2(T.awa_nir, 3) * r2) * r2)) * tc2;
-                        const R w3 = ((R)1. - N2(T.ara_nir, 1)) * tc3;
-                        const R w4 = ((R)1. - (N2(T.aia_nir, 1) + (N2(T.aia_nir, 2) + N2(T.aia_nir, 3) * rs) * rs)) * tc4;
-                        ssa = (w1 + w2 + w3 + w4) / tauc;
-                        const R g1 = (N2(T.aig_nir, 1) + (N2(T.aig_nir, 2) + N2(T.aig_nir, 3) * r1) * r1) * w1;
-                        const R g2 = (N2(T.awg_nir, 1) + (N2(T.awg_nir, 2) + N2(T.awg_nir, 3) * r2) * r2) * w2;
-                        const R g3 = N2(T.arg_nir, 1) * w3;
-                        const R g4 = (N2(T.aig_nir, 1) + (N2(T.aig_nir, 2) + N2(T.aig_nir, 3) * r4) * r4) * w4;      // reff(k,4), not the capped value
-                        if (w1 + w2 + w3 + w4 != 0) asy = (g1 + g2 + g3 + g4) / (w1 + w2 + w3 + w4);
-                    }
-                }
+                if (cloudy) so_cld_asy<R, NIR>(T, ib, r1, r2, r4, rs, tc1, tc2, tc3, tc4, tauc, asy, ssa);
                 if (A.asycl) A.asycl[o] = asy;
                 if (NIR && A.ssacl) A.ssacl[o] = ssa;
             }
         }
     }
-#undef CAIB
-#undef CAIF
-#undef N2
 }
 
 template <typename R> __global__ void __launch_bounds__(256) k_getvistau(GtArgs<R> A, const SoradDev<R> *__restrict__ Tp) { gt_swtau<R, false>(A, Tp); }

@@ -22,8 +22,8 @@
 #include <type_traits>
 #include "../../include/geosrad.h"
 #include "lw_device.hpp"
-#include "chou_kernels.hpp"      // gr_log10
-#include "sorad_kernels.hpp"     // SoradDev: the Chou-Suarez SW tables (caif, aib_uv, awb_uv, arb_uv)
+#include "chou_kernels.hpp"
+#include "sorad_kernels.hpp"     // SoradDev: the Chou-Suarez SW tables; so_cld_tau, so_cld_index, so_caif_scale; gr_log10 (lw_kernels.hpp)
 #include "obio_bands.hpp"        // NB_OBIO, OBIO_MAXBANDS, OBIO_MAXPAIRS
 
 namespace geosrad {
@@ -1091,13 +1091,11 @@ __global__ void __launch_bounds__(256, WPS) k_sw_update_clouds(SwCld<R> U, const
     if (!U.optics) return;
 
     const SoradDev<R> &T = *Tp;
-    const R dt = (R)0.30103, da = (R)0.1, t1 = (R)-0.9031;
     const R grav = U.grav, taucrit = U.taucrit;
     const R *__restrict__ ple = U.in[GEOSRAD_SWK_PLE];
     const R *__restrict__ q[4] = {U.in[GEOSRAD_SWK_QI], U.in[GEOSRAD_SWK_QL], U.in[GEOSRAD_SWK_QR], U.in[GEOSRAD_SWK_QS]};
     const R *__restrict__ r[4] = {U.in[GEOSRAD_SWK_RI], U.in[GEOSRAD_SWK_RL], U.in[GEOSRAD_SWK_RR], U.in[GEOSRAD_SWK_RS]};
     // GETVISTAU's cosz (ZTH = max(ZTH,0.0), :6874) enters only its beam scaling (fm, caib), which no export reads: ZTH is not read.
-#define CAIF(a, b) T.caif[((b) - 1) * 9 + ((a) - 1)]
     R th = 0, tm = 0, tl = 0;                 // aTAUH / aTAUM / aTAUL (:7293-7345), summed top down
     int ktop = 0;                             // topmost layer with TAUCLD(:,:,L,1) > TAUCRIT (:7380-7388), 0 = none
     R pup = ple[ij];                          // PLE(k-1)
@@ -1120,28 +1118,16 @@ __global__ void __launch_bounds__(256, WPS) k_sw_update_clouds(SwCld<R> U, const
             const R dp = pl[j] - pup;                                       // DP = PLL(:,:,1:LM)-PLL(:,:,0:LM-1) (:7238)
             const R wp = (dp * (R)1.0e3) / grav;
             const R r1 = re[0][j] * (R)1.e6, r2 = re[1][j] * (R)1.e6, r4 = re[3][j] * (R)1.e6;      // REFF = R? * 1.e6 (:7246-7249)
-            const R tc1 = r1 <= 0 ? (R)0 : (wp * h[0][j]) * T.aib_uv / r1;
-            const R tc2 = r2 <= 0 ? (R)0 : (wp * h[1][j]) * (T.awb_uv[0] + T.awb_uv[1] / r2);
-            const R tc3 = (wp * h[2][j]) * T.arb_uv[0];
-            const R rs = r4 < (R)112.0 ? r4 : (R)112.0;                      // reff_snow = min(reff(k,4),112.0)
-            const R tc4 = rs <= 0 ? (R)0 : (wp * h[3][j]) * T.aib_uv / rs;
+            R tc1, tc2, tc3, tc4, rs;
+            so_cld_tau<R, false>(T, 0, wp, r1, r2, r4, h[0][j], h[1][j], h[2][j], h[3][j], tc1, tc2, tc3, tc4, rs);
             R d1 = 0, d2 = 0, d3 = 0, d4 = 0;                                // taudiff(k,1:4)
             const R tauc = tc1 + tc2 + tc3 + tc4;
             if (tauc > (R)0.02 && f[j] > (R)0.01) {
                 const R cc = k < ict ? ch : (k < icb ? cm : cl);
                 R fa = f[j] / cc;
-                const R tcap = tauc < (R)32. ? tauc : (R)32.;
-                R ft = (gr_log10<R>(tcap) - t1) / dt;
-                fa = fa / da;
-                int it = (int)(ft + (R)1.5), ia = (int)(fa + (R)1.5);
-                it = it > 2 ? it : 2; ia = ia > 2 ? ia : 2;
-                it = it < 8 ? it : 8; ia = ia < 10 ? ia : 10;
-                ft = ft - (R)(it - 1); fa = fa - (R)(ia - 1);
-                const R f0 = CAIF(it, ia);
-                R xai = (-CAIF(it - 1, ia) * ((R)1. - ft) + CAIF(it + 1, ia) * ((R)1. + ft)) * ft * (R).5 + f0 * ((R)1. - ft * ft);
-                xai = xai + (-CAIF(it, ia - 1) * ((R)1. - fa) + CAIF(it, ia + 1) * ((R)1. + fa)) * fa * (R).5 + f0 * ((R)1. - fa * fa);
-                xai = xai - f0;
-                xai = xai > 0 ? xai : (R)0; xai = xai < 1 ? xai : (R)1;
+                int it, ia; R ft;
+                so_cld_index<R>(tauc, fa, it, ia, ft);
+                const R xai = so_caif_scale<R>(T.caif, it, ia, ft, fa);
                 d1 = tc1 * xai; d2 = tc2 * xai; d3 = tc3 * xai; d4 = tc4 * xai;
             }
             if (O[GEOSRAD_SWK_TAUCLI]) O[GEOSRAD_SWK_TAUCLI][o] = d1;
@@ -1154,7 +1140,6 @@ __global__ void __launch_bounds__(256, WPS) k_sw_update_clouds(SwCld<R> U, const
             pup = pl[j];
         }
     }
-#undef CAIF
     const R undef = U.undef;
     const R tx = ct > (R)0. ? (tl * cl + tm * cm + th * ch) / ct : (R)0;       // aTAUT (:7361)
     const R t4[4] = {tl, tm, th, th + tm + tl}, x4[4] = {tl, tm, th, tx};      // TAUT = aTAUH + aTAUM + aTAUL (:7352)

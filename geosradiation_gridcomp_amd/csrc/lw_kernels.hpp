@@ -27,6 +27,9 @@ template <> GR_DEV double gr_exp<double>(double x) { return exp(x); }
 template <typename R> GR_DEV R gr_log(R x);
 template <> GR_DEV float gr_log<float>(float x) { return logf(x); }
 template <> GR_DEV double gr_log<double>(double x) { return log(x); }
+template <typename R> GR_DEV R gr_log10(R x);
+template <> GR_DEV float gr_log10<float>(float x) { return log10f(x); }
+template <> GR_DEV double gr_log10<double>(double x) { return log10(x); }
 template <typename R> GR_DEV R gr_pow(R x, R y);
 template <> GR_DEV float gr_pow<float>(float x, float y) { return powf(x, y); }
 template <> GR_DEV double gr_pow<double>(double x, double y) { return pow(x, y); }

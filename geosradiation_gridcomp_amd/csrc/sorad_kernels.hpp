@@ -230,6 +230,9 @@ __global__ void __launch_bounds__(256) k_sorad_prep(SoradArgs<R> A)
 // OC (-DOVERCAST: getvistau / getnirtau called with ict = icb = 0, sorad.F90:421, 955): every layer of every column, the optical
 // thickness NOT scaled (getvistau.code:7, 173-182) - a layer's condensate counts in full even where fcld <= 0.01; fcld only decides
 // whether the layer gets its own asymmetry factor / single-scattering albedo
+// This kernel keeps its own statement of the optics that so_cld_tau .. so_cld_asy (below) state for the other kernels: their
+// `fp contract(off)` is lexical, this kernel is compiled with contraction on, and the fused multiply-adds the compiler forms here are
+// part of sorad's committed bits (calling them from here turns 8 of 82 v_fma_f32 into separate multiplies and adds).
 template <typename R, bool OC = false>
 __global__ void __launch_bounds__(256) k_sorad_cloud(SoradArgs<R> A, const SoradDev<R> *__restrict__ Tp)
 {
@@ -329,8 +332,98 @@ __global__ void __launch_bounds__(256) k_sorad_cloud(SoradArgs<R> A, const Sorad
 #undef CLD
 #undef CAIB
 #undef CAIF
-#undef N2
 }
+
+// getvistau.code (NIR = false) / getnirtau.code (NIR = true, band ib = 1..3) piece by piece, the reference's statements operation by
+// operation (contraction off): the one statement of k_getvistau, k_getnirtau (all of them) and k_sw_update_clouds (so_cld_tau,
+// so_cld_index, so_caif_scale).  caib / caif are passed as pointers: T.caib / T.caif or a block's LDS copy.  N2: as in k_sorad_cloud.
+// the four species' optical thicknesses; rs = the capped snow radius
+template <typename R, bool NIR>
+GR_DEV void so_cld_tau(const SoradDev<R> &T, int ib, R wp, R r1, R r2, R r4, R h1, R h2, R h3, R h4, R &tc1, R &tc2, R &tc3, R &tc4, R &rs)
+{
+#pragma clang fp contract(off)
+    rs = r4 < (R)112.0 ? r4 : (R)112.0;      // reff_snow = min(reff(k,4),112.0)
+    if (!NIR) {
+        tc1 = r1 <= 0 ? (R)0 : (wp * h1) * T.aib_uv / r1;
+        tc2 = r2 <= 0 ? (R)0 : (wp * h2) * (T.awb_uv[0] + T.awb_uv[1] / r2);
+        tc3 = (wp * h3) * T.arb_uv[0];
+        tc4 = rs <= 0 ? (R)0 : (wp * h4) * T.aib_uv / rs;
+    } else {
+        tc1 = r1 <= 0 ? (R)0 : (wp * h1) * T.aib_nir / r1;
+        tc2 = r2 <= 0 ? (R)0 : (wp * h2) * (N2(T.awb_nir, 1) + N2(T.awb_nir, 2) / r2);
+        tc3 = (wp * h3) * N2(T.arb_nir, 1);
+        tc4 = rs <= 0 ? (R)0 : (wp * h4) * T.aib_nir / rs;
+    }
+}
+// the overlap tables' index step: the cell (it, ia) nearest to (log10 of the capped tauc, fa = fcld / super-layer cover), offsets (ft, fa)
+template <typename R> GR_DEV void so_cld_index(R tauc, R &fa, int &it, int &ia, R &ft)
+{
+#pragma clang fp contract(off)
+    const R dt = (R)0.30103, da = (R)0.1, t1 = (R)-0.9031;
+    const R tcap = tauc < (R)32. ? tauc : (R)32.;
+    ft = (gr_log10<R>(tcap) - t1) / dt;
+    fa = fa / da;
+    it = (int)(ft + (R)1.5); ia = (int)(fa + (R)1.5);
+    it = it > 2 ? it : 2; ia = ia > 2 ? ia : 2;
+    it = it < 8 ? it : 8; ia = ia < 10 ? ia : 10;
+    ft = ft - (R)(it - 1); fa = fa - (R)(ia - 1);
+}
+// the scaling of the beam thickness, caib (11,9,11) at (cosz, it, ia)
+template <typename R> GR_DEV R so_caib_scale(const R *caib, R cosz, int it, int ia, R ft, R fa)
+{
+#pragma clang fp contract(off)
+#define CAIB(a, b, c) caib[(((c) - 1) * 9 + ((b) - 1)) * 11 + ((a) - 1)]
+    R fm = cosz / (R)0.1;
+    int im = (int)(fm + (R)1.5);
+    im = im > 2 ? im : 2; im = im < 10 ? im : 10;
+    fm = fm - (R)(im - 1);
+    const R c0 = CAIB(im, it, ia);
+    R xai = (-CAIB(im - 1, it, ia) * ((R)1. - fm) + CAIB(im + 1, it, ia) * ((R)1. + fm)) * fm * (R).5 + c0 * ((R)1. - fm * fm);
+    xai = xai + (-CAIB(im, it - 1, ia) * ((R)1. - ft) + CAIB(im, it + 1, ia) * ((R)1. + ft)) * ft * (R).5 + c0 * ((R)1. - ft * ft);
+    xai = xai + (-CAIB(im, it, ia - 1) * ((R)1. - fa) + CAIB(im, it, ia + 1) * ((R)1. + fa)) * fa * (R).5 + c0 * ((R)1. - fa * fa);
+    xai = xai - (R)2. * c0;
+    xai = xai > 0 ? xai : (R)0;
+    return xai < 1 ? xai : (R)1;
+#undef CAIB
+}
+// the scaling of the diffuse thickness, caif (9,11) at (it, ia)
+template <typename R> GR_DEV R so_caif_scale(const R *caif, int it, int ia, R ft, R fa)
+{
+#pragma clang fp contract(off)
+#define CAIF(a, b) caif[((b) - 1) * 9 + ((a) - 1)]
+    const R f0 = CAIF(it, ia);
+    R xai = (-CAIF(it - 1, ia) * ((R)1. - ft) + CAIF(it + 1, ia) * ((R)1. + ft)) * ft * (R).5 + f0 * ((R)1. - ft * ft);
+    xai = xai + (-CAIF(it, ia - 1) * ((R)1. - fa) + CAIF(it, ia + 1) * ((R)1. + fa)) * fa * (R).5 + f0 * ((R)1. - fa * fa);
+    xai = xai - f0;
+    xai = xai > 0 ? xai : (R)0;
+    return xai < 1 ? xai : (R)1;
+#undef CAIF
+}
+// asymmetry factor and (NIR) single-scattering albedo of a cloudy layer, tauc = tc1 + tc2 + tc3 + tc4
+template <typename R, bool NIR>
+GR_DEV void so_cld_asy(const SoradDev<R> &T, int ib, R r1, R r2, R r4, R rs, R tc1, R tc2, R tc3, R tc4, R tauc, R &asy, R &ssa)
+{
+#pragma clang fp contract(off)
+    if (!NIR) {
+        const R g1 = (T.aig_uv[0] + (T.aig_uv[1] + T.aig_uv[2] * r1) * r1) * tc1;
+        const R g2 = (T.awg_uv[0] + (T.awg_uv[1] + T.awg_uv[2] * r2) * r2) * tc2;
+        const R g3 = T.arg_uv[0] * tc3;
+        const R g4 = (T.aig_uv[0] + (T.aig_uv[1] + T.aig_uv[2] * rs) * rs) * tc4;
+        asy = (g1 + g2 + g3 + g4) / tauc;
+    } else {
+        const R w1 = ((R)1. - (N2(T.aia_nir, 1) + (N2(T.aia_nir, 2) + N2(T.aia_nir, 3) * r1) * r1)) * tc1;
+        const R w2 = ((R)1. - (N2(T.awa_nir, 1) + (N2(T.awa_nir, 2) + N2(T.awa_nir, 3) * r2) * r2)) * tc2;
+        const R w3 = ((R)1. - N2(T.ara_nir, 1)) * tc3;
+        const R w4 = ((R)1. - (N2(T.aia_nir, 1) + (N2(T.aia_nir, 2) + N2(T.aia_nir, 3) * rs) * rs)) * tc4;
+        ssa = (w1 + w2 + w3 + w4) / tauc;
+        const R g1 = (N2(T.aig_nir, 1) + (N2(T.aig_nir, 2) + N2(T.aig_nir, 3) * r1) * r1) * w1;
+        const R g2 = (N2(T.awg_nir, 1) + (N2(T.awg_nir, 2) + N2(T.awg_nir, 3) * r2) * r2) * w2;
+        const R g3 = N2(T.arg_nir, 1) * w3;
+        const R g4 = (N2(T.aig_nir, 1) + (N2(T.aig_nir, 2) + N2(T.aig_nir, 3) * r4) * r4) * w4;      // reff(k,4), not the capped value
+        if (w1 + w2 + w3 + w4 != 0) asy = (g1 + g2 + g3 + g4) / (w1 + w2 + w3 + w4);
+    }
+}
+#undef N2
 
 // ---------------------------------------------------------------------------------------------------
 // k_sorad_pass<R, CLS>: one thread per (position, spectral pass); every lane of a block belongs to class CLS (which cloud groups hold
@@ -918,13 +1011,8 @@ __global__ void __launch_bounds__(256) k_sorad_col(SoradArgs<R> A, const SoradDe
                     BCP(s_, 0, 0) = tda; BCP(s_, 1, 0) = tta; BCP(s_, 2, 0) = rsa;
                     for (int kk = 1; kk <= np; kk++) {
                         const int j = kk < ict ? ih : (kk < icb ? im : is);
-                        const R rr = BLY(0, j, kk), tt = BLY(1, j, kk), td = BLY(2, j, kk), rs = BLY(3, j, kk), ts = BLY(4, j, kk);
-                        const R denm = so_div(ts, (R)1. - rsa * rs);
-                        // (the reference writes tda*rsa*rr in the high and middle groups and tda*rr*rsa in the low one)
-                        const R x3 = kk < icb ? tda * rsa * rr : tda * rr * rsa;
-                        const R ntta = tda * tt + (x3 + tta - tda) * denm;
-                        const R nrsa = rs + ts * rsa * denm;
-                        tda = tda * td; tta = ntta; rsa = nrsa;
+                        const SoL5<R> l{BLY(0, j, kk), BLY(1, j, kk), BLY(2, j, kk), BLY(3, j, kk), BLY(4, j, kk)};
+                        if (kk < icb) so_add_down<R, false>(l, tda, tta, rsa); else so_add_down<R, true>(l, tda, tta, rsa);
                         BCP(s_, 0, kk) = tda; BCP(s_, 1, kk) = tta; BCP(s_, 2, kk) = rsa;
                     }
                 } else {
@@ -932,10 +1020,7 @@ __global__ void __launch_bounds__(256) k_sorad_col(SoradArgs<R> A, const SoradDe
                     BCP(s_, 3, np + 1) = rra; BCP(s_, 4, np + 1) = rxa;
                     for (int kk = np; kk >= 0; kk--) {
                         const int j = kk >= icb ? is : (kk >= ict ? im : ih);
-                        const R rr = BLY(0, j, kk), tt = BLY(1, j, kk), td = BLY(2, j, kk), rs = BLY(3, j, kk), ts = BLY(4, j, kk);
-                        const R denm = so_div(ts, (R)1. - rs * rxa);
-                        const R nrra = rr + (td * rra + (tt - td) * rxa) * denm;
-                        rxa = rs + ts * rxa * denm; rra = nrra;
+                        so_add_up<R>(SoL5<R>{BLY(0, j, kk), BLY(1, j, kk), BLY(2, j, kk), BLY(3, j, kk), BLY(4, j, kk)}, rra, rxa);
                         BCP(s_, 3, kk) = rra; BCP(s_, 4, kk) = rxa;
                     }
                 }
@@ -1000,6 +1085,22 @@ __global__ void __launch_bounds__(256) k_sorad_col(SoradArgs<R> A, const SoradDe
 // NA (the aerosol-free pass; GEOS_SolarGridComp.F90:3997-4016 keeps FSWNAN, FSCNAN, FSWUNAN, FSCUNAN, FSWBANDNAN of it): flx, flc and
 // flx_sfc_band only - neither the direct / diffuse components nor drband / dfband are formed or written
 // ---------------------------------------------------------------------------------------------------
+// the look-up of both flux reductions (:1440-1475, 1496-1531): the table `tab`, Fortran (nu, nw) with first coordinates u1, w1 and steps du, dw,
+// interpolated linearly from the cell of (ulog, wlog), both capped at the table's end; not below 0
+template <typename R> GR_DEV R so_reduce_lookup(const R *tab, int nu, int nw, R u1, R du, R w1, R dw, R ulog, R wlog)
+{
+#define TAB(a, b) tab[((b) - 1) * nu + ((a) - 1)]
+    const R x0 = u1 + (R)nu * du, y0 = w1 + (R)nw * dw, x1 = u1 - (R)0.5 * du, y1 = w1 - (R)0.5 * dw;
+    ulog = ulog < x0 ? ulog : x0; wlog = wlog < y0 ? wlog : y0;
+    int ic = (int)((ulog - x1) / du + (R)1.), iw = (int)((wlog - y1) / dw + (R)1.);
+    ic = ic > 2 ? ic : 2; iw = iw > 2 ? iw : 2; ic = ic < nu ? ic : nu; iw = iw < nw ? iw : nw;
+    const R dc = ulog - (R)(ic - 2) * du - u1, dd = wlog - (R)(iw - 2) * dw - w1;
+    const R x2 = TAB(ic - 1, iw - 1) + (TAB(ic - 1, iw) - TAB(ic - 1, iw - 1)) / dw * dd;
+    const R y2 = x2 + (TAB(ic, iw - 1) - TAB(ic - 1, iw - 1)) / du * dc;
+#undef TAB
+    return y2 > 0 ? y2 : (R)0;
+}
+
 template <typename R, bool NA = false>
 __global__ void __launch_bounds__(256) k_sorad_reduce(SoradArgs<R> A, const SoradDev<R> *__restrict__ Tp, SoradOut<R> O)
 {
@@ -1034,36 +1135,10 @@ __global__ void __launch_bounds__(256) k_sorad_reduce(SoradArgs<R> A, const Sora
     for (int k = 1; k <= np + 1; k++) {
         if (k > 1) { const R sc = A.lay[((size_t)3 * K2 + (k - 1)) * m + pos]; so2o = so2o + sc * cnt; so2c = so2c + ((R)789. * A.co2) * sc; }
         R df = (R)0.0633 * ((R)1. - gr_exp<R>((R)-0.000155 * sqrt(so2o)));
-        {
-            const R u1 = (R)-3.0, du = (R)0.15, w1 = (R)-4.0, dw = (R)0.15;
-            const R x0 = u1 + (R)43 * du, y0 = w1 + (R)37 * dw, x1 = u1 - (R)0.5 * du, y1 = w1 - (R)0.5 * dw;
-            R ulog = gr_log10<R>(so2c * snt); ulog = ulog < x0 ? ulog : x0;
-            R wlog = gr_log10<R>(A.swh[(size_t)k * m + pos] * snt); wlog = wlog < y0 ? wlog : y0;
-            int ic = (int)((ulog - x1) / du + (R)1.), iw = (int)((wlog - y1) / dw + (R)1.);
-            ic = ic > 2 ? ic : 2; iw = iw > 2 ? iw : 2; ic = ic < 43 ? ic : 43; iw = iw < 37 ? iw : 37;
-            const R dc = ulog - (R)(ic - 2) * du - u1, dd = wlog - (R)(iw - 2) * dw - w1;
-#define CAH(a, b) T.cah[((b) - 1) * 43 + ((a) - 1)]
-            const R x2 = CAH(ic - 1, iw - 1) + (CAH(ic - 1, iw) - CAH(ic - 1, iw - 1)) / dw * dd;
-            R y2 = x2 + (CAH(ic, iw - 1) - CAH(ic - 1, iw - 1)) / du * dc;
-#undef CAH
-            y2 = y2 > 0 ? y2 : (R)0;
-            df = df + (R)1.5 * y2;
-        }
-        {
-            const R u1 = (R)0.000250, du = (R)0.000050, w1 = (R)-2.0, dw = (R)0.05;
-            const R x0 = u1 + (R)62 * du, y0 = w1 + (R)101 * dw, x1 = u1 - (R)0.5 * du, y1 = w1 - (R)0.5 * dw;
-            R ulog = A.co2 * snt; ulog = ulog < x0 ? ulog : x0;
-            R wlog = gr_log10<R>(A.pl[(size_t)(k - 1) * ld + i]); wlog = wlog < y0 ? wlog : y0;
-            int ic = (int)((ulog - x1) / du + (R)1.), iw = (int)((wlog - y1) / dw + (R)1.);
-            ic = ic > 2 ? ic : 2; iw = iw > 2 ? iw : 2; ic = ic < 62 ? ic : 62; iw = iw < 101 ? iw : 101;
-            const R dc = ulog - (R)(ic - 2) * du - u1, dd = wlog - (R)(iw - 2) * dw - w1;
-#define COA(a, b) T.coa[((b) - 1) * 62 + ((a) - 1)]
-            const R x2 = COA(ic - 1, iw - 1) + (COA(ic - 1, iw) - COA(ic - 1, iw - 1)) / dw * dd;
-            R y2 = x2 + (COA(ic, iw - 1) - COA(ic - 1, iw - 1)) / du * dc;
-#undef COA
-            y2 = y2 > 0 ? y2 : (R)0;
-            df = df + (R)1.5 * y2;
-        }
+        df = df + (R)1.5 * so_reduce_lookup<R>(T.cah, 43, 37, (R)-3.0, (R)0.15, (R)-4.0, (R)0.15, gr_log10<R>(so2c * snt),
+                                               gr_log10<R>(A.swh[(size_t)k * m + pos] * snt));
+        df = df + (R)1.5 * so_reduce_lookup<R>(T.coa, 62, 101, (R)0.000250, (R)0.000050, (R)-2.0, (R)0.05, A.co2 * snt,
+                                               gr_log10<R>(A.pl[(size_t)(k - 1) * ld + i]));
         // below the cloud top the reduction scales with the all-sky flux, Eq. (6.18)
         if (k == ntop) dftop = df;
         R fl = OUT2(O.flx, k);

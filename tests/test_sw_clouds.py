@@ -371,6 +371,56 @@ def test_each_export_alone_gives_the_same_bits(gpu_ctx, rk):
         np.testing.assert_array_equal(nozth[k], full[k], err_msg=k)
 
 
+def _shared_optics_fields(dt, ncol=70, lm=9):
+    """70 columns (a full wavefront and a partial one) x 9 layers (getvistau's run of 8 layers and a tail of one; an odd tail of this
+    kernel's two-layer walk), super-layers 1-2 / 3-5 / 6-9: condensate over five decades, covers and radii with every special case"""
+    rng = np.random.default_rng(41)
+    f = {"PLE": np.linspace(1000.0, 100000.0, lm + 1)[:, None] * rng.uniform(0.97, 1.03, ncol), "ZTH": rng.uniform(0.05, 1.0, ncol),
+         "T": rng.uniform(210.0, 290.0, (lm, ncol)), "FCLD": rng.uniform(0.0, 1.0, (lm, ncol))}
+    f["FCLD"][rng.uniform(0, 1, (lm, ncol)) < 0.15] = 0.005
+    f["FCLD"][rng.uniform(0, 1, (lm, ncol)) < 0.10] = 0.0
+    for q in ("QI", "QL", "QR", "QS"):
+        f[q] = 10.0 ** rng.uniform(-8.0, -3.0, (lm, ncol))
+    for r, (lo, hi) in (("RI", (15e-6, 60e-6)), ("RL", (6e-6, 20e-6)), ("RR", (50e-6, 200e-6)), ("RS", (40e-6, 200e-6))):
+        f[r] = rng.uniform(lo, hi, (lm, ncol))
+        f[r][rng.uniform(0, 1, (lm, ncol)) < 0.08] = 0.0
+        f[r][rng.uniform(0, 1, (lm, ncol)) < 0.04] = -1e-6
+    return {k: np.ascontiguousarray(v, dtype=dt) for k, v in f.items()}, 3, 6
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rk", [4, 8])
+def test_species_thicknesses_are_getvistaus_taudiff_bit_for_bit(gpu_ctx, rk):
+    """TAUCLI / TAUCLW / TAUCLR / TAUCLS = geosrad_getvistau_dev's taudiff(:,:,1:4) on the same fields, bit for bit: both kernels take
+    the species' thicknesses, the table index step and the caif scaling from the same device functions"""
+    import torch
+    ctx = gpu_ctx[rk]; dt = ctx.dtype
+    f, mh, ml = _shared_optics_fields(dt)
+    lm, ncol = f["FCLD"].shape
+    assert (ncol, lm, mh, ml) == (70, 9, 3, 6)
+    tauc = _unscaled(f, dt).astype(dt).sum(axis=0, dtype=dt)
+    cloudy = (tauc > dt(0.02)) & (f["FCLD"] > dt(0.01))
+    assert (tauc <= dt(0.02)).any() and (tauc > dt(32.)).any() and (f["FCLD"] <= dt(0.01)).any()
+    assert all((f[r] <= 0).any() for r in ("RI", "RL", "RS")) and (f["RS"] * dt(1.e6) > dt(112.0)).any()
+    assert cloudy[:mh - 1].any() and cloudy[mh - 1:ml - 1].any() and cloudy[ml - 1:].any() and (tauc[cloudy] > dt(32.)).any()
+    names = ["TAUCLI", "TAUCLW", "TAUCLR", "TAUCLS"]
+    got = _run(ctx, f, mh, ml, names=names)
+    a = {"cosz": f["ZTH"], "dp": f["PLE"][1:] - f["PLE"][:-1], "fcld": f["FCLD"],
+         "reff": np.stack([f[k] * dt(1.e6) for k in ("RI", "RL", "RR", "RS")]), "hydromets": np.stack([f[k] for k in ("QI", "QL", "QR", "QS")])}
+    assert all(v.dtype == dt for v in a.values())
+    t = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in a.items()}
+    t["taudiff"] = torch.full((4, lm, ncol), -7.0, dtype=t["dp"].dtype, device="cuda")
+    try:
+        ctx.getvistau_dev(_stream(), ncol, lm, {k: v.data_ptr() for k, v in t.items()}, mh, ml, grav=9.80665)
+        ctx.check(_stream())
+    finally:
+        torch.cuda.synchronize()
+    taudiff = t["taudiff"].cpu().numpy()
+    assert (taudiff[:, cloudy] > 0).any() and (taudiff[:, ~cloudy] == 0).all()
+    for s, k in enumerate(names):
+        np.testing.assert_array_equal(got[k].view(np.uint32 if rk == 4 else np.uint64), taudiff[s].view(np.uint32 if rk == 4 else np.uint64), err_msg=k)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("rk", [4, 8])
 def test_null_exports_untouched_and_einval_writes_nothing(gpu_ctx, rk):
