@@ -64,7 +64,10 @@ class GeosradInputError(GeosradError):
 def _params(name):
     """((parameter, int | float for a scalar, None for a pointer), ...) of the library function `name`, in the order of include/geosrad.h"""
     protos = _lib.all_prototypes()
-    return tuple((p, _SCALAR.get(t)) for t, p in (protos[name] if name in protos else _lib.satsim_prototypes()[name])[1])
+    for more in (_lib.satsim_prototypes, _lib.misr_modis_prototypes):
+        if name not in protos:
+            protos = more()
+    return tuple((p, _SCALAR.get(t)) for t, p in protos[name][1])
 
 
 def _args(name, vals):
@@ -496,6 +499,61 @@ class Context:
         (int32) and of the wanted outputs fq_isccp ... boxptop, SGFCLD (lm, npoints)."""
         up = ("T", "QV", "FCLD", "CCA", "PLE", "PLO", "DTAU_S", "EMISS", "DTAU_C", "DEM_C", "TS", "SGFCLD")
         self._dev("geosrad_isccp_dev", ptr, {k.lower(): k for k in up}, stream=stream, npoints=npoints, lm=lm, ncol=ncol, overlap=overlap,
+                  top_height=top_height, top_height_direction=top_height_direction, emsfc_lw=emsfc_lw)
+
+    # ---- the MISR simulator (include/geosrad_misr_modis.h) --------------------------------------------------------------------
+    MISR_OUT = ("fq_MISR_TAU_v_CTH", "dist_model_layertops", "MISR_mean_ztop", "MISR_cldarea")
+
+    def misr(self, npoints, nlev, ncol, sunlit, zfull, at, dtau_s, dtau_c, frac_out, missing_value, want=MISR_OUT):
+        """MISR_simulator (MISR_simulator.f) in its own argument order: arrays (nlev, npoints) TOA first, frac_out (nlev, ncol, npoints) in
+        the real kind, sunlit int32 (npoints).  Returns dict(fq_MISR_TAU_v_CTH (16 heights, 7 tau, npoints); dist_model_layertops (16,
+        npoints); MISR_mean_ztop, MISR_cldarea (npoints)) of the names in `want`.  The pattern matcher works on the call's first point only
+        and a dark point's MISR_mean_ztop is 0 unless it is the call's last: the reference's behaviour (include/geosrad_misr_modis.h)."""
+        a = {k: v for k, v in locals().items() if k not in ("self", "want", "sunlit")}
+        unknown = set(want) - set(self.MISR_OUT)
+        if unknown:
+            raise TypeError(f"geosrad_misr: no output {sorted(unknown)}")
+        shapes = {"fq_MISR_TAU_v_CTH": (16, 7, npoints), "dist_model_layertops": (16, npoints)}
+        out = self._zeros([(k, shapes.get(k, (npoints,))) for k in self.MISR_OUT if k in want])
+        self._host("geosrad_misr", a, out, sunlit=np.ascontiguousarray(sunlit, dtype=np.int32))
+        return out
+
+    def misr_dev(self, stream, npoints, nlev, ncol, ptr, missing_value):
+        """`ptr`: name -> device address of sunlit (int32), zfull, at, dtau_s, dtau_c, frac_out_u8 (one byte per cell) and of the wanted
+        outputs fq_MISR_TAU_v_CTH, dist_model_layertops, MISR_mean_ztop, MISR_cldarea (missing = NULL)."""
+        self._dev("geosrad_misr_dev", ptr, stream=stream, npoints=npoints, nlev=nlev, ncol=ncol, missing_value=missing_value)
+
+    # ---- the MODIS simulator and the whole COSP path (include/geosrad_misr_modis.h) ------------------------------------------
+    MODIS_OUT = ("modis_mean", "modis_hist", "phase", "ctp", "tau", "size")
+    MODIS_MEAN = ("cf_total", "cf_water", "cf_ice", "cf_high", "cf_mid", "cf_low", "tau_total", "tau_water", "tau_ice", "logtau_total", "logtau_water",
+                  "logtau_ice", "size_water", "size_ice", "ctp_total", "lwp", "iwp")          # the GEOSRAD_MODIS_* indices of modis_mean
+
+    def modis(self, npoints, nlev, ncol, sunlit, t, p, ph, dtau_s, dtau_c, frac_out, mr_lsliq, mr_lsice, mr_cvliq, mr_cvice, reff_lsliq,
+              reff_lsice, reff_cvliq, reff_cvice, isccp_boxtau, isccp_boxptop, want=("modis_mean", "modis_hist")):
+        """COSP_Modis_Simulator on gridbox-level fields (nlev, npoints) TOA first, ph (nlev + 1, npoints), frac_out (nlev, ncol, npoints) in the
+        real kind, isccp_boxtau / isccp_boxptop (ncol, npoints); dtau_c and the convective arrays may be None (zero), isccp_boxtau too (not
+        read).  Returns dict(modis_mean (17, npoints) in MODIS_MEAN's order; modis_hist (7 pressure, 7 tau, npoints); phase int32, ctp, tau,
+        size (ncol, npoints)) of the names in `want`; -1.0E30 where the reference leaves R_UNDEF."""
+        a = {k: v for k, v in locals().items() if k not in ("self", "want", "sunlit")}
+        unknown = set(want) - set(self.MODIS_OUT)
+        if unknown:
+            raise TypeError(f"geosrad_modis: no output {sorted(unknown)}")
+        shapes = {"modis_mean": (17, npoints), "modis_hist": (7, 7, npoints)}
+        out = {k: np.zeros(shapes.get(k, (ncol, npoints)), dtype=np.int32 if k == "phase" else self.dtype) for k in self.MODIS_OUT if k in want}
+        self._host("geosrad_modis", a, out, sunlit=np.ascontiguousarray(sunlit, dtype=np.int32))
+        return out
+
+    def modis_dev(self, stream, npoints, nlev, ncol, ptr):
+        """`ptr`: name -> device address of sunlit (int32), t, p, ph, dtau_s, dtau_c, frac_out_u8, mr_lsliq ... reff_cvice, isccp_boxtau,
+        isccp_boxptop and of the wanted outputs modis_mean, modis_hist, phase (int32), ctp, tau, size (missing = NULL)."""
+        self._dev("geosrad_modis_dev", ptr, stream=stream, npoints=npoints, nlev=nlev, ncol=ncol)
+
+    def cosp_dev(self, stream, npoints, lm, ncol, ptr, overlap=3, top_height=1, top_height_direction=2, emsfc_lw=0.999):
+        """call COSP with the ISCCP, MISR and MODIS simulators on, on GEOS fields in model order: `ptr` as for isccp_dev, plus ZLE (lm + 1,
+        npoints), QLTOT, QITOT, RDFL, RDFI (lm, npoints) and the wanted outputs fq_MISR_TAU_v_CTH, dist_model_layertops, MISR_mean_ztop,
+        MISR_cldarea, modis_mean, modis_hist.  An output group that is missing altogether skips that simulator."""
+        up = ("T", "QV", "FCLD", "CCA", "PLE", "PLO", "DTAU_S", "EMISS", "DTAU_C", "DEM_C", "TS", "SGFCLD", "ZLE", "QLTOT", "QITOT", "RDFL", "RDFI")
+        self._dev("geosrad_cosp_dev", ptr, {k.lower(): k for k in up}, stream=stream, npoints=npoints, lm=lm, ncol=ncol, overlap=overlap,
                   top_height=top_height, top_height_direction=top_height_direction, emsfc_lw=emsfc_lw)
 
     # ---- Chou-Suarez SW, host arrays ---------------------------------------------------------------------

@@ -25,6 +25,7 @@
 #include "../../include/geosrad.h"
 #include "../../include/geosrad_gettau.h"
 #include "../../include/geosrad_satsim.h"
+#include "../../include/geosrad_misr_modis.h"
 #include "dev_buf.hpp"
 #include "lw_device.hpp"
 #include "lw_kernels.hpp"
@@ -36,6 +37,7 @@
 #include "gridcomp_kernels.hpp"
 #include "gettau_kernels.hpp"
 #include "satsim_kernels.hpp"
+#include "misr_modis_kernels.hpp"
 #include "lw_cols.hpp"
 #include "lw_split.hpp"
 #include "sw_reform.hpp"
@@ -664,6 +666,7 @@ struct geosrad_ctx {
         bool cosp = false;
         int32_t *seed = nullptr;
         void *sgfcld = nullptr;
+        bool scops_only = false;        // geosrad_cosp_dev with neither an ISCCP output nor MODIS wanted: SCOPS, the seeds and SGFCLD only
     };
     // the argument rules of include/geosrad_satsim.h, the same for every kind of context
     int satsim_check(const char *who, int npoints, int nlev, int ncol, int overlap, int top_height, int top_height_direction)
@@ -698,6 +701,61 @@ struct geosrad_ctx {
     virtual int icarus_dev(hipStream_t, const IcarusCall &C) { return nodev(C.cosp ? "geosrad_isccp_dev" : "geosrad_icarus_dev"); }
     virtual int icarus_host(const IcarusCall &) = 0;
     virtual int cosp_seeds_dev(hipStream_t, int, const void *, int32_t *) { return nodev("geosrad_cosp_seeds_dev"); }
+    // the MISR simulator (include/geosrad_misr_modis.h): one record, shared by the `_dev` and the host variant
+    enum MisrIn { MI_ZFULL, MI_AT, MI_DTAU_S, MI_DTAU_C, MI_NIN };
+    enum MisrOut { MIO_FQ, MIO_DIST, MIO_ZTOP, MIO_AREA, MIO_NOUT };
+    struct MisrCall {
+        int npoints, nlev, ncol;
+        double missing_value;
+        const int32_t *sunlit;
+        const void *in[MI_NIN];
+        const void *frac_out;           // bytes (`_dev`) or reals (host)
+        void *out[MIO_NOUT];
+        // whether the points of this record begin / end the caller's: the pattern matcher works on the call's first point and a dark
+        // last point of the call gets missing_value in MISR_mean_ztop; a chunk or a shard in the middle has neither
+        bool first = true, last = true;
+    };
+    int misr_check(const MisrCall &C)
+    {
+        if (const int rc = satsim_check("geosrad_misr", C.npoints, C.nlev, C.ncol, 1, 1, 1)) return rc;
+        // MISR_simulator.f:294-313: with one sub-column the pattern matcher couples neighbouring points in one serial scan over the grid
+        if (C.ncol == 1) return fail(GEOSRAD_EINVAL, "geosrad_misr: ncol must be at least 2 (ncol = 1 is the reference's serial scan over the points)");
+        for (int k = 0; k < MI_NIN; k++)
+            if (!C.in[k]) return fail(GEOSRAD_EINVAL, "geosrad_misr: null input array");
+        if (!C.sunlit || !C.frac_out) return fail(GEOSRAD_EINVAL, "geosrad_misr: null input array");
+        return GEOSRAD_OK;
+    }
+    virtual int misr_dev(hipStream_t, const MisrCall &) { return nodev("geosrad_misr_dev"); }
+    virtual int misr_host(const MisrCall &) = 0;
+    // the MODIS simulator: one record, shared by the `_dev` and the host variant
+    enum ModisIn { MDI_T, MDI_P, MDI_PH, MDI_DTAU_S, MDI_DTAU_C, MDI_MR, MDI_REFF = MDI_MR + 4, MDI_BOXTAU = MDI_REFF + 4, MDI_BOXPTOP, MDI_NIN };
+    enum ModisOut { MDO_MEAN, MDO_HIST, MDO_PHASE, MDO_CTP, MDO_TAU, MDO_SIZE, MDO_NOUT };
+    struct ModisCall {
+        int npoints, nlev, ncol;
+        const int32_t *sunlit;
+        const void *in[MDI_NIN];        // dtau_c and the convective contents and radii may be null (zero); boxtau is not read
+        const void *frac_out;           // bytes (`_dev`) or reals (host)
+        void *out[MDO_NOUT];
+        bool geos = false;              // geosrad_cosp_dev: in[MDI_PH] is PLE (npoints,0:lm), the water contents are clamped at 0
+    };
+    static bool modis_optional(int k) { return k == MDI_DTAU_C || k == MDI_MR + 2 || k == MDI_MR + 3 || k == MDI_REFF + 2 || k == MDI_REFF + 3 || k == MDI_BOXTAU; }
+    int modis_check(const ModisCall &C)
+    {
+        if (const int rc = satsim_check("geosrad_modis", C.npoints, C.nlev, C.ncol, 1, 1, 1)) return rc;
+        for (int k = 0; k < MDI_NIN; k++)
+            if (!C.in[k] && !modis_optional(k)) return fail(GEOSRAD_EINVAL, "geosrad_modis: null input array");
+        if (!C.sunlit || !C.frac_out) return fail(GEOSRAD_EINVAL, "geosrad_modis: null input array");
+        return GEOSRAD_OK;
+    }
+    virtual int modis_dev(hipStream_t, const ModisCall &) { return nodev("geosrad_modis_dev"); }
+    virtual int modis_host(const ModisCall &) = 0;
+    // geosrad_cosp_dev: the record of geosrad_isccp_dev and what MISR and MODIS need beside it
+    struct CospCall {
+        IcarusCall ic;
+        const void *zle, *qltot, *qitot, *rdfl, *rdfi;
+        void *misr[MIO_NOUT], *modis[2];
+    };
+    virtual int cosp_dev(hipStream_t, const CospCall &) { return nodev("geosrad_cosp_dev"); }
 };
 
 // order of the `in` / `out` pointer arrays of sw_dev / sw_host
@@ -773,6 +831,11 @@ static inline ArrShape gt_out_shape(int kind, int k, size_t L) { return {kind ==
 // icarus: the inputs of IcIn, the outputs of IcOut (L levels, S sub-columns); frac_out is (S * L) rows
 static inline ArrShape ic_in_shape(int k, size_t L) { return {k == geosrad_ctx::IC_PHALF ? L + 1 : k == geosrad_ctx::IC_SKT ? 1 : L, 1}; }
 static inline ArrShape ic_out_shape(int k, size_t S) { return {k == geosrad_ctx::ICO_FQ ? 49 : k >= geosrad_ctx::ICO_BOXTAU ? S : 1, 1}; }
+// misr: every input of MisrIn is (npoints,L); the outputs of MisrOut
+// modis: the inputs of ModisIn and the outputs of ModisOut (L levels, S sub-columns)
+static inline ArrShape modis_in_shape(int k, size_t L, size_t S) { return {k == geosrad_ctx::MDI_PH ? L + 1 : k >= geosrad_ctx::MDI_BOXTAU ? S : L, 1}; }
+static inline ArrShape modis_out_shape(int k, size_t S) { return {k == geosrad_ctx::MDO_MEAN ? (size_t)17 : k == geosrad_ctx::MDO_HIST ? (size_t)49 : S, 1}; }
+static inline ArrShape misr_out_shape(int k) { return {k == geosrad_ctx::MIO_FQ ? (size_t)(7 * 16) : k == geosrad_ctx::MIO_DIST ? (size_t)16 : (size_t)1, 1}; }
 
 // The arrays of one host-pointer call, added in host_pipeline's order (copied in only, both ways, back only).  src: copied in, dst:
 // copied back (null: the array only has its place on the device).  *at receives the array's device address before the solver is
@@ -1025,7 +1088,7 @@ template <typename R> struct Ctx : geosrad_ctx {
     size_t workspace_bytes() const override
     {
         size_t t = 0;
-        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_ws_hb, &d_ws_ss, &d_zero, &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
+        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_ws_hb, &d_ws_ss, &d_ws_misr, &d_ws_modis, &d_zero, &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
             t += b->bytes;
         return t;
     }
@@ -2037,20 +2100,28 @@ template <typename R> struct Ctx : geosrad_ctx {
     {
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamSynchronize(st));
-        uint32_t e2[4] = {0, 0, 0, 0};
-        HIPCHK(hipMemcpy(e2, d_err, 16, hipMemcpyDeviceToHost));
+        uint32_t e2[5] = {0, 0, 0, 0, 0};
+        HIPCHK(hipMemcpy(e2, d_err, 20, hipMemcpyDeviceToHost));
         // slot 0 = RRTMG_LW (+ McICA), slot 1 = RRTMG_SW; the Chou schemes have no input assertions (neither has the reference).
         // The host-pointer entry points look at their own solver's slot only (a flag left by an unchecked `_dev` call of the other
         // solver is that call's to report); geosrad_check reports either.  Only the slot that is reported is cleared - with the two
         // solvers on two streams the other one's flag stays up for the check of its own stream - and it is cleared in stream order
         // on `st`, so a kernel of the other solver running on another stream cannot lose a bit to it.
-        // slot 3 = the range check of ICARUS (icarus.f:403-455), reported last
-        if (which == 0) e2[1] = e2[3] = 0;
-        if (which == 1) e2[0] = e2[3] = 0;
-        if (which == 3) e2[0] = e2[1] = 0;
-        if (!e2[0] && !e2[1] && !e2[3]) return GEOSRAD_OK;
-        HIPCHK(hipMemsetAsync(d_err + (e2[1] ? 1 : e2[0] ? 0 : 3), 0, 4, st));
+        // slot 3 = the range check of ICARUS (icarus.f:403-455), slot 4 = that of MODIS (modis_simulator.F90:202-206), reported last
+        // (slot 2 is k_chou_prep's and is not looked at here)
+        if (which == 0) e2[1] = e2[3] = e2[4] = 0;
+        if (which == 1) e2[0] = e2[3] = e2[4] = 0;
+        if (which == 3) e2[0] = e2[1] = e2[4] = 0;
+        if (which == 4) e2[0] = e2[1] = e2[3] = 0;
+        if (!e2[0] && !e2[1] && !e2[3] && !e2[4]) return GEOSRAD_OK;
+        HIPCHK(hipMemsetAsync(d_err + (e2[1] ? 1 : e2[0] ? 0 : e2[3] ? 3 : 4), 0, 4, st));
         HIPCHK(hipStreamSynchronize(st));
+        if (!e2[0] && !e2[1] && !e2[3]) {
+            static const char *MD_NAMES[MDERR_N] = {"t", "p", "dtau_s", "dtau_c", "reff_lsliq", "reff_lsice", "reff_cvliq", "reff_cvice"};
+            for (int k = 0; k < MDERR_N; k++)
+                if (e2[4] & (1u << k)) return fail(GEOSRAD_EINPUT, std::string("Input values out of bounds: ") + MD_NAMES[k]);
+            return fail(GEOSRAD_EINPUT, "device-side input check failed (modis)");
+        }
         if (!e2[0] && !e2[1]) {
             static const char *IC_NAMES[6] = {"cc", "conv", "dtau_s", "dtau_c", "dem_s", "dem_c"};
             for (int k = 0; k < 6; k++)
@@ -2086,9 +2157,14 @@ template <typename R> struct Ctx : geosrad_ctx {
     // without assertions, the caller synchronises.
     int host_call(int ncol, HostArrs &H, int which, const std::function<int(hipStream_t, int)> &run)
     {
-        auto chunk = [&](hipStream_t st, int nc, int, char *dev, int) -> int {
+        return host_call_at(ncol, H, which, [&](hipStream_t st, int nc, int) { return run(st, nc); });
+    }
+    // the same for a solver that has to know where in the call its chunk lies: run(stream, columns, first column)
+    int host_call_at(int ncol, HostArrs &H, int which, const std::function<int(hipStream_t, int, int)> &run)
+    {
+        auto chunk = [&](hipStream_t st, int nc, int c0, char *dev, int) -> int {
             for (size_t i = 0; i < H.arrs.size(); i++) *H.at[i] = dev + H.arrs[i].off;
-            return run(st, nc);
+            return run(st, nc, c0);
         };
         if (which < 0) return host_pipeline(ncol, H.arrs, chunk);
         int rc = clear_slot(which);
@@ -2931,6 +3007,7 @@ template <typename R> struct Ctx : geosrad_ctx {
             // SCOPS takes FCLD / CCA as they are (cosp.F90:392-397); the 0.999999 of cosp_isccp_simulator.F90:65-66 is on icarus' arguments only
             if (const int rc = scops_launch(st, S, w.seed0)) return rc;
             if (C.sgfcld) hipLaunchKernelGGL((k_sgfcld<R>), dim3(grid256(np), C.nlev), dim3(256), 0, st, np, C.ncol, (const uint8_t *)w.mask, (R *)C.sgfcld);
+            if (C.scops_only) { HIPCHK(hipGetLastError()); return GEOSRAD_OK; }
         }
         IcArgs<R> A{};
         A.npoints = np; A.nlev = C.nlev; A.ncol = C.ncol; A.top_height = C.top_height; A.top_height_direction = C.top_height_direction;
@@ -3011,6 +3088,176 @@ template <typename R> struct Ctx : geosrad_ctx {
             hipLaunchKernelGGL((k_real_to_mask<R>), dim3(grid256(nn)), dim3(256), 0, st, nn, (const R *)frac_at, (uint8_t *)u8_at);
             return icarus_dev(st, D);
         });
+    }
+
+    // =====================================================================================================
+    // the MISR simulator (include/geosrad_misr_modis.h; misr_modis_kernels.hpp)
+    // =====================================================================================================
+    DevBuf<> d_ws_misr;      // two (npoints,ncol) planes: a sub-column's optical depth and its MISR cloud-top height
+    int misr_dev(hipStream_t st, const MisrCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = misr_check(C)) return rc;
+        return misr_launch(st, C);
+    }
+    // the two kernels on a record that misr_check has passed (a chunk of misr_host's: checked once for the call)
+    int misr_launch(hipStream_t st, const MisrCall &C)
+    {
+        const size_t ps = (size_t)C.npoints * C.ncol;
+        if (d_ws_misr.reserve(2 * ps * sizeof(R)) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the MISR simulator's workspace failed");
+        MisrArgs<R> A{};
+        A.npoints = C.npoints; A.nlev = C.nlev; A.ncol = C.ncol; A.first = C.first; A.last = C.last; A.missing_value = (R)C.missing_value;
+        A.sunlit = C.sunlit;
+        A.zfull = (const R *)C.in[MI_ZFULL]; A.at = (const R *)C.in[MI_AT]; A.dtau_s = (const R *)C.in[MI_DTAU_S]; A.dtau_c = (const R *)C.in[MI_DTAU_C];
+        A.frac = (const uint8_t *)C.frac_out;
+        A.tau = (R *)d_ws_misr.p; A.ztop = A.tau + ps;
+        A.fq = (R *)C.out[MIO_FQ]; A.dist = (R *)C.out[MIO_DIST]; A.mean_ztop = (R *)C.out[MIO_ZTOP]; A.cldarea = (R *)C.out[MIO_AREA];
+        hipLaunchKernelGGL((k_misr_box<R>), dim3(grid256(ps)), dim3(256), 0, st, A);
+        hipLaunchKernelGGL((k_misr_stats<R>), dim3((unsigned)((C.npoints + MISR_STATS_T - 1) / MISR_STATS_T)), dim3(MISR_STATS_T), 0, st, A);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+    // host arrays through the chunk pipeline: chunks split the points; only the chunk that holds the call's first / last point gets the
+    // record's `first` / `last`
+    int misr_host(const MisrCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = misr_check(C)) return rc;
+        HostArrs H(sizeof(R));
+        MisrCall D = C;
+        const void *sun_at = nullptr, *frac_at = nullptr, *u8_at = nullptr;
+        const size_t cells = (size_t)C.ncol * C.nlev;
+        for (int k = 0; k < MI_NIN; k++) H.add(C.in[k], nullptr, {(size_t)C.nlev, 1}, &D.in[k]);
+        H.add(C.sunlit, nullptr, {1, 1}, &sun_at, sizeof(int32_t));
+        H.add(C.frac_out, nullptr, {cells, 1}, &frac_at);
+        H.add(nullptr, nullptr, {cells, 1}, &u8_at, 1);
+        for (int k = 0; k < MIO_NOUT; k++) { D.out[k] = nullptr; if (C.out[k]) H.add(nullptr, C.out[k], misr_out_shape(k), &D.out[k]); }
+        const int rc = host_call_at(C.npoints, H, -1, [&](hipStream_t st, int nc, int c0) {
+            D.npoints = nc; D.sunlit = (const int32_t *)sun_at; D.frac_out = u8_at;
+            D.first = C.first && c0 == 0; D.last = C.last && c0 + nc == C.npoints;
+            const size_t nn = cells * nc;
+            hipLaunchKernelGGL((k_real_to_mask<R>), dim3(grid256(nn)), dim3(256), 0, st, nn, (const R *)frac_at, (uint8_t *)u8_at);
+            return misr_launch(st, D);
+        });
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(stream));
+        return GEOSRAD_OK;
+    }
+
+    // =====================================================================================================
+    // the MODIS simulator and the whole COSP path (include/geosrad_misr_modis.h; misr_modis_kernels.hpp)
+    // =====================================================================================================
+    DevBuf<> d_ws_modis;      // two (npoints,nlev) planes, four (npoints,ncol) planes; for geosrad_cosp_dev zfull and boxptop too
+    const ModisTab<R> md_tab = md_tables<R>();
+    struct MdWs { R *frac_ls, *frac_cv, *ctp, *tau, *size, *zfull, *boxptop; int32_t *phase; };
+    size_t md_layout(int np, int nlev, int ncol, bool cosp, MdWs &w, Carve c) const
+    {
+        const size_t pl = (size_t)np * nlev, ps = (size_t)np * ncol;
+        w.frac_ls = c.take<R>(pl); w.frac_cv = c.take<R>(pl); w.ctp = c.take<R>(ps); w.tau = c.take<R>(ps); w.size = c.take<R>(ps);
+        w.phase = c.take<int32_t>(ps);
+        w.zfull = c.take<R>(cosp ? pl : 0); w.boxptop = c.take<R>(cosp ? ps : 0);
+        return c.off;
+    }
+    bool md_cosp = false;      // once taken, the two planes of geosrad_cosp_dev stay part of the layout
+    int md_workspace(int np, int nlev, int ncol, bool cosp, MdWs &w)
+    {
+        md_cosp |= cosp;
+        if (d_ws_modis.reserve(md_layout(np, nlev, ncol, md_cosp, w, Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the MODIS simulator's workspace failed");
+        md_layout(np, nlev, ncol, md_cosp, w, Carve(d_ws_modis.p));
+        return GEOSRAD_OK;
+    }
+    int modis_dev(hipStream_t st, const ModisCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = modis_check(C)) return rc;
+        return modis_launch(st, C);
+    }
+    // the three kernels on a record that modis_check has passed
+    int modis_launch(hipStream_t st, const ModisCall &C)
+    {
+        MdWs w;
+        if (const int rc = md_workspace(C.npoints, C.nlev, C.ncol, false, w)) return rc;
+        const int np = C.npoints;
+        ModisArgs<R> A{};
+        A.npoints = np; A.nlev = C.nlev; A.ncol = C.ncol; A.ple_shift = C.geos; A.clamp_mr = C.geos;
+        A.sunlit = C.sunlit;
+        auto I = [&](int k) { return (const R *)C.in[k]; };
+        A.t = I(MDI_T); A.p = I(MDI_P); A.ph = I(MDI_PH); A.dtau_s = I(MDI_DTAU_S); A.dtau_c = I(MDI_DTAU_C);
+        for (int k = 0; k < 4; k++) { A.mr[k] = I(MDI_MR + k); A.reff[k] = I(MDI_REFF + k); }
+        A.boxptop = I(MDI_BOXPTOP);
+        A.frac = (const uint8_t *)C.frac_out;
+        A.frac_ls = w.frac_ls; A.frac_cv = w.frac_cv; A.phase = w.phase; A.ctp = w.ctp; A.tau = w.tau; A.size = w.size;
+        A.err = d_err + 4;
+        A.mean = (R *)C.out[MDO_MEAN]; A.hist = (R *)C.out[MDO_HIST];
+        A.o_phase = (int32_t *)C.out[MDO_PHASE]; A.o_ctp = (R *)C.out[MDO_CTP]; A.o_tau = (R *)C.out[MDO_TAU]; A.o_size = (R *)C.out[MDO_SIZE];
+        A.tab = md_tab;
+        hipLaunchKernelGGL((k_cosp_fracs<R>), dim3(grid256(np), C.nlev), dim3(256), 0, st, A);
+        hipLaunchKernelGGL((k_modis_box<R>), dim3(grid256((size_t)np * C.ncol)), dim3(256), 0, st, A);
+        hipLaunchKernelGGL((k_modis_stats<R>), dim3((unsigned)((np + MD_STATS_T - 1) / MD_STATS_T)), dim3(MD_STATS_T), 0, st, A);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+    int modis_host(const ModisCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = modis_check(C)) return rc;
+        HostArrs H(sizeof(R));
+        ModisCall D = C;
+        const void *sun_at = nullptr, *frac_at = nullptr, *u8_at = nullptr;
+        const size_t cells = (size_t)C.ncol * C.nlev;
+        for (int k = 0; k < MDI_NIN; k++) { D.in[k] = nullptr; if (C.in[k] && k != MDI_BOXTAU) H.add(C.in[k], nullptr, modis_in_shape(k, C.nlev, C.ncol), &D.in[k]); }
+        H.add(C.sunlit, nullptr, {1, 1}, &sun_at, sizeof(int32_t));
+        H.add(C.frac_out, nullptr, {cells, 1}, &frac_at);
+        H.add(nullptr, nullptr, {cells, 1}, &u8_at, 1);
+        for (int k = 0; k < MDO_NOUT; k++) {
+            D.out[k] = nullptr;
+            if (C.out[k]) H.add(nullptr, C.out[k], modis_out_shape(k, C.ncol), &D.out[k], k == MDO_PHASE ? sizeof(int32_t) : 0);
+        }
+        return host_call(C.npoints, H, 4, [&](hipStream_t st, int nc) {
+            D.npoints = nc; D.sunlit = (const int32_t *)sun_at; D.frac_out = u8_at;
+            const size_t nn = cells * nc;
+            hipLaunchKernelGGL((k_real_to_mask<R>), dim3(grid256(nn)), dim3(256), 0, st, nn, (const R *)frac_at, (uint8_t *)u8_at);
+            return modis_launch(st, D);
+        });
+    }
+    // call COSP with the ISCCP, MISR and MODIS simulators on: one SCOPS mask in the workspace serves the three
+    int cosp_dev(hipStream_t st, const CospCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        IcarusCall I = C.ic;
+        if (const int rc = icarus_check(I)) return rc;
+        if (!C.zle || !C.qltot || !C.qitot || !C.rdfl || !C.rdfi) return fail(GEOSRAD_EINVAL, "geosrad_cosp_dev: null input array");
+        bool want_isccp = false, want_misr = false;
+        for (int k = 0; k < ICO_NOUT; k++) want_isccp |= I.out[k] != nullptr;
+        for (int k = 0; k < MIO_NOUT; k++) want_misr |= C.misr[k] != nullptr;
+        const bool want_modis = C.modis[0] || C.modis[1];
+        const int np = I.npoints, lm = I.nlev, ncol = I.ncol;
+        // MISR_simulator.f:294-313: one sub-column is the reference's serial scan over the points
+        if (want_misr && ncol == 1) return fail(GEOSRAD_EINVAL, "geosrad_cosp_dev: the MISR simulator needs ncol of at least 2");
+        MdWs m;
+        if (const int rc = md_workspace(np, lm, ncol, true, m)) return rc;
+        if (want_modis && !I.out[ICO_BOXPTOP]) I.out[ICO_BOXPTOP] = m.boxptop;      // ISCCP runs into the workspace for MODIS
+        I.scops_only = !want_isccp && !want_modis;
+        if (const int rc = icarus_dev(st, I)) return rc;
+        SsWs w;
+        if (const int rc = ss_workspace(np, lm, ncol, true, w)) return rc;      // no larger than icarus_dev's: the same planes, the mask among them
+        if (want_misr) {
+            hipLaunchKernelGGL((k_cosp_zfull<R>), dim3(grid256(np), lm), dim3(256), 0, st, np, lm, (const R *)C.zle, m.zfull);
+            MisrCall M{np, lm, ncol, -1.0E30, I.sunlit, {m.zfull, I.in[IC_AT], I.in[IC_DTAU_S], I.in[IC_DTAU_C]}, w.mask,
+                       {C.misr[MIO_FQ], C.misr[MIO_DIST], C.misr[MIO_ZTOP], C.misr[MIO_AREA]}};
+            if (const int rc = misr_launch(st, M)) return rc;
+        }
+        if (want_modis) {
+            ModisCall D{};
+            D.npoints = np; D.nlev = lm; D.ncol = ncol; D.sunlit = I.sunlit; D.frac_out = w.mask; D.geos = true;
+            D.in[MDI_T] = I.in[IC_AT]; D.in[MDI_P] = I.in[IC_PFULL]; D.in[MDI_PH] = I.in[IC_PHALF]; D.in[MDI_DTAU_S] = I.in[IC_DTAU_S];
+            D.in[MDI_DTAU_C] = I.in[IC_DTAU_C];
+            D.in[MDI_MR] = C.qltot; D.in[MDI_MR + 1] = C.qitot; D.in[MDI_REFF] = C.rdfl; D.in[MDI_REFF + 1] = C.rdfi;
+            D.in[MDI_BOXPTOP] = I.out[ICO_BOXPTOP];
+            D.out[MDO_MEAN] = C.modis[0]; D.out[MDO_HIST] = C.modis[1];
+            if (const int rc = modis_launch(st, D)) return rc;
+        }
+        return GEOSRAD_OK;
     }
 
     // in: ple, t, fcld, qi, ql, qr, qs, ri, rl, rr, rs; out: tauir, cldtmp, cldprs
@@ -3268,6 +3515,29 @@ struct MultiCtx final : geosrad_ctx {
             for (int j = 0; j < IC_NIN; j++) S.in[j] = off(C.in[j], c0);
             for (int j = 0; j < ICO_NOUT; j++) S.out[j] = off(C.out[j], c0);
             return k->icarus_host(S);
+        });
+    }
+    int misr_host(const MisrCall &C) override
+    {
+        if (const int rc = misr_check(C)) return rc;
+        return run_shards(C.npoints, [&](geosrad_ctx *k, int c0, int nc) {
+            MisrCall S = C;
+            S.npoints = nc; S.sunlit = C.sunlit + c0; S.frac_out = off(C.frac_out, c0);
+            S.first = C.first && c0 == 0; S.last = C.last && c0 + nc == C.npoints;
+            for (int j = 0; j < MI_NIN; j++) S.in[j] = off(C.in[j], c0);
+            for (int j = 0; j < MIO_NOUT; j++) S.out[j] = off(C.out[j], c0);
+            return k->misr_host(S);
+        });
+    }
+    int modis_host(const ModisCall &C) override
+    {
+        if (const int rc = modis_check(C)) return rc;
+        return run_shards(C.npoints, [&](geosrad_ctx *k, int c0, int nc) {
+            ModisCall S = C;
+            S.npoints = nc; S.sunlit = C.sunlit + c0; S.frac_out = off(C.frac_out, c0);
+            for (int j = 0; j < MDI_NIN; j++) S.in[j] = off(C.in[j], c0);
+            for (int j = 0; j < MDO_NOUT; j++) S.out[j] = j == MDO_PHASE && C.out[j] ? (void *)((int32_t *)C.out[j] + c0) : off(C.out[j], c0);
+            return k->modis_host(S);
         });
     }
     int mcica_host(int, int, int, const void *, const void *, int, const void *, const void *, const void *, const void *, double,
@@ -4058,6 +4328,65 @@ int geosrad_isccp_dev(geosrad_ctx *c, void *stream, int npoints, int lm, int nco
     return c->icarus_dev((hipStream_t)stream, C);
 }
 #undef IC_CALL
+
+// ---- include/geosrad_misr_modis.h --------------------------------------------------------------------------------------------
+int geosrad_misr(geosrad_ctx *c, int npoints, int nlev, int ncol, const int32_t *sunlit, const void *zfull, const void *at, const void *dtau_s,
+                 const void *dtau_c, const void *frac_out, double missing_value, void *fq_MISR_TAU_v_CTH, void *dist_model_layertops,
+                 void *MISR_mean_ztop, void *MISR_cldarea)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    return c->misr_host({npoints, nlev, ncol, missing_value, sunlit, {zfull, at, dtau_s, dtau_c}, frac_out,
+                         {fq_MISR_TAU_v_CTH, dist_model_layertops, MISR_mean_ztop, MISR_cldarea}});
+}
+#define MD_CALL(frac) geosrad_ctx::ModisCall C{npoints, nlev, ncol, sunlit,                                                              \
+        {t, p, ph, dtau_s, dtau_c, mr_lsliq, mr_lsice, mr_cvliq, mr_cvice, reff_lsliq, reff_lsice, reff_cvliq, reff_cvice, isccp_boxtau,     \
+         isccp_boxptop}, frac, {modis_mean, modis_hist, phase, ctp, tau, size}}
+int geosrad_modis(geosrad_ctx *c, int npoints, int nlev, int ncol, const int32_t *sunlit, const void *t, const void *p, const void *ph,
+                  const void *dtau_s, const void *dtau_c, const void *frac_out, const void *mr_lsliq, const void *mr_lsice, const void *mr_cvliq,
+                  const void *mr_cvice, const void *reff_lsliq, const void *reff_lsice, const void *reff_cvliq, const void *reff_cvice,
+                  const void *isccp_boxtau, const void *isccp_boxptop, void *modis_mean, void *modis_hist, int32_t *phase, void *ctp, void *tau,
+                  void *size)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    MD_CALL(frac_out);
+    return c->modis_host(C);
+}
+int geosrad_modis_dev(geosrad_ctx *c, void *stream, int npoints, int nlev, int ncol, const int32_t *sunlit, const void *t, const void *p,
+                      const void *ph, const void *dtau_s, const void *dtau_c, const void *frac_out_u8, const void *mr_lsliq, const void *mr_lsice,
+                      const void *mr_cvliq, const void *mr_cvice, const void *reff_lsliq, const void *reff_lsice, const void *reff_cvliq,
+                      const void *reff_cvice, const void *isccp_boxtau, const void *isccp_boxptop, void *modis_mean, void *modis_hist,
+                      int32_t *phase, void *ctp, void *tau, void *size)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    MD_CALL(frac_out_u8);
+    return c->modis_dev((hipStream_t)stream, C);
+}
+#undef MD_CALL
+int geosrad_cosp_dev(geosrad_ctx *c, void *stream, int npoints, int lm, int ncol, const void *t, const void *qv, const void *fcld, const void *cca,
+                     const void *ple, const void *plo, const void *dtau_s, const void *emiss, const void *dtau_c, const void *dem_c, const void *ts,
+                     const int32_t *sunlit, int32_t *seed, int overlap, int top_height, int top_height_direction, double emsfc_lw, void *fq_isccp,
+                     void *totalcldarea, void *meanptop, void *meantaucld, void *meanalbedocld, void *meantb, void *meantbclr, void *boxtau,
+                     void *boxptop, void *sgfcld, const void *zle, const void *qltot, const void *qitot, const void *rdfl, const void *rdfi,
+                     void *fq_MISR_TAU_v_CTH, void *dist_model_layertops, void *MISR_mean_ztop, void *MISR_cldarea, void *modis_mean,
+                     void *modis_hist)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    geosrad_ctx::CospCall C{{npoints, lm, ncol, top_height, top_height_direction, overlap, emsfc_lw, sunlit,
+                             {plo, ple, qv, fcld, cca, dtau_s, dtau_c, ts, t, emiss, dem_c}, nullptr,
+                             {fq_isccp, totalcldarea, meanptop, meantaucld, meanalbedocld, meantb, meantbclr, boxtau, boxptop}},
+                            zle, qltot, qitot, rdfl, rdfi, {fq_MISR_TAU_v_CTH, dist_model_layertops, MISR_mean_ztop, MISR_cldarea},
+                            {modis_mean, modis_hist}};
+    C.ic.cosp = true; C.ic.seed = seed; C.ic.sgfcld = sgfcld;
+    return c->cosp_dev((hipStream_t)stream, C);
+}
+int geosrad_misr_dev(geosrad_ctx *c, void *stream, int npoints, int nlev, int ncol, const int32_t *sunlit, const void *zfull, const void *at,
+                     const void *dtau_s, const void *dtau_c, const void *frac_out_u8, double missing_value, void *fq_MISR_TAU_v_CTH,
+                     void *dist_model_layertops, void *MISR_mean_ztop, void *MISR_cldarea)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    return c->misr_dev((hipStream_t)stream, {npoints, nlev, ncol, missing_value, sunlit, {zfull, at, dtau_s, dtau_c}, frac_out_u8,
+                                             {fq_MISR_TAU_v_CTH, dist_model_layertops, MISR_mean_ztop, MISR_cldarea}});
+}
 
 int geosrad_profile(geosrad_ctx *c, int enable)
 {
