@@ -67,9 +67,10 @@ def build(force=False):
     cols_only = {"lw_cols_kernels.hpp", "sw_reform_kernels.hpp", "lw_split_kernels.hpp"}      # headers geosrad.hip does not include
     # geosrad.hip includes the four public headers and gettau_kernels.hpp, satsim_kernels.hpp, misr_modis_kernels.hpp (with every other .hpp but cols_only): an edit of either rebuilds it
     deps_main = [os.path.join(CSRC, "geosrad.hip"), HEADER, HEADER_GETTAU, HEADER_SATSIM, HEADER_MISR_MODIS] + [p for f, p in hpp.items() if f not in cols_only]
-    deps_cols = [os.path.join(CSRC, "lw_cols.hip")] + [hpp[f] for f in ("lw_cols_kernels.hpp", "lw_cols.hpp", "lw_kernels.hpp", "lw_device.hpp")]
-    deps_split = [os.path.join(CSRC, "lw_split.hip")] + [hpp[f] for f in ("lw_split_kernels.hpp", "lw_split.hpp", "lw_kernels.hpp", "lw_device.hpp")]
-    deps_swq = [os.path.join(CSRC, "sw_reform.hip")] + [hpp[f] for f in ("sw_reform_kernels.hpp", "sw_reform.hpp", "sw_kernels.hpp", "lw_kernels.hpp", "lw_device.hpp")]
+    lw_layers = ("lw_layer_down.hpp", "lw_layer_up.hpp")      # the layer bodies lw_kernels.hpp includes (twice each)
+    deps_cols = [os.path.join(CSRC, "lw_cols.hip")] + [hpp[f] for f in ("lw_cols_kernels.hpp", "lw_cols.hpp", "lw_kernels.hpp", "lw_device.hpp") + lw_layers]
+    deps_split = [os.path.join(CSRC, "lw_split.hip")] + [hpp[f] for f in ("lw_split_kernels.hpp", "lw_split.hpp", "lw_kernels.hpp", "lw_device.hpp") + lw_layers]
+    deps_swq = [os.path.join(CSRC, "sw_reform.hip")] + [hpp[f] for f in ("sw_reform_kernels.hpp", "sw_reform.hpp", "sw_kernels.hpp", "lw_kernels.hpp", "lw_device.hpp") + lw_layers]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = os.path.join(os.path.dirname(HERE), "build", "obj")
     os.makedirs(objdir, exist_ok=True)

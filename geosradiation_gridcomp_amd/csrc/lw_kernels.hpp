@@ -1242,225 +1242,36 @@ GR_DEV void band_body(const LwArgs<R> &A, const LwDev<R> &Tg, int col, int nclea
     R plk_up = planck_at<R>(T.totplnk, IB, ldg(A.tlev + (size_t)nlay * ld, cba));   // level above the current layer
     // the layer's cloud flag is read one layer ahead: it decides (by ballot) whether the layer's McICA optical depths are requested,
     // and behind a load of its own that request would start a memory round trip late
-    int lc_next = CLD ? (int)ldg(A.laycloudy, (uint32_t)(nlay - 1) * (uint32_t)n + ucol) : 0;
+    // ctop: 1 + the highest layer in which a column of the wave has cloud fraction (k_mcica's walk ends there too), wave-uniform.
+    // The down sweep is split at it: the layers [ctop, nlay) are clear for every g-point of every lane, so their instantiation of
+    // the layer body (ABOVE) has no cloud flags, ballots or McICA requests, and the clear-sky stream, which IS the total one there,
+    // is not formed a second time.  What a column computes does not depend on the loop a layer runs in.
+    int ctop = 0;
+    if constexpr (CLD) {
+        const int t = ccol ? (int)ldg(A.colcloudy, (uint32_t)pc) : 0;
+        int m = 0;                         // maximum over the wave's active lanes, bit by bit (ballots only see active lanes)
+#pragma unroll
+        for (int b = 7; b >= 0; b--)
+            if (__ballot(t >= (m | (1 << b))) != 0) m |= 1 << b;
+        ctop = m < nlay ? m : nlay;
+    }
+    const int nbelow = CLD ? ctop : nlay;      // layers of the general body
+    int lc_next = (CLD && nbelow > 0) ? (int)ldg(A.laycloudy, (uint32_t)(nbelow - 1) * (uint32_t)n + ucol) : 0;
+    if constexpr (CLD) {
 #pragma nounroll
-    for (int lay = nlay - 1; lay >= 0; lay--) {
-        const int lc_cur = lc_next;
-        if (CLD && lay > 0) lc_next = (int)ldg(A.laycloudy, (uint32_t)(lay - 1) * (uint32_t)n + ucol);
-        const bool laycld0 = CLD && ccol && lc_cur != 0;
-        const bool wlc0 = CLD && __ballot(laycld0) != 0;
-        // McICA optical depths of ALL the layer's g-points, requested with the layer record: one HBM round trip per cloudy layer instead
-        // of one per g-group
-        R tcall[CLD ? NG : 1];
-        if (CLD) {
-#pragma unroll
-            for (int g = 0; g < NG; g++) tcall[g] = 0;
-            if (wlc0) {
-#pragma unroll
-                for (int g = 0; g < NG; g++)
-                    tcall[g] = ldg(taucmc_b, (((uint32_t)lay * (uint32_t)NG + (uint32_t)g) * (uint32_t)n + ucol) * (uint32_t)sizeof(R));
-            }
+        for (int lay = nlay - 1; lay >= ctop; lay--) {
+#define LW_ABOVE 1
+#include "lw_layer_down.hpp"
+#undef LW_ABOVE
         }
-        Layer<R> L;
-        load_layer<R>(A, lay, col, pc, L);
-        // the layer's aerosol and temperatures are requested, and the Planck look-ups they lead to made, BEFORE the band's prep: behind
-        // it they were a memory round trip of their own in every layer (5.12 -> 4.85 ms per 100 000 clear-sky columns)
-        const R ta = A.tauaer ? ldg(A.tauaer + (size_t)(IB - 1) * nlay * ld, L.ab) : (R)0;
-        const R blay = planck_at<R>(T.totplnk, IB, ldg(A.tlay, L.ab));
-        const R plk_dn = planck_at<R>(T.totplnk, IB, ldg(A.tlev, L.ab));
-        Prep<R> P;
-        BAND::template prep<R>(T, A, L, P);
-        const R dplankup = plk_up - blay, dplankdn = plk_dn - blay;
-        plk_up = plk_dn;
-        bool laycld = false;
-        if (CLD) {
-            laycld = laycld0;
-            if (laycld && !diverge) { diverge = true; ltop = lay; }   // (:297-299) before this layer's clear-sky update
-        }
-        const uint32_t cell0 = ((uint32_t)lay * (uint32_t)NG) * (uint32_t)n + ucol;   // g = 0 cell of this layer; + g*n
-        R dsum = 0, dcsum = 0;
-        if constexpr (!CLD) {
 #pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            R tau[W], pf[W];
-            BAND::template eval<R, W>(T, L, P, q * W, tau, pf);
-            // phase 1: Pade index of the gas optical depth + LUT gathers of the whole group
-            int itg[W];
-            R2 eg[W];
-#pragma unroll
-            for (int j = 0; j < W; j++) {
-                const int g = q * W + j;
-                if (g >= NG) { itg[j] = 0; eg[j].x = 0; eg[j].y = 0; continue; }   // padding of the last group
-                if (DBG) {
-                    const size_t o = ((size_t)pc * NG_LW + (G0 + g)) * nlay + lay;   // Fortran (nlay,140,ncol)
-                    A.dbg_taug[o] = tau[j] + ta;
-                    A.dbg_pfracs[o] = pf[j];
-                }
-                R odepth = secdiff * (tau[j] + ta);
-                if (odepth < 0) odepth = 0;
-                const R tblind = lw_pade<R>(odepth, bpade);
-                itg[j] = (int)(tblint * tblind + (R)0.5);
-                eg[j] = lut_at(itg[j]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // phase 2: only now write the PREVIOUS group's parked cells.  Loads and stores share one in-order counter
-            // (vmcnt) on gfx9: a load issued after a store cannot be consumed before that store is acknowledged, so the
-            // stores go behind this group's loads and get a whole group of arithmetic to drain.
-            if (npend) {
-#pragma unroll
-                for (int j = 0; j < W; j++)
-                    if (j < npend) {
-                        stg_nt(s1_b, poff[j] * (uint32_t)sizeof(PK), pend1[j]);
-                        if (CLD && (pmask2 >> j) & 1u) stg_nt(s2_b, poff[j] * (uint32_t)sizeof(PK), pend2[j]);
-                    }
-            }
-            npend = 0; pmask2 = 0;
-            __builtin_amdgcn_sched_barrier(0);
-            // phase 3: radiance recurrences of the group
-#pragma unroll
-            for (int j = 0; j < W; j++) {
-                const int g = q * W + j;
-                if (g >= NG) continue;
-                const int itgas = itg[j];
-                const R2 e = eg[j];
-                const R agas = (R)1. - e.x, tfacgas = e.y;
-                const R bbdgas = pf[j] * (blay + tfacgas * dplankdn);
-                const R bbugas = pf[j] * (blay + tfacgas * dplankup);
-                const uint32_t cell = cell0 + (uint32_t)g * (uint32_t)n;
-                const uint32_t scell = SCELL(lay, g);
-                R atot = agas, bbutot = bbugas;
-                int itp = itgas;                 // index parked for the total-sky stream
-                const R radprev = rad[g];
-                bool cldcell = false;
-                if (CLD && laycld) {
-                    const R tc = ldg(taucmc_b, cell * (uint32_t)sizeof(R));
-                    if (tc > 0) {
-                        cldcell = true;
-                        // cloud added to the DISCRETISED gas tau (:264-268)
-                        const R odtot = ldg(T.tau_tbl, (uint32_t)itgas * (uint32_t)sizeof(R)) + secdiff * tc;
-                        const R tb2 = lw_pade<R>(odtot, bpade);
-                        const int ittot = (int)(tblint * tb2 + (R)0.5);
-                        itp = ittot;
-                        const R2 e2 = lut_at(ittot);
-                        atot = (R)1. - e2.x;
-                        const R bbdtot = pf[j] * (blay + e2.y * dplankdn);
-                        bbutot = pf[j] * (blay + e2.y * dplankup);
-                        rad[g] = radprev + (bbdtot - radprev) * atot;
-                    }
-                }
-                if (!cldcell) rad[g] = radprev + (bbdgas - radprev) * agas;
-                if (DEFER) { pend1[j] = (PK)(itp); poff[j] = scell; npend = j + 1; }
-                else stg_nt(s1_b, scell * (uint32_t)sizeof(PK), (PK)(itp));
-                dsum = dsum + sumfac * rad[g];
-                if (CLD && ccol) {
-                    if (diverge) {
-                        radc[g] = radc[g] + (bbdgas - radc[g]) * agas;
-                        if (DEFER) { pend2[j] = (PK)(itgas); pmask2 |= 1u << j; }
-                        else stg_nt(s2_b, scell * (uint32_t)sizeof(PK), (PK)(itgas));
-                    } else {
-                        radc[g] = rad[g];
-                    }
-                    dcsum = dcsum + sumfac * radc[g];
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);   // keep one g-group's table rows in flight at a time
-        }
-        } else {
-        // general (cloudy-column) body.  Control flow around memory operations is wave-uniform only (ballots): a per-lane branch
-        // with a load inside makes the loads of a group wait for one another.  Lanes the test does not concern load / store
-        // along and select afterwards (their values are never used: unwritten cloud cells, gas-only pairs above their own cloud top).
-        const bool wlc = CLD && __ballot(laycld) != 0;       // some column of the wave has cloud in this layer
-        const bool wdv = CLD && __ballot(diverge) != 0;      // some column of the wave keeps gas-only pairs from here down
-#pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            R tcv[W];
-#pragma unroll
-            for (int j = 0; j < W; j++) tcv[j] = 0;
-            if (wlc) {
-#pragma unroll
-                for (int j = 0; j < W; j++)
-                    if (q * W + j < NG) tcv[j] = tcall[q * W + j];
-#pragma unroll
-                for (int j = 0; j < W; j++) tcv[j] = laycld ? tcv[j] : (R)0;
-            }
-            R tau[W], pf[W];
-            BAND::template eval<R, W>(T, L, P, q * W, tau, pf);
-            int itg[W];
-            R2 eg[W];
-            R ttb[W];
-            bool anyc = false;
-#pragma unroll
-            for (int j = 0; j < W; j++) {
-                const int g = q * W + j;
-                ttb[j] = 0;
-                if (g >= NG) { itg[j] = 0; eg[j].x = 0; eg[j].y = 0; continue; }   // padding of the last group
-                if (DBG) {
-                    const size_t o = ((size_t)pc * NG_LW + (G0 + g)) * nlay + lay;   // Fortran (nlay,140,ncol)
-                    A.dbg_taug[o] = tau[j] + ta;
-                    A.dbg_pfracs[o] = pf[j];
-                }
-                R odepth = secdiff * (tau[j] + ta);
-                if (odepth < 0) odepth = 0;
-                const R tblind = lw_pade<R>(odepth, bpade);
-                itg[j] = (int)(tblint * tblind + (R)0.5);
-                eg[j] = lut_at(itg[j]);
-                anyc = anyc || tcv[j] > 0;
-            }
-            const bool wcl = wlc && __ballot(anyc) != 0;         // some cell of the group is cloudy in some column of the wave
-            if (wcl) {
-#pragma unroll
-                for (int j = 0; j < W; j++) ttb[j] = ldg(T.tau_tbl, (uint32_t)itg[j] * (uint32_t)sizeof(R));
-            }
-            // the PREVIOUS group's parked cells are written only now, behind this group's loads (see the cloud-free body)
-            __builtin_amdgcn_sched_barrier(0);
-            if (npend) {
-#pragma unroll
-                for (int j = 0; j < W; j++)
-                    if (j < npend) {
-                        stg_nt(s1_b, poff[j] * (uint32_t)sizeof(PK), pend1[j]);
-                        if ((pmask2 >> j) & 1u) stg_nt(s2_b, poff[j] * (uint32_t)sizeof(PK), pend2[j]);
-                    }
-            }
-            npend = 0; pmask2 = 0;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < W; j++) {
-                const int g = q * W + j;
-                if (g >= NG) continue;
-                const R agas = (R)1. - eg[j].x, tfacgas = eg[j].y;
-                const R bbdgas = pf[j] * (blay + tfacgas * dplankdn);
-                const R bbugas = pf[j] * (blay + tfacgas * dplankup);
-                const uint32_t scell = SCELL(lay, g);
-                R atot = agas, bbutot = bbugas, bbd = bbdgas;
-                int itp = itg[j];
-                if (wcl) {
-                    // cloud added to the DISCRETISED gas tau (:264-268); evaluated for the whole wave, kept for the cloudy cells
-                    const bool cld = tcv[j] > 0;
-                    const R odtot = ttb[j] + secdiff * tcv[j];
-                    const R tb2 = lw_pade<R>(odtot, bpade);
-                    const int ittot = (int)(tblint * tb2 + (R)0.5);
-                    itp = cld ? ittot : itg[j];
-                    const R2 e2 = lut_at(itp);
-                    const R ac = (R)1. - e2.x;
-                    const R bbdtot = pf[j] * (blay + e2.y * dplankdn), bbut = pf[j] * (blay + e2.y * dplankup);
-                    atot = cld ? ac : agas; bbutot = cld ? bbut : bbugas; bbd = cld ? bbdtot : bbdgas;
-                }
-                rad[g] = rad[g] + (bbd - rad[g]) * atot;
-                pend1[j] = (PK)(itp); poff[j] = scell; npend = j + 1;
-                dsum = dsum + sumfac * rad[g];
-                if (CLD) {
-                    const R rc = radc[g] + (bbdgas - radc[g]) * agas;
-                    radc[g] = diverge ? rc : rad[g];
-                    if (wdv) { pend2[j] = (PK)(itg[j]); pmask2 |= 1u << j; }
-                    dcsum = dcsum + sumfac * radc[g];
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);   // keep one g-group's table rows in flight at a time
-        }
-        }
-        err_wave(ta < 0, A.err, 20);      // LW/rrtmg_lw_rad.F90:209-318 on tauaer: every band visits every layer of its columns
-        PART(0, lay, dsum);
-        if (CLD && ccol) PART(1, lay, dcsum);
+        for (int g = 0; g < NG; g++) radc[g] = rad[g];
+    }
+#pragma nounroll
+    for (int lay = nbelow - 1; lay >= 0; lay--) {
+#define LW_ABOVE 0
+#include "lw_layer_down.hpp"
+#undef LW_ABOVE
     }
 #pragma unroll
     for (int j = 0; j < W; j++)
@@ -1483,77 +1294,21 @@ GR_DEV void band_body(const LwArgs<R> &A, const LwDev<R> &Tg, int col, int nclea
     R dlu[NG], dclu[NG];
 #pragma unroll
     for (int g = 0; g < NG; g++) { dlu[g] = 0; dclu[g] = 0; }
+    // ABOVE (layers above wtop): no lane has a gas-only pair of its own, the clear-sky stream takes the first look-up's pair
+    const int nown = CLD ? wtop + 1 : nlay;      // layers of the general body
 #pragma nounroll
-    for (int lay = 0; lay < nlay; lay++) {
-        R u0 = 0, uc0 = 0, du0 = 0, duc0 = 0;       // level 0 (surface) sums, formed in the first trip
-        usum = 0; ucsum = 0; dusum = 0; ducsum = 0;
-        PK sv[NG], sg[NG];
-#pragma unroll
-        for (int g = 0; g < NG; g++) sv[g] = ldg_nt(s1_b, SCELL(lay, g) * (uint32_t)sizeof(PK));
-        if (CLD && lay <= wtop) {
-            // (lanes that have no pair of their own here read what happens to be there and do not use it)
-#pragma unroll
-            for (int g = 0; g < NG; g++) sg[g] = ldg_nt(s2_b, SCELL(lay, g) * (uint32_t)sizeof(PK));
-        } else {
-#pragma unroll
-            for (int g = 0; g < NG; g++) sg[g] = sv[g];
+    for (int lay = 0; lay < nown; lay++) {
+#define LW_ABOVE 0
+#include "lw_layer_up.hpp"
+#undef LW_ABOVE
+    }
+    if constexpr (CLD) {
+#pragma nounroll
+        for (int lay = nown; lay < nlay; lay++) {
+#define LW_ABOVE 1
+#include "lw_layer_up.hpp"
+#undef LW_ABOVE
         }
-        const bool own = CLD && ccol && diverge && lay <= ltop;      // above ltop the layer is clear for every g-point: gas == total
-        // (absorptivity, upward source) of the cell from its parked index: the transmittance table, the layer's Planck terms and
-        // the Planck fraction, which the band body evaluates again (its optical-depth terms are dead code here)
-        Layer<R> L;
-        load_layer<R>(A, lay, col, pc, L);
-        const R blay = planck_at<R>(T.totplnk, IB, ldg(A.tlay, L.ab));
-        const R dplankup = planck_at<R>(T.totplnk, IB, ldg(A.tlev + (size_t)ld, L.ab)) - blay;
-        Prep<R> P;
-        BAND::template prep<R>(T, A, L, P);
-#pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            R tau[W], pf[W];
-            BAND::template eval<R, W>(T, L, P, q * W, tau, pf);
-#pragma unroll
-            for (int j = 0; j < W; j++) {
-                const int g = q * W + j;
-                if (g >= NG) continue;
-                if (lay == 0) {
-                    // surface: emission + reflection turn the downward radiance into the upward one (:319-333)
-                    const R rad0 = pf[j] * plankbnd;
-                    rad[g] = rad0 + reflect * rad[g];
-                    dlu[g] = pf[j] * dplankbnd;
-                    u0 = u0 + sumfac * rad[g];
-                    du0 = du0 + sumfac * dlu[g];
-                    if (CLD) {
-                        radc[g] = rad0 + reflect * radc[g];
-                        dclu[g] = dlu[g];
-                        uc0 = uc0 + sumfac * radc[g];
-                        duc0 = duc0 + sumfac * dclu[g];
-                    }
-                }
-                const R2 e1 = lut_at((int)sv[g]);
-                const R a1 = (R)1. - e1.x, b1 = pf[j] * (blay + e1.y * dplankup);
-                rad[g] = rad[g] + (b1 - rad[g]) * a1;
-                dlu[g] = dlu[g] - dlu[g] * a1;
-                usum = usum + sumfac * rad[g];
-                dusum = dusum + sumfac * dlu[g];
-                if (CLD) {
-                    const R2 e2 = lut_at(own ? (int)sg[g] : (int)sv[g]);
-                    const R gx = (R)1. - e2.x, gy = pf[j] * (blay + e2.y * dplankup);
-                    const R rc = radc[g] + (gy - radc[g]) * gx, dc = dclu[g] - dclu[g] * gx;
-                    radc[g] = diverge ? rc : rad[g];
-                    dclu[g] = diverge ? dc : dlu[g];
-                    ucsum = ucsum + sumfac * radc[g];
-                    ducsum = ducsum + sumfac * dclu[g];
-                }
-            }
-        }
-        if (lay == 0) {
-            PART(2, 0, u0);
-            if (CLD && ccol) PART(3, 0, uc0);
-            if (dudTs) { PART(4, 0, du0); if (CLD && ccol) PART(5, 0, duc0); }
-        }
-        PART(2, lay + 1, usum);
-        if (CLD && ccol) PART(3, lay + 1, ucsum);
-        if (dudTs) { PART(4, lay + 1, dusum); if (CLD && ccol) PART(5, lay + 1, ducsum); }
     }
 #undef PART
 }
