@@ -53,20 +53,26 @@ EXPORTS_SATSIM = [
 # same reason - tests/test_satsim_abi.py pins geosrad_satsim.h to its six names
 HEADER_MISR_MODIS = os.path.join(os.path.dirname(HERE), "include", "geosrad_misr_modis.h")
 EXPORTS_MISR_MODIS = ["geosrad_misr", "geosrad_misr_dev", "geosrad_modis", "geosrad_modis_dev", "geosrad_cosp_dev"]
-HEADERS_ALL = HEADERS + [(HEADER_SATSIM, EXPORTS_SATSIM), (HEADER_MISR_MODIS, EXPORTS_MISR_MODIS)]      # every public header
+HEADERS_ALL = HEADERS + [(HEADER_SATSIM, EXPORTS_SATSIM), (HEADER_MISR_MODIS, EXPORTS_MISR_MODIS)]      # the four headers before the lidar's
+# the lidar simulator and the COSP path with it: the fifth public header, include/geosrad_lidar.h, bound beside the others for the same
+# reason - tests/test_misr_modis_abi.py pins geosrad_misr_modis.h to its five names and HEADERS_ALL to four headers, so the list of every
+# public header has a name of its own
+HEADER_LIDAR = os.path.join(os.path.dirname(HERE), "include", "geosrad_lidar.h")
+EXPORTS_LIDAR = ["geosrad_lidar", "geosrad_lidar_dev", "geosrad_cosp_lidar_dev"]
+HEADERS_PUBLIC = HEADERS_ALL + [(HEADER_LIDAR, EXPORTS_LIDAR)]      # every public header
 
 _lib = None
 
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU).  Objects (compiled in parallel, each rebuilt only when one of
-    the files it includes is newer): geosrad.hip three times - fp32 kernels, fp64 kernels, the extern "C" layer of the four public headers; it
-    includes gettau_kernels.hpp, satsim_kernels.hpp and misr_modis_kernels.hpp like every solver's kernels - and lw_cols.hip (the
+    the files it includes is newer): geosrad.hip three times - fp32 kernels, fp64 kernels, the extern "C" layer of the five public headers; it
+    includes gettau_kernels.hpp, satsim_kernels.hpp, misr_modis_kernels.hpp and lidar_kernels.hpp like every solver's kernels - and lw_cols.hip (the
     on-chip RRTMG_LW band sweeps) and sw_reform.hip (the default RRTMG_SW band sweeps) twice each - fp32, fp64."""
     hpp = {f: os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")}
     cols_only = {"lw_cols_kernels.hpp", "sw_reform_kernels.hpp", "lw_split_kernels.hpp"}      # headers geosrad.hip does not include
-    # geosrad.hip includes the four public headers and gettau_kernels.hpp, satsim_kernels.hpp, misr_modis_kernels.hpp (with every other .hpp but cols_only): an edit of either rebuilds it
-    deps_main = [os.path.join(CSRC, "geosrad.hip"), HEADER, HEADER_GETTAU, HEADER_SATSIM, HEADER_MISR_MODIS] + [p for f, p in hpp.items() if f not in cols_only]
+    # geosrad.hip includes the five public headers and gettau_kernels.hpp, satsim_kernels.hpp, misr_modis_kernels.hpp, lidar_kernels.hpp (with every other .hpp but cols_only): an edit of either rebuilds it
+    deps_main = [os.path.join(CSRC, "geosrad.hip"), HEADER, HEADER_GETTAU, HEADER_SATSIM, HEADER_MISR_MODIS, HEADER_LIDAR] + [p for f, p in hpp.items() if f not in cols_only]
     lw_layers = ("lw_layer_down.hpp", "lw_layer_up.hpp")      # the layer bodies lw_kernels.hpp includes (twice each)
     deps_cols = [os.path.join(CSRC, "lw_cols.hip")] + [hpp[f] for f in ("lw_cols_kernels.hpp", "lw_cols.hpp", "lw_kernels.hpp", "lw_device.hpp") + lw_layers]
     deps_split = [os.path.join(CSRC, "lw_split.hip")] + [hpp[f] for f in ("lw_split_kernels.hpp", "lw_split.hpp", "lw_kernels.hpp", "lw_device.hpp") + lw_layers]
@@ -170,13 +176,24 @@ def misr_modis_prototypes():
     return protos
 
 
+@functools.lru_cache(maxsize=None)
+def lidar_prototypes():
+    """the prototypes of include/geosrad_lidar.h, held to EXPORTS_LIDAR"""
+    if not os.path.exists(HEADER_LIDAR):
+        raise RuntimeError(f"{HEADER_LIDAR} is missing: the binding takes every entry point's argument order and types from it")
+    protos = parse_header(open(HEADER_LIDAR).read())
+    if set(protos) != set(EXPORTS_LIDAR):
+        raise RuntimeError(f"{HEADER_LIDAR} and its export list differ: {sorted(set(protos) ^ set(EXPORTS_LIDAR))}")
+    return protos
+
+
 def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(SO):
             raise RuntimeError(f"{SO} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(there is no CPU fallback)")
-        protos = {**all_prototypes(), **satsim_prototypes(), **misr_modis_prototypes()}
+        protos = {**all_prototypes(), **satsim_prototypes(), **misr_modis_prototypes(), **lidar_prototypes()}
         # PyTorch ships its own copy of the HIP runtime; when it is going to be used in this process (device tensors and streams
         # handed to the `_dev` entry points) it has to be the one this library binds to, so it is loaded first.
         try:

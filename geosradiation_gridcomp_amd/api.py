@@ -64,7 +64,7 @@ class GeosradInputError(GeosradError):
 def _params(name):
     """((parameter, int | float for a scalar, None for a pointer), ...) of the library function `name`, in the order of include/geosrad.h"""
     protos = _lib.all_prototypes()
-    for more in (_lib.satsim_prototypes, _lib.misr_modis_prototypes):
+    for more in (_lib.satsim_prototypes, _lib.misr_modis_prototypes, _lib.lidar_prototypes):
         if name not in protos:
             protos = more()
     return tuple((p, _SCALAR.get(t)) for t, p in protos[name][1])
@@ -555,6 +555,40 @@ class Context:
         up = ("T", "QV", "FCLD", "CCA", "PLE", "PLO", "DTAU_S", "EMISS", "DTAU_C", "DEM_C", "TS", "SGFCLD", "ZLE", "QLTOT", "QITOT", "RDFL", "RDFI")
         self._dev("geosrad_cosp_dev", ptr, {k.lower(): k for k in up}, stream=stream, npoints=npoints, lm=lm, ncol=ncol, overlap=overlap,
                   top_height=top_height, top_height_direction=top_height_direction, emsfc_lw=emsfc_lw)
+
+    # ---- the lidar simulator and the COSP path with it (include/geosrad_lidar.h) ------------------------------------------------
+    LIDAR_OUT = ("lidarcld", "cldlayer", "cfad_sr", "parasolrefl", "pmol", "beta_tot", "tau_tot", "refl")
+    LIDAR_CAT = ("low", "mid", "high", "total")          # the GEOSRAD_LIDAR_* indices of cldlayer
+
+    def lidar(self, npoints, nlev, ncol, ice_type, p, t, presf, pplay, frac_out, mr_lsliq, mr_lsice, mr_cvliq, mr_cvice, reff_lsliq,
+              reff_lsice, reff_cvliq, reff_cvice, land, want=("lidarcld", "cldlayer", "cfad_sr", "parasolrefl", "pmol")):
+        """COSP_LIDAR and diag_lidar on gridbox-level fields (nlev, npoints) TOA first, presf (nlev + 1, npoints), frac_out (nlev, ncol, npoints)
+        in the real kind, land (npoints); the convective arrays may be None (zero).  Returns dict(lidarcld, pmol (nlev, npoints); cldlayer (4,
+        npoints) in LIDAR_CAT's order; cfad_sr (nlev, 15, npoints); parasolrefl (5, npoints); beta_tot, tau_tot (nlev, ncol, npoints); refl (5,
+        ncol, npoints)) of the names in `want`; -1.0E30 where the reference leaves R_UNDEF."""
+        a = {k: v for k, v in locals().items() if k not in ("self", "want")}
+        unknown = set(want) - set(self.LIDAR_OUT)
+        if unknown:
+            raise TypeError(f"geosrad_lidar: no output {sorted(unknown)}")
+        shapes = {"lidarcld": (nlev, npoints), "cldlayer": (4, npoints), "cfad_sr": (nlev, 15, npoints), "parasolrefl": (5, npoints),
+                  "pmol": (nlev, npoints), "beta_tot": (nlev, ncol, npoints), "tau_tot": (nlev, ncol, npoints), "refl": (5, ncol, npoints)}
+        out = self._zeros([(k, shapes[k]) for k in self.LIDAR_OUT if k in want])
+        self._host("geosrad_lidar", a, out)
+        return out
+
+    def lidar_dev(self, stream, npoints, nlev, ncol, ice_type, ptr):
+        """`ptr`: name -> device address of p, t, presf, pplay, frac_out_u8 (one byte per cell), mr_lsliq ... reff_cvice, land and of the
+        wanted outputs lidarcld, cldlayer, cfad_sr, parasolrefl, pmol, beta_tot, tau_tot, refl (missing = NULL)."""
+        self._dev("geosrad_lidar_dev", ptr, stream=stream, npoints=npoints, nlev=nlev, ncol=ncol, ice_type=ice_type)
+
+    def cosp_lidar_dev(self, stream, npoints, lm, ncol, ptr, overlap=3, top_height=1, top_height_direction=2, emsfc_lw=0.999, ice_type=0):
+        """call COSP with the ISCCP, MISR, MODIS and lidar simulators on, on GEOS fields in model order: `ptr` as for cosp_dev, plus FROCEAN
+        (npoints) and the wanted lidar outputs clcalipso, lidarpmol (lm, npoints), cldlayer (4, npoints), cfad_sr (lm, 15, npoints), parasolrefl
+        (5, npoints).  An output group that is missing altogether skips that simulator.  ice_type: GEOS_SatsimGridComp.F90:3535 sets 0."""
+        up = ("T", "QV", "FCLD", "CCA", "PLE", "PLO", "DTAU_S", "EMISS", "DTAU_C", "DEM_C", "TS", "SGFCLD", "ZLE", "QLTOT", "QITOT", "RDFL", "RDFI",
+              "FROCEAN")
+        self._dev("geosrad_cosp_lidar_dev", ptr, {k.lower(): k for k in up}, stream=stream, npoints=npoints, lm=lm, ncol=ncol, overlap=overlap,
+                  top_height=top_height, top_height_direction=top_height_direction, emsfc_lw=emsfc_lw, ice_type=ice_type)
 
     # ---- Chou-Suarez SW, host arrays ---------------------------------------------------------------------
     def sorad(self, m, np_, nb, cosz, pl, ta, wa, oa, co2, cwc, fcld, ict, icb, reff, hk_uv, hk_ir, taua, ssaa, asya,

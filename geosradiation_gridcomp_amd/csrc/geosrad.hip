@@ -26,6 +26,7 @@
 #include "../../include/geosrad_gettau.h"
 #include "../../include/geosrad_satsim.h"
 #include "../../include/geosrad_misr_modis.h"
+#include "../../include/geosrad_lidar.h"
 #include "dev_buf.hpp"
 #include "lw_device.hpp"
 #include "lw_kernels.hpp"
@@ -38,6 +39,7 @@
 #include "gettau_kernels.hpp"
 #include "satsim_kernels.hpp"
 #include "misr_modis_kernels.hpp"
+#include "lidar_kernels.hpp"
 #include "lw_cols.hpp"
 #include "lw_split.hpp"
 #include "sw_reform.hpp"
@@ -756,6 +758,37 @@ struct geosrad_ctx {
         void *misr[MIO_NOUT], *modis[2];
     };
     virtual int cosp_dev(hipStream_t, const CospCall &) { return nodev("geosrad_cosp_dev"); }
+    // the lidar simulator (include/geosrad_lidar.h): one record, shared by the `_dev` and the host variant
+    enum LidarIn { LDI_P, LDI_T, LDI_PRESF, LDI_PPLAY, LDI_MR, LDI_REFF = LDI_MR + 4, LDI_LAND = LDI_REFF + 4, LDI_NIN };
+    enum LidarOut { LDO_CLD, LDO_LAYER, LDO_CFAD, LDO_PARASOL, LDO_PMOL, LDO_BETA, LDO_TAU, LDO_REFL, LDO_NOUT };
+    struct LidarCall {
+        int npoints, nlev, ncol, ice_type;
+        const void *in[LDI_NIN];        // the convective contents and radii may be null (zero)
+        const void *frac_out;           // bytes (`_dev`) or reals (host)
+        void *out[LDO_NOUT];
+        bool geos = false;              // geosrad_cosp_lidar_dev: in[LDI_PRESF] and in[LDI_PPLAY] are PLE (npoints,0:lm), in[LDI_LAND] is FROCEAN, the contents are clamped at 0
+    };
+    static bool lidar_optional(int k) { return k == LDI_MR + 2 || k == LDI_MR + 3 || k == LDI_REFF + 2 || k == LDI_REFF + 3; }
+    int lidar_check(const LidarCall &C)
+    {
+        if (const int rc = satsim_check("geosrad_lidar", C.npoints, C.nlev, C.ncol, 1, 1, 1)) return rc;
+        // lidar_simulator.F90:206-241 sets the ice coefficients under ice_type = 0 and = 1 only
+        if (C.ice_type != 0 && C.ice_type != 1) return fail(GEOSRAD_EINVAL, "geosrad_lidar: ice_type must be 0 or 1");
+        for (int k = 0; k < LDI_NIN; k++)
+            if (!C.in[k] && !lidar_optional(k)) return fail(GEOSRAD_EINVAL, "geosrad_lidar: null input array");
+        if (!C.frac_out) return fail(GEOSRAD_EINVAL, "geosrad_lidar: null input array");
+        return GEOSRAD_OK;
+    }
+    virtual int lidar_dev(hipStream_t, const LidarCall &) { return nodev("geosrad_lidar_dev"); }
+    virtual int lidar_host(const LidarCall &) = 0;
+    // geosrad_cosp_lidar_dev: the record of geosrad_cosp_dev and what the lidar needs beside it
+    struct CospLidarCall {
+        CospCall cosp;
+        const void *frocean;
+        int ice_type;
+        void *lidar[5];                 // clcalipso, cldlayer, cfad_sr, parasolrefl, lidarpmol
+    };
+    virtual int cosp_lidar_dev(hipStream_t, const CospLidarCall &) { return nodev("geosrad_cosp_lidar_dev"); }
 };
 
 // order of the `in` / `out` pointer arrays of sw_dev / sw_host
@@ -835,6 +868,13 @@ static inline ArrShape ic_out_shape(int k, size_t S) { return {k == geosrad_ctx:
 // modis: the inputs of ModisIn and the outputs of ModisOut (L levels, S sub-columns)
 static inline ArrShape modis_in_shape(int k, size_t L, size_t S) { return {k == geosrad_ctx::MDI_PH ? L + 1 : k >= geosrad_ctx::MDI_BOXTAU ? S : L, 1}; }
 static inline ArrShape modis_out_shape(int k, size_t S) { return {k == geosrad_ctx::MDO_MEAN ? (size_t)17 : k == geosrad_ctx::MDO_HIST ? (size_t)49 : S, 1}; }
+// lidar: the inputs of LidarIn and the outputs of LidarOut (L levels, S sub-columns)
+static inline ArrShape lidar_in_shape(int k, size_t L) { return {k == geosrad_ctx::LDI_PRESF ? L + 1 : k == geosrad_ctx::LDI_LAND ? 1 : L, 1}; }
+static inline ArrShape lidar_out_shape(int k, size_t L, size_t S)
+{
+    const size_t rows[geosrad_ctx::LDO_NOUT] = {L, 4, 15 * L, 5, L, S * L, S * L, S * 5};
+    return {rows[k], 1};
+}
 static inline ArrShape misr_out_shape(int k) { return {k == geosrad_ctx::MIO_FQ ? (size_t)(7 * 16) : k == geosrad_ctx::MIO_DIST ? (size_t)16 : (size_t)1, 1}; }
 
 // The arrays of one host-pointer call, added in host_pipeline's order (copied in only, both ways, back only).  src: copied in, dst:
@@ -1088,7 +1128,7 @@ template <typename R> struct Ctx : geosrad_ctx {
     size_t workspace_bytes() const override
     {
         size_t t = 0;
-        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_ws_hb, &d_ws_ss, &d_ws_misr, &d_ws_modis, &d_zero, &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
+        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_ws_hb, &d_ws_ss, &d_ws_misr, &d_ws_modis, &d_ws_lidar, &d_zero, &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
             t += b->bytes;
         return t;
     }
@@ -2100,22 +2140,25 @@ template <typename R> struct Ctx : geosrad_ctx {
     {
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamSynchronize(st));
-        uint32_t e2[5] = {0, 0, 0, 0, 0};
-        HIPCHK(hipMemcpy(e2, d_err, 20, hipMemcpyDeviceToHost));
+        uint32_t e2[6] = {0, 0, 0, 0, 0, 0};
+        HIPCHK(hipMemcpy(e2, d_err, 24, hipMemcpyDeviceToHost));
         // slot 0 = RRTMG_LW (+ McICA), slot 1 = RRTMG_SW; the Chou schemes have no input assertions (neither has the reference).
         // The host-pointer entry points look at their own solver's slot only (a flag left by an unchecked `_dev` call of the other
         // solver is that call's to report); geosrad_check reports either.  Only the slot that is reported is cleared - with the two
         // solvers on two streams the other one's flag stays up for the check of its own stream - and it is cleared in stream order
         // on `st`, so a kernel of the other solver running on another stream cannot lose a bit to it.
         // slot 3 = the range check of ICARUS (icarus.f:403-455), slot 4 = that of MODIS (modis_simulator.F90:202-206), reported last
-        // (slot 2 is k_chou_prep's and is not looked at here)
-        if (which == 0) e2[1] = e2[3] = e2[4] = 0;
-        if (which == 1) e2[0] = e2[3] = e2[4] = 0;
-        if (which == 3) e2[0] = e2[1] = e2[4] = 0;
-        if (which == 4) e2[0] = e2[1] = e2[3] = 0;
-        if (!e2[0] && !e2[1] && !e2[3] && !e2[4]) return GEOSRAD_OK;
-        HIPCHK(hipMemsetAsync(d_err + (e2[1] ? 1 : e2[0] ? 0 : e2[3] ? 3 : 4), 0, 4, st));
+        // (slot 2 is k_chou_prep's and is not looked at here); slot 5 = the range check of the lidar simulator, reported after MODIS's
+        for (int k : {0, 1, 3, 4, 5})
+            if (which >= 0 && which != k) e2[k] = 0;
+        if (!e2[0] && !e2[1] && !e2[3] && !e2[4] && !e2[5]) return GEOSRAD_OK;
+        HIPCHK(hipMemsetAsync(d_err + (e2[1] ? 1 : e2[0] ? 0 : e2[3] ? 3 : e2[4] ? 4 : 5), 0, 4, st));
         HIPCHK(hipStreamSynchronize(st));
+        if (!e2[0] && !e2[1] && !e2[3] && !e2[4]) {
+            if (e2[5] & (1u << LDERR_P)) return fail(GEOSRAD_EINPUT, "Input values out of bounds (lidar): p");
+            if (e2[5] & (1u << LDERR_T)) return fail(GEOSRAD_EINPUT, "Input values out of bounds (lidar): t");
+            return fail(GEOSRAD_EINPUT, "Input values out of bounds (lidar): a non-finite pnorm");
+        }
         if (!e2[0] && !e2[1] && !e2[3]) {
             static const char *MD_NAMES[MDERR_N] = {"t", "p", "dtau_s", "dtau_c", "reff_lsliq", "reff_lsice", "reff_cvliq", "reff_cvice"};
             for (int k = 0; k < MDERR_N; k++)
@@ -3260,6 +3303,96 @@ template <typename R> struct Ctx : geosrad_ctx {
         return GEOSRAD_OK;
     }
 
+    // =====================================================================================================
+    // the lidar simulator and the COSP path with it (include/geosrad_lidar.h; lidar_kernels.hpp)
+    // =====================================================================================================
+    DevBuf<> d_ws_lidar;      // eleven (npoints,nlev) planes, two (npoints,ncol) planes, one byte per cell and one per sub-column
+    const LidarTab<R> ld_tab = ld_tables<R>();
+    struct LdWs { R *pl[11], *tau_liq, *tau_ice; uint8_t *bin, *cat; };
+    size_t ld_layout(int np, int nlev, int ncol, LdWs &w, Carve c) const
+    {
+        const size_t pl = (size_t)np * nlev, ps = (size_t)np * ncol;
+        for (int k = 0; k < 11; k++) w.pl[k] = c.take<R>(pl);
+        w.tau_liq = c.take<R>(ps); w.tau_ice = c.take<R>(ps);
+        w.bin = c.take<uint8_t>(ps * nlev); w.cat = c.take<uint8_t>(ps);
+        return c.off;
+    }
+    int lidar_dev(hipStream_t st, const LidarCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = lidar_check(C)) return rc;
+        return lidar_launch(st, C);
+    }
+    // the three kernels on a record that lidar_check has passed
+    int lidar_launch(hipStream_t st, const LidarCall &C)
+    {
+        LdWs w;
+        const int np = C.npoints;
+        if (d_ws_lidar.reserve(ld_layout(np, C.nlev, C.ncol, w, Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the lidar simulator's workspace failed");
+        ld_layout(np, C.nlev, C.ncol, w, Carve(d_ws_lidar.p));
+        LidarArgs<R> A{};
+        A.npoints = np; A.nlev = C.nlev; A.ncol = C.ncol; A.ice_type = C.ice_type;
+        A.ple_shift = C.geos; A.clamp_mr = C.geos; A.ocean = C.geos;
+        auto I = [&](int k) { return (const R *)C.in[k]; };
+        A.p = I(LDI_P); A.t = I(LDI_T); A.presf = I(LDI_PRESF); A.pplay = I(LDI_PPLAY); A.land = I(LDI_LAND);
+        for (int k = 0; k < 4; k++) { A.mr[k] = I(LDI_MR + k); A.reff[k] = I(LDI_REFF + k); A.kp[k] = w.pl[5 + k]; }
+        A.frac = (const uint8_t *)C.frac_out;
+        A.dz = w.pl[0]; A.taumol = w.pl[1]; A.betamol = w.pl[2]; A.pmol = w.pl[3]; A.rho = w.pl[4]; A.frac_ls = w.pl[9]; A.frac_cv = w.pl[10];
+        A.tau_liq = w.tau_liq; A.tau_ice = w.tau_ice; A.bin = w.bin; A.cat = w.cat;
+        A.err = d_err + 5;
+        auto O = [&](int k) { return (R *)C.out[k]; };
+        A.lidarcld = O(LDO_CLD); A.cldlayer = O(LDO_LAYER); A.cfad = O(LDO_CFAD); A.parasol = O(LDO_PARASOL); A.o_pmol = O(LDO_PMOL);
+        A.o_beta = O(LDO_BETA); A.o_tau = O(LDO_TAU); A.o_refl = O(LDO_REFL);
+        A.tab = ld_tab;
+        hipLaunchKernelGGL((k_lidar_point<R>), dim3(grid256(np), C.nlev), dim3(256), 0, st, A);
+        hipLaunchKernelGGL((k_lidar_box<R>), dim3(grid256((size_t)np * C.ncol)), dim3(256), 0, st, A);
+        hipLaunchKernelGGL((k_lidar_stats<R>), dim3(grid256(np), C.nlev), dim3(256), 0, st, A);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+    int lidar_host(const LidarCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = lidar_check(C)) return rc;
+        HostArrs H(sizeof(R));
+        LidarCall D = C;
+        const void *frac_at = nullptr, *u8_at = nullptr;
+        const size_t cells = (size_t)C.ncol * C.nlev;
+        for (int k = 0; k < LDI_NIN; k++) { D.in[k] = nullptr; if (C.in[k]) H.add(C.in[k], nullptr, lidar_in_shape(k, C.nlev), &D.in[k]); }
+        H.add(C.frac_out, nullptr, {cells, 1}, &frac_at);
+        H.add(nullptr, nullptr, {cells, 1}, &u8_at, 1);
+        for (int k = 0; k < LDO_NOUT; k++) {
+            D.out[k] = nullptr;
+            if (C.out[k]) H.add(nullptr, C.out[k], lidar_out_shape(k, C.nlev, C.ncol), (const void **)&D.out[k]);
+        }
+        return host_call(C.npoints, H, 5, [&](hipStream_t st, int nc) {
+            D.npoints = nc; D.frac_out = u8_at;
+            const size_t nn = cells * nc;
+            hipLaunchKernelGGL((k_real_to_mask<R>), dim3(grid256(nn)), dim3(256), 0, st, nn, (const R *)frac_at, (uint8_t *)u8_at);
+            return lidar_launch(st, D);
+        });
+    }
+    // call COSP with all four simulators on: geosrad_cosp_dev's own path, then the lidar on the same SCOPS mask
+    int cosp_lidar_dev(hipStream_t st, const CospLidarCall &C) override
+    {
+        bool want = false;
+        for (int k = 0; k < 5; k++) want |= C.lidar[k] != nullptr;
+        if (want && !C.frocean) return fail(GEOSRAD_EINVAL, "geosrad_cosp_lidar_dev: null input array");
+        if (want && C.ice_type != 0 && C.ice_type != 1) return fail(GEOSRAD_EINVAL, "geosrad_cosp_lidar_dev: ice_type must be 0 or 1");
+        if (const int rc = cosp_dev(st, C.cosp)) return rc;
+        if (!want) return GEOSRAD_OK;
+        const IcarusCall &I = C.cosp.ic;
+        SsWs w;
+        if (const int rc = ss_workspace(I.npoints, I.nlev, I.ncol, true, w)) return rc;      // no larger than cosp_dev's: the same planes, the mask among them
+        LidarCall D{};
+        D.npoints = I.npoints; D.nlev = I.nlev; D.ncol = I.ncol; D.ice_type = C.ice_type; D.frac_out = w.mask; D.geos = true;
+        D.in[LDI_P] = I.in[IC_PFULL]; D.in[LDI_T] = I.in[IC_AT]; D.in[LDI_PRESF] = I.in[IC_PHALF]; D.in[LDI_PPLAY] = I.in[IC_PHALF];
+        D.in[LDI_MR] = C.cosp.qltot; D.in[LDI_MR + 1] = C.cosp.qitot; D.in[LDI_REFF] = C.cosp.rdfl; D.in[LDI_REFF + 1] = C.cosp.rdfi;
+        D.in[LDI_LAND] = C.frocean;
+        for (int k = 0; k < 5; k++) D.out[k] = C.lidar[k];
+        return lidar_launch(st, D);
+    }
+
     // in: ple, t, fcld, qi, ql, qr, qs, ri, rl, rr, rs; out: tauir, cldtmp, cldprs
     int lw_cloud_diag_dev(hipStream_t st, int ncol, int lm, double grav, double undef, double taucrit, const void *const *in,
                           void *const *out) override
@@ -3538,6 +3671,17 @@ struct MultiCtx final : geosrad_ctx {
             for (int j = 0; j < MDI_NIN; j++) S.in[j] = off(C.in[j], c0);
             for (int j = 0; j < MDO_NOUT; j++) S.out[j] = j == MDO_PHASE && C.out[j] ? (void *)((int32_t *)C.out[j] + c0) : off(C.out[j], c0);
             return k->modis_host(S);
+        });
+    }
+    int lidar_host(const LidarCall &C) override
+    {
+        if (const int rc = lidar_check(C)) return rc;
+        return run_shards(C.npoints, [&](geosrad_ctx *k, int c0, int nc) {
+            LidarCall S = C;
+            S.npoints = nc; S.frac_out = off(C.frac_out, c0);
+            for (int j = 0; j < LDI_NIN; j++) S.in[j] = off(C.in[j], c0);
+            for (int j = 0; j < LDO_NOUT; j++) S.out[j] = off(C.out[j], c0);
+            return k->lidar_host(S);
         });
     }
     int mcica_host(int, int, int, const void *, const void *, int, const void *, const void *, const void *, const void *, double,
@@ -4378,6 +4522,50 @@ int geosrad_cosp_dev(geosrad_ctx *c, void *stream, int npoints, int lm, int ncol
                             {modis_mean, modis_hist}};
     C.ic.cosp = true; C.ic.seed = seed; C.ic.sgfcld = sgfcld;
     return c->cosp_dev((hipStream_t)stream, C);
+}
+// ---- include/geosrad_lidar.h -------------------------------------------------------------------------------------------------
+#define LD_CALL(frac) geosrad_ctx::LidarCall C{npoints, nlev, ncol, ice_type,                                                             \
+        {p, t, presf, pplay, mr_lsliq, mr_lsice, mr_cvliq, mr_cvice, reff_lsliq, reff_lsice, reff_cvliq, reff_cvice, land}, frac,            \
+        {lidarcld, cldlayer, cfad_sr, parasolrefl, pmol, beta_tot, tau_tot, refl}}
+int geosrad_lidar(geosrad_ctx *c, int npoints, int nlev, int ncol, int ice_type, const void *p, const void *t, const void *presf,
+                  const void *pplay, const void *frac_out, const void *mr_lsliq, const void *mr_lsice, const void *mr_cvliq, const void *mr_cvice,
+                  const void *reff_lsliq, const void *reff_lsice, const void *reff_cvliq, const void *reff_cvice, const void *land,
+                  void *lidarcld, void *cldlayer, void *cfad_sr, void *parasolrefl, void *pmol, void *beta_tot, void *tau_tot, void *refl)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    LD_CALL(frac_out);
+    return c->lidar_host(C);
+}
+int geosrad_lidar_dev(geosrad_ctx *c, void *stream, int npoints, int nlev, int ncol, int ice_type, const void *p, const void *t,
+                      const void *presf, const void *pplay, const void *frac_out_u8, const void *mr_lsliq, const void *mr_lsice,
+                      const void *mr_cvliq, const void *mr_cvice, const void *reff_lsliq, const void *reff_lsice, const void *reff_cvliq,
+                      const void *reff_cvice, const void *land, void *lidarcld, void *cldlayer, void *cfad_sr, void *parasolrefl, void *pmol,
+                      void *beta_tot, void *tau_tot, void *refl)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    LD_CALL(frac_out_u8);
+    return c->lidar_dev((hipStream_t)stream, C);
+}
+#undef LD_CALL
+int geosrad_cosp_lidar_dev(geosrad_ctx *c, void *stream, int npoints, int lm, int ncol, const void *t, const void *qv, const void *fcld,
+                           const void *cca, const void *ple, const void *plo, const void *dtau_s, const void *emiss, const void *dtau_c,
+                           const void *dem_c, const void *ts, const int32_t *sunlit, int32_t *seed, int overlap, int top_height,
+                           int top_height_direction, double emsfc_lw, void *fq_isccp, void *totalcldarea, void *meanptop, void *meantaucld,
+                           void *meanalbedocld, void *meantb, void *meantbclr, void *boxtau, void *boxptop, void *sgfcld, const void *zle,
+                           const void *qltot, const void *qitot, const void *rdfl, const void *rdfi, void *fq_MISR_TAU_v_CTH,
+                           void *dist_model_layertops, void *MISR_mean_ztop, void *MISR_cldarea, void *modis_mean, void *modis_hist,
+                           const void *frocean, int ice_type, void *clcalipso, void *cldlayer, void *cfad_sr, void *parasolrefl,
+                           void *lidarpmol)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    geosrad_ctx::CospLidarCall C{{{npoints, lm, ncol, top_height, top_height_direction, overlap, emsfc_lw, sunlit,
+                                  {plo, ple, qv, fcld, cca, dtau_s, dtau_c, ts, t, emiss, dem_c}, nullptr,
+                                  {fq_isccp, totalcldarea, meanptop, meantaucld, meanalbedocld, meantb, meantbclr, boxtau, boxptop}},
+                                 zle, qltot, qitot, rdfl, rdfi, {fq_MISR_TAU_v_CTH, dist_model_layertops, MISR_mean_ztop, MISR_cldarea},
+                                 {modis_mean, modis_hist}},
+                                frocean, ice_type, {clcalipso, cldlayer, cfad_sr, parasolrefl, lidarpmol}};
+    C.cosp.ic.cosp = true; C.cosp.ic.seed = seed; C.cosp.ic.sgfcld = sgfcld;
+    return c->cosp_lidar_dev((hipStream_t)stream, C);
 }
 int geosrad_misr_dev(geosrad_ctx *c, void *stream, int npoints, int nlev, int ncol, const int32_t *sunlit, const void *zfull, const void *at,
                      const void *dtau_s, const void *dtau_c, const void *frac_out_u8, double missing_value, void *fq_MISR_TAU_v_CTH,
