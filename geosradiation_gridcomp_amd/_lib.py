@@ -59,20 +59,26 @@ HEADERS_ALL = HEADERS + [(HEADER_SATSIM, EXPORTS_SATSIM), (HEADER_MISR_MODIS, EX
 # public header has a name of its own
 HEADER_LIDAR = os.path.join(os.path.dirname(HERE), "include", "geosrad_lidar.h")
 EXPORTS_LIDAR = ["geosrad_lidar", "geosrad_lidar_dev", "geosrad_cosp_lidar_dev"]
-HEADERS_PUBLIC = HEADERS_ALL + [(HEADER_LIDAR, EXPORTS_LIDAR)]      # every public header
+HEADERS_PUBLIC = HEADERS_ALL + [(HEADER_LIDAR, EXPORTS_LIDAR)]      # the five headers before the radar's
+# the radar simulator's front end: the sixth public header, include/geosrad_radar.h, bound beside the others for the same reason -
+# tests/test_lidar_abi.py pins HEADERS_PUBLIC to five headers, so the list of every public header has a new name again
+HEADER_RADAR = os.path.join(os.path.dirname(HERE), "include", "geosrad_radar.h")
+EXPORTS_RADAR = ["geosrad_prec_scops", "geosrad_prec_scops_dev", "geosrad_cosp_sghydro", "geosrad_cosp_sghydro_dev", "geosrad_radar_gases",
+                 "geosrad_radar_gases_dev"]
+HEADERS_EVERY = HEADERS_PUBLIC + [(HEADER_RADAR, EXPORTS_RADAR)]      # every public header
 
 _lib = None
 
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU).  Objects (compiled in parallel, each rebuilt only when one of
-    the files it includes is newer): geosrad.hip three times - fp32 kernels, fp64 kernels, the extern "C" layer of the five public headers; it
-    includes gettau_kernels.hpp, satsim_kernels.hpp, misr_modis_kernels.hpp and lidar_kernels.hpp like every solver's kernels - and lw_cols.hip (the
+    the files it includes is newer): geosrad.hip three times - fp32 kernels, fp64 kernels, the extern "C" layer of the six public headers; it
+    includes gettau_kernels.hpp, satsim_kernels.hpp, misr_modis_kernels.hpp, lidar_kernels.hpp and radar_kernels.hpp like every solver's kernels - and lw_cols.hip (the
     on-chip RRTMG_LW band sweeps) and sw_reform.hip (the default RRTMG_SW band sweeps) twice each - fp32, fp64."""
     hpp = {f: os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")}
     cols_only = {"lw_cols_kernels.hpp", "sw_reform_kernels.hpp", "lw_split_kernels.hpp"}      # headers geosrad.hip does not include
-    # geosrad.hip includes the five public headers and gettau_kernels.hpp, satsim_kernels.hpp, misr_modis_kernels.hpp, lidar_kernels.hpp (with every other .hpp but cols_only): an edit of either rebuilds it
-    deps_main = [os.path.join(CSRC, "geosrad.hip"), HEADER, HEADER_GETTAU, HEADER_SATSIM, HEADER_MISR_MODIS, HEADER_LIDAR] + [p for f, p in hpp.items() if f not in cols_only]
+    # geosrad.hip includes the six public headers and gettau_kernels.hpp, satsim_kernels.hpp, misr_modis_kernels.hpp, lidar_kernels.hpp, radar_kernels.hpp (with every other .hpp but cols_only): an edit of either rebuilds it
+    deps_main = [os.path.join(CSRC, "geosrad.hip"), HEADER, HEADER_GETTAU, HEADER_SATSIM, HEADER_MISR_MODIS, HEADER_LIDAR, HEADER_RADAR] + [p for f, p in hpp.items() if f not in cols_only]
     lw_layers = ("lw_layer_down.hpp", "lw_layer_up.hpp")      # the layer bodies lw_kernels.hpp includes (twice each)
     deps_cols = [os.path.join(CSRC, "lw_cols.hip")] + [hpp[f] for f in ("lw_cols_kernels.hpp", "lw_cols.hpp", "lw_kernels.hpp", "lw_device.hpp") + lw_layers]
     deps_split = [os.path.join(CSRC, "lw_split.hip")] + [hpp[f] for f in ("lw_split_kernels.hpp", "lw_split.hpp", "lw_kernels.hpp", "lw_device.hpp") + lw_layers]
@@ -187,13 +193,24 @@ def lidar_prototypes():
     return protos
 
 
+@functools.lru_cache(maxsize=None)
+def radar_prototypes():
+    """the prototypes of include/geosrad_radar.h, held to EXPORTS_RADAR"""
+    if not os.path.exists(HEADER_RADAR):
+        raise RuntimeError(f"{HEADER_RADAR} is missing: the binding takes every entry point's argument order and types from it")
+    protos = parse_header(open(HEADER_RADAR).read())
+    if set(protos) != set(EXPORTS_RADAR):
+        raise RuntimeError(f"{HEADER_RADAR} and its export list differ: {sorted(set(protos) ^ set(EXPORTS_RADAR))}")
+    return protos
+
+
 def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(SO):
             raise RuntimeError(f"{SO} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(there is no CPU fallback)")
-        protos = {**all_prototypes(), **satsim_prototypes(), **misr_modis_prototypes(), **lidar_prototypes()}
+        protos = {**all_prototypes(), **satsim_prototypes(), **misr_modis_prototypes(), **lidar_prototypes(), **radar_prototypes()}
         # PyTorch ships its own copy of the HIP runtime; when it is going to be used in this process (device tensors and streams
         # handed to the `_dev` entry points) it has to be the one this library binds to, so it is loaded first.
         try:

@@ -64,7 +64,7 @@ class GeosradInputError(GeosradError):
 def _params(name):
     """((parameter, int | float for a scalar, None for a pointer), ...) of the library function `name`, in the order of include/geosrad.h"""
     protos = _lib.all_prototypes()
-    for more in (_lib.satsim_prototypes, _lib.misr_modis_prototypes, _lib.lidar_prototypes):
+    for more in (_lib.satsim_prototypes, _lib.misr_modis_prototypes, _lib.lidar_prototypes, _lib.radar_prototypes):
         if name not in protos:
             protos = more()
     return tuple((p, _SCALAR.get(t)) for t, p in protos[name][1])
@@ -589,6 +589,57 @@ class Context:
               "FROCEAN")
         self._dev("geosrad_cosp_lidar_dev", ptr, {k.lower(): k for k in up}, stream=stream, npoints=npoints, lm=lm, ncol=ncol, overlap=overlap,
                   top_height=top_height, top_height_direction=top_height_direction, emsfc_lw=emsfc_lw, ice_type=ice_type)
+
+    # ---- the radar simulator's front end (include/geosrad_radar.h) ------------------------------------------------------------
+    HYDRO = ("lsliq", "lsice", "lsrain", "lssnow", "cvliq", "cvice", "cvrain", "cvsnow", "lsgrpl")          # the GEOSRAD_HYDRO_* indices
+    SGHYDRO_OUT = ("prec_frac", "frac_ls", "frac_cv", "prec_ls", "prec_cv", "mr_sub", "mr_hydro_sg")
+
+    def prec_scops(self, npoints, nlev, ncol, ls_p_rate, cv_p_rate, frac_out):
+        """prec_scops (llnl/prec_scops.f) in its own argument order: the rates (nlev, npoints) TOA first, frac_out (nlev, ncol, npoints) in
+        the real kind.  Returns prec_frac (nlev, ncol, npoints) in the real kind: 0 clear, 1 large-scale, 2 convective, 3 both."""
+        a = dict(npoints=npoints, nlev=nlev, ncol=ncol, ls_p_rate=ls_p_rate, cv_p_rate=cv_p_rate, frac_out=frac_out)
+        out = self._zeros([("prec_frac", (nlev, ncol, npoints))])
+        self._host("geosrad_prec_scops", a, out)
+        return out["prec_frac"]
+
+    def prec_scops_dev(self, stream, npoints, nlev, ncol, ptr):
+        """`ptr`: name -> device address of ls_p_rate, cv_p_rate, frac_out_u8 and prec_frac_u8 (one byte per cell)."""
+        self._dev("geosrad_prec_scops_dev", ptr, stream=stream, npoints=npoints, nlev=nlev, ncol=ncol)
+
+    def cosp_sghydro(self, npoints, nlev, ncol, frac_out, mr_lsliq, mr_lsice, mr_lsrain, mr_lssnow, mr_cvliq=None, mr_cvice=None, mr_cvrain=None,
+                     mr_cvsnow=None, mr_lsgrpl=None, want=("prec_frac", "frac_ls", "frac_cv", "prec_ls", "prec_cv", "mr_sub")):
+        """The sub-grid hydrometeor contents of cosp.F90:399-519 from the SCOPS mask frac_out (nlev, ncol, npoints) in the real kind and the
+        gridbox mixing ratios (nlev, npoints) TOA first; the convective ones and the graupel may be None (zero).  Returns dict(prec_frac (nlev,
+        ncol, npoints); frac_ls, frac_cv, prec_ls, prec_cv (nlev, npoints); mr_sub (9, nlev, npoints) in HYDRO's order; mr_hydro_sg (9, nlev,
+        ncol, npoints)) of the names in `want`."""
+        a = {k: v for k, v in locals().items() if k not in ("self", "want")}
+        unknown = set(want) - set(self.SGHYDRO_OUT)
+        if unknown:
+            raise TypeError(f"geosrad_cosp_sghydro: no output {sorted(unknown)}")
+        shapes = {"prec_frac": (nlev, ncol, npoints), "mr_sub": (9, nlev, npoints), "mr_hydro_sg": (9, nlev, ncol, npoints)}
+        out = self._zeros([(k, shapes.get(k, (nlev, npoints))) for k in self.SGHYDRO_OUT if k in want])
+        self._host("geosrad_cosp_sghydro", a, out)
+        return out
+
+    def cosp_sghydro_dev(self, stream, npoints, nlev, ncol, ptr):
+        """`ptr`: name -> device address of frac_out_u8 (one byte per cell), mr_lsliq ... mr_lsgrpl and of the wanted outputs prec_frac_u8,
+        frac_ls, frac_cv, prec_ls, prec_cv, mr_sub, mr_hydro_sg (missing = NULL)."""
+        self._dev("geosrad_cosp_sghydro_dev", ptr, stream=stream, npoints=npoints, nlev=nlev, ncol=ncol)
+
+    def radar_gases(self, npoints, nlev, p, t, rh, zlev, freq, surface_radar=0, want=("g_vol", "g_to_vol")):
+        """gases (quickbeam/gases.f90) for every volume and path_integral to every gate (radar_simulator.f90:470-484): p (Pa), t (K), rh (%),
+        zlev (m) (nlev, npoints) TOA first, freq in GHz.  Returns dict(g_vol dB/km, g_to_vol dB (nlev, npoints)), float64 in either kind."""
+        a = {k: v for k, v in locals().items() if k not in ("self", "want")}
+        unknown = set(want) - {"g_vol", "g_to_vol"}
+        if unknown:
+            raise TypeError(f"geosrad_radar_gases: no output {sorted(unknown)}")
+        out = self._zeros([(k, (nlev, npoints)) for k in ("g_vol", "g_to_vol") if k in want], dtype=np.float64)
+        self._host("geosrad_radar_gases", a, out)
+        return out
+
+    def radar_gases_dev(self, stream, npoints, nlev, ptr, freq, surface_radar=0):
+        """`ptr`: name -> device address of p, t, rh, zlev and of the wanted outputs g_vol, g_to_vol (doubles; missing = NULL)."""
+        self._dev("geosrad_radar_gases_dev", ptr, stream=stream, npoints=npoints, nlev=nlev, freq=freq, surface_radar=surface_radar)
 
     # ---- Chou-Suarez SW, host arrays ---------------------------------------------------------------------
     def sorad(self, m, np_, nb, cosz, pl, ta, wa, oa, co2, cwc, fcld, ict, icb, reff, hk_uv, hk_ir, taua, ssaa, asya,

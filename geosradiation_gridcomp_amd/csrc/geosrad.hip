@@ -27,6 +27,7 @@
 #include "../../include/geosrad_satsim.h"
 #include "../../include/geosrad_misr_modis.h"
 #include "../../include/geosrad_lidar.h"
+#include "../../include/geosrad_radar.h"
 #include "dev_buf.hpp"
 #include "lw_device.hpp"
 #include "lw_kernels.hpp"
@@ -40,6 +41,7 @@
 #include "satsim_kernels.hpp"
 #include "misr_modis_kernels.hpp"
 #include "lidar_kernels.hpp"
+#include "radar_kernels.hpp"
 #include "lw_cols.hpp"
 #include "lw_split.hpp"
 #include "sw_reform.hpp"
@@ -789,6 +791,58 @@ struct geosrad_ctx {
         void *lidar[5];                 // clcalipso, cldlayer, cfad_sr, parasolrefl, lidarpmol
     };
     virtual int cosp_lidar_dev(hipStream_t, const CospLidarCall &) { return nodev("geosrad_cosp_lidar_dev"); }
+    // the radar simulator's front end (include/geosrad_radar.h): one record an entry point, shared by the `_dev` and the host variant
+    struct PrecScopsCall {
+        int npoints, nlev, ncol;
+        const void *ls, *cv;
+        const void *frac_out;           // bytes (`_dev`) or reals (host)
+        void *prec_frac;                // the same
+    };
+    int prec_scops_check(const PrecScopsCall &C)
+    {
+        if (const int rc = satsim_check("geosrad_prec_scops", C.npoints, C.nlev, C.ncol, 1, 1, 1)) return rc;
+        if (!C.ls || !C.cv || !C.frac_out || !C.prec_frac) return fail(GEOSRAD_EINVAL, "geosrad_prec_scops: null array");
+        return GEOSRAD_OK;
+    }
+    virtual int prec_scops_dev(hipStream_t, const PrecScopsCall &) { return nodev("geosrad_prec_scops_dev"); }
+    virtual int prec_scops_host(const PrecScopsCall &) = 0;
+    enum SgOut { SGO_FRAC_LS, SGO_FRAC_CV, SGO_PREC_LS, SGO_PREC_CV, SGO_MR_SUB, SGO_MR_SG, SGO_NOUT };
+    struct SgHydroCall {
+        int npoints, nlev, ncol;
+        const void *frac_out;           // bytes (`_dev`) or reals (host)
+        const void *mr[GEOSRAD_NHYDRO]; // the convective ones and the graupel may be null (zero)
+        void *prec_frac;                // bytes (`_dev`) or reals (host), may be null
+        void *out[SGO_NOUT];
+    };
+    int sghydro_check(const SgHydroCall &C)
+    {
+        if (const int rc = satsim_check("geosrad_cosp_sghydro", C.npoints, C.nlev, C.ncol, 1, 1, 1)) return rc;
+        bool ok = C.frac_out != nullptr;
+        for (int k = GEOSRAD_HYDRO_LSLIQ; k <= GEOSRAD_HYDRO_LSSNOW; k++) ok = ok && C.mr[k];
+        if (!ok) return fail(GEOSRAD_EINVAL, "geosrad_cosp_sghydro: null input array");
+        return GEOSRAD_OK;
+    }
+    virtual int sghydro_dev(hipStream_t, const SgHydroCall &) { return nodev("geosrad_cosp_sghydro_dev"); }
+    virtual int sghydro_host(const SgHydroCall &) = 0;
+    enum GasIn { GI_P, GI_T, GI_RH, GI_ZLEV, GI_NIN };
+    struct GasCall {
+        int npoints, nlev, surface_radar;
+        double freq;
+        const void *in[GI_NIN];
+        void *out[2];                   // g_vol, g_to_vol: doubles in either kind
+    };
+    int radar_gases_check(const GasCall &C)
+    {
+        if (const int rc = satsim_check("geosrad_radar_gases", C.npoints, C.nlev, 1, 1, 1, 1)) return rc;
+        // order_data knows a radar at the surface and a spaceborne one (format_input.f90:111-116)
+        if (C.surface_radar != 0 && C.surface_radar != 1) return fail(GEOSRAD_EINVAL, "geosrad_radar_gases: surface_radar must be 0 or 1");
+        if (!(C.freq > 0)) return fail(GEOSRAD_EINVAL, "geosrad_radar_gases: freq must be positive");
+        for (int k = 0; k < GI_NIN; k++)
+            if (!C.in[k]) return fail(GEOSRAD_EINVAL, "geosrad_radar_gases: null input array");
+        return GEOSRAD_OK;
+    }
+    virtual int radar_gases_dev(hipStream_t, const GasCall &) { return nodev("geosrad_radar_gases_dev"); }
+    virtual int radar_gases_host(const GasCall &) = 0;
 };
 
 // order of the `in` / `out` pointer arrays of sw_dev / sw_host
@@ -1128,7 +1182,7 @@ template <typename R> struct Ctx : geosrad_ctx {
     size_t workspace_bytes() const override
     {
         size_t t = 0;
-        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_ws_hb, &d_ws_ss, &d_ws_misr, &d_ws_modis, &d_ws_lidar, &d_zero, &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
+        for (const DevBuf<> *b : {&d_ws, &d_ws_sw, &d_ws_ch, &d_ws_lwk, &d_ws_so, &d_ws_drvs[0], &d_ws_drvs[1], &d_ws_hb, &d_ws_ss, &d_ws_misr, &d_ws_modis, &d_ws_lidar, &d_ws_radar, &d_zero, &d_io, &d_tab, &d_tab_sw, &d_tab_ch})
             t += b->bytes;
         return t;
     }
@@ -2140,20 +2194,27 @@ template <typename R> struct Ctx : geosrad_ctx {
     {
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamSynchronize(st));
-        uint32_t e2[6] = {0, 0, 0, 0, 0, 0};
-        HIPCHK(hipMemcpy(e2, d_err, 24, hipMemcpyDeviceToHost));
+        uint32_t e2[7] = {0, 0, 0, 0, 0, 0, 0};
+        HIPCHK(hipMemcpy(e2, d_err, 28, hipMemcpyDeviceToHost));
         // slot 0 = RRTMG_LW (+ McICA), slot 1 = RRTMG_SW; the Chou schemes have no input assertions (neither has the reference).
         // The host-pointer entry points look at their own solver's slot only (a flag left by an unchecked `_dev` call of the other
         // solver is that call's to report); geosrad_check reports either.  Only the slot that is reported is cleared - with the two
         // solvers on two streams the other one's flag stays up for the check of its own stream - and it is cleared in stream order
         // on `st`, so a kernel of the other solver running on another stream cannot lose a bit to it.
         // slot 3 = the range check of ICARUS (icarus.f:403-455), slot 4 = that of MODIS (modis_simulator.F90:202-206), reported last
-        // (slot 2 is k_chou_prep's and is not looked at here); slot 5 = the range check of the lidar simulator, reported after MODIS's
-        for (int k : {0, 1, 3, 4, 5})
+        // (slot 2 is k_chou_prep's and is not looked at here); slot 5 = the range check of the lidar simulator, reported after MODIS's;
+        // slot 6 = that of the radar's gaseous attenuation (geosrad_radar_gases), reported after the lidar's
+        for (int k : {0, 1, 3, 4, 5, 6})
             if (which >= 0 && which != k) e2[k] = 0;
-        if (!e2[0] && !e2[1] && !e2[3] && !e2[4] && !e2[5]) return GEOSRAD_OK;
-        HIPCHK(hipMemsetAsync(d_err + (e2[1] ? 1 : e2[0] ? 0 : e2[3] ? 3 : e2[4] ? 4 : 5), 0, 4, st));
+        if (!e2[0] && !e2[1] && !e2[3] && !e2[4] && !e2[5] && !e2[6]) return GEOSRAD_OK;
+        HIPCHK(hipMemsetAsync(d_err + (e2[1] ? 1 : e2[0] ? 0 : e2[3] ? 3 : e2[4] ? 4 : e2[5] ? 5 : 6), 0, 4, st));
         HIPCHK(hipStreamSynchronize(st));
+        if (!e2[0] && !e2[1] && !e2[3] && !e2[4] && !e2[5]) {
+            static const char *RD_NAMES[RDERR_N] = {"p", "t", "zlev (heights must decrease strictly with the level)"};
+            for (int k = 0; k < RDERR_N; k++)
+                if (e2[6] & (1u << k)) return fail(GEOSRAD_EINPUT, std::string("Input values out of bounds (radar_gases): ") + RD_NAMES[k]);
+            return fail(GEOSRAD_EINPUT, "device-side input check failed (radar_gases)");
+        }
         if (!e2[0] && !e2[1] && !e2[3] && !e2[4]) {
             if (e2[5] & (1u << LDERR_P)) return fail(GEOSRAD_EINPUT, "Input values out of bounds (lidar): p");
             if (e2[5] & (1u << LDERR_T)) return fail(GEOSRAD_EINPUT, "Input values out of bounds (lidar): t");
@@ -3393,6 +3454,172 @@ template <typename R> struct Ctx : geosrad_ctx {
         return lidar_launch(st, D);
     }
 
+    // =====================================================================================================
+    // the radar simulator's front end (include/geosrad_radar.h; radar_kernels.hpp)
+    // =====================================================================================================
+    DevBuf<> d_ws_radar;      // what the call at hand needs of: one byte per (point, sub-column) and per cell, nine and five (npoints,nlev) planes
+    // prec_scops on a record that prec_scops_check has passed; the rates are sums of up to three / two device planes (cosp.F90:404-408)
+    int prec_launch(hipStream_t st, int np, int nlev, int ncol, const R *const *ls, const R *const *cv, const uint8_t *frac, uint8_t *prec, uint8_t *colflag)
+    {
+        PrecArgs<R> A{};
+        A.npoints = np; A.nlev = nlev; A.ncol = ncol;
+        {
+#pragma clang fp contract(off)
+            A.cv_col = (int)((R)0.05 * (R)ncol);      // prec_scops.f:54-55, formed in the real kind
+        }
+        if (A.cv_col == 0) A.cv_col = 1;
+        for (int k = 0; k < 3; k++) A.ls[k] = ls[k];
+        for (int k = 0; k < 2; k++) A.cv[k] = cv[k];
+        A.frac = frac; A.prec = prec; A.colflag = colflag;
+        hipLaunchKernelGGL((k_prec_columns<R>), dim3(grid256((size_t)np * ncol)), dim3(256), 0, st, A);
+        hipLaunchKernelGGL((k_prec_scops<R>), dim3(grid256(np)), dim3(256), 0, st, A);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+    int prec_scops_dev(hipStream_t st, const PrecScopsCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = prec_scops_check(C)) return rc;
+        if (d_ws_radar.reserve((size_t)C.npoints * C.ncol) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the radar front end's workspace failed");
+        const R *ls[3] = {(const R *)C.ls, nullptr, nullptr}, *cv[2] = {(const R *)C.cv, nullptr};
+        return prec_launch(st, C.npoints, C.nlev, C.ncol, ls, cv, (const uint8_t *)C.frac_out, (uint8_t *)C.prec_frac, (uint8_t *)d_ws_radar.p);
+    }
+    int prec_scops_host(const PrecScopsCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = prec_scops_check(C)) return rc;
+        HostArrs H(sizeof(R));
+        PrecScopsCall D = C;
+        const void *frac_at = nullptr, *u8_at = nullptr, *p8_at = nullptr, *prec_at = nullptr;
+        const size_t cells = (size_t)C.ncol * C.nlev;
+        H.add(C.ls, nullptr, {(size_t)C.nlev, 1}, &D.ls);
+        H.add(C.cv, nullptr, {(size_t)C.nlev, 1}, &D.cv);
+        H.add(C.frac_out, nullptr, {cells, 1}, &frac_at);
+        H.add(nullptr, nullptr, {cells, 1}, &u8_at, 1);
+        H.add(nullptr, nullptr, {cells, 1}, &p8_at, 1);
+        H.add(nullptr, C.prec_frac, {cells, 1}, &prec_at);
+        const int rc = host_call(C.npoints, H, -1, [&](hipStream_t st, int nc) {
+            D.npoints = nc; D.frac_out = u8_at; D.prec_frac = (void *)p8_at;
+            const size_t nn = cells * nc;
+            hipLaunchKernelGGL((k_real_to_mask<R>), dim3(grid256(nn)), dim3(256), 0, st, nn, (const R *)frac_at, (uint8_t *)u8_at);
+            if (const int r = prec_scops_dev(st, D)) return r;
+            hipLaunchKernelGGL((k_mask_to_real<R>), dim3(grid256(nn)), dim3(256), 0, st, nn, (const uint8_t *)p8_at, (R *)prec_at);
+            return hip_rc("k_mask_to_real", hipGetLastError());
+        });
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(stream));
+        return GEOSRAD_OK;
+    }
+    // the sub-grid hydrometeor contents on a byte mask in HBM (a caller's, or the one SCOPS left in the workspace)
+    struct SgWs { uint8_t *colflag, *prec; R *mr_sub; };
+    size_t sg_layout(const SgHydroCall &C, SgWs &w, Carve c) const
+    {
+        const size_t np = (size_t)C.npoints;
+        w.colflag = c.take<uint8_t>(np * C.ncol);
+        w.prec = C.prec_frac ? nullptr : c.take<uint8_t>(np * C.ncol * C.nlev);
+        w.mr_sub = (C.out[SGO_MR_SUB] || !C.out[SGO_MR_SG]) ? nullptr : c.take<R>(np * C.nlev * GEOSRAD_NHYDRO);
+        return c.off;
+    }
+    int sghydro_launch(hipStream_t st, const SgHydroCall &C)
+    {
+        SgWs w;
+        const int np = C.npoints;
+        if (d_ws_radar.reserve(sg_layout(C, w, Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the radar front end's workspace failed");
+        sg_layout(C, w, Carve(d_ws_radar.p));
+        SgHydroArgs<R> A{};
+        A.npoints = np; A.nlev = C.nlev; A.ncol = C.ncol;
+        A.frac = (const uint8_t *)C.frac_out;
+        uint8_t *prec = C.prec_frac ? (uint8_t *)C.prec_frac : w.prec;
+        A.prec = prec;
+        for (int k = 0; k < GEOSRAD_NHYDRO; k++) A.mr[k] = (const R *)C.mr[k];
+        auto O = [&](int k) { return (R *)C.out[k]; };
+        A.frac_ls = O(SGO_FRAC_LS); A.frac_cv = O(SGO_FRAC_CV); A.prec_ls = O(SGO_PREC_LS); A.prec_cv = O(SGO_PREC_CV);
+        A.mr_sub = C.out[SGO_MR_SUB] ? O(SGO_MR_SUB) : w.mr_sub; A.mr_sg = O(SGO_MR_SG);
+        // cosp.F90:404-408: rain + snow + graupel, convective rain + snow
+        const R *ls[3] = {A.mr[GEOSRAD_HYDRO_LSRAIN], A.mr[GEOSRAD_HYDRO_LSSNOW], A.mr[GEOSRAD_HYDRO_LSGRPL]};
+        const R *cv[2] = {A.mr[GEOSRAD_HYDRO_CVRAIN], A.mr[GEOSRAD_HYDRO_CVSNOW]};
+        if (const int rc = prec_launch(st, np, C.nlev, C.ncol, ls, cv, A.frac, prec, w.colflag)) return rc;
+        hipLaunchKernelGGL((k_sghydro<R>), dim3(grid256(np), C.nlev), dim3(256), 0, st, A);
+        if (A.mr_sg) hipLaunchKernelGGL((k_sghydro_expand<R>), dim3(grid256((size_t)np * C.ncol), C.nlev), dim3(256), 0, st, A);
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+    int sghydro_dev(hipStream_t st, const SgHydroCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = sghydro_check(C)) return rc;
+        return sghydro_launch(st, C);
+    }
+    int sghydro_host(const SgHydroCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = sghydro_check(C)) return rc;
+        HostArrs H(sizeof(R));
+        SgHydroCall D = C;
+        const void *frac_at = nullptr, *u8_at = nullptr, *p8_at = nullptr, *prec_at = nullptr;
+        const size_t cells = (size_t)C.ncol * C.nlev, L = (size_t)C.nlev;
+        const size_t rows[SGO_NOUT] = {L, L, L, L, L * GEOSRAD_NHYDRO, cells * GEOSRAD_NHYDRO};
+        for (int k = 0; k < GEOSRAD_NHYDRO; k++) { D.mr[k] = nullptr; if (C.mr[k]) H.add(C.mr[k], nullptr, {L, 1}, &D.mr[k]); }
+        H.add(C.frac_out, nullptr, {cells, 1}, &frac_at);
+        H.add(nullptr, nullptr, {cells, 1}, &u8_at, 1);
+        if (C.prec_frac) { H.add(nullptr, nullptr, {cells, 1}, &p8_at, 1); H.add(nullptr, C.prec_frac, {cells, 1}, &prec_at); }
+        for (int k = 0; k < SGO_NOUT; k++) { D.out[k] = nullptr; if (C.out[k]) H.add(nullptr, C.out[k], {rows[k], 1}, (const void **)&D.out[k]); }
+        const int rc = host_call(C.npoints, H, -1, [&](hipStream_t st, int nc) {
+            D.npoints = nc; D.frac_out = u8_at; D.prec_frac = (void *)p8_at;
+            const size_t nn = cells * nc;
+            hipLaunchKernelGGL((k_real_to_mask<R>), dim3(grid256(nn)), dim3(256), 0, st, nn, (const R *)frac_at, (uint8_t *)u8_at);
+            if (const int r = sghydro_launch(st, D)) return r;
+            if (p8_at) hipLaunchKernelGGL((k_mask_to_real<R>), dim3(grid256(nn)), dim3(256), 0, st, nn, (const uint8_t *)p8_at, (R *)prec_at);
+            return hip_rc("k_mask_to_real", hipGetLastError());
+        });
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(stream));
+        return GEOSRAD_OK;
+    }
+    // the gaseous attenuation: every volume's, then the path to every gate
+    int radar_gases_launch(hipStream_t st, const GasCall &C)
+    {
+        const int np = C.npoints;
+        const size_t pl = (size_t)np * C.nlev;
+        GasArgs<R> A{};
+        auto carve = [&](Carve c) {
+            A.g = c.take<double>(pl); A.x = c.take<double>(pl); A.ca = c.take<double>(pl); A.cb = c.take<double>(pl); A.cc = c.take<double>(pl);
+            return c.off;
+        };
+        if (d_ws_radar.reserve(carve(Carve())) != hipSuccess) return fail(GEOSRAD_ENOMEM, "hipMalloc of the radar front end's workspace failed");
+        carve(Carve(d_ws_radar.p));
+        A.npoints = np; A.nlev = C.nlev; A.surface_radar = C.surface_radar; A.freq = C.freq;
+        A.p = (const R *)C.in[GI_P]; A.t = (const R *)C.in[GI_T]; A.rh = (const R *)C.in[GI_RH]; A.zlev = (const R *)C.in[GI_ZLEV];
+        A.g_vol = (double *)C.out[0]; A.g_to_vol = (double *)C.out[1];
+        A.err = d_err + 6;
+        hipLaunchKernelGGL((k_radar_gases<R>), dim3(grid256(np), C.nlev), dim3(256), 0, st, A);
+        if (A.g_to_vol) {
+            if (C.nlev > 2) hipLaunchKernelGGL((k_radar_gas_parab<R>), dim3(grid256(np), C.nlev - 2), dim3(256), 0, st, A);
+            hipLaunchKernelGGL((k_radar_gas_path<R>), dim3(grid256(np), C.nlev), dim3(256), 0, st, A);
+        }
+        HIPCHK(hipGetLastError());
+        return GEOSRAD_OK;
+    }
+    int radar_gases_dev(hipStream_t st, const GasCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = radar_gases_check(C)) return rc;
+        return radar_gases_launch(st, C);
+    }
+    int radar_gases_host(const GasCall &C) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (const int rc = radar_gases_check(C)) return rc;
+        HostArrs H(sizeof(R));
+        GasCall D = C;
+        for (int k = 0; k < GI_NIN; k++) H.add(C.in[k], nullptr, {(size_t)C.nlev, 1}, &D.in[k]);
+        for (int k = 0; k < 2; k++) { D.out[k] = nullptr; if (C.out[k]) H.add(nullptr, C.out[k], {(size_t)C.nlev, 1}, (const void **)&D.out[k], sizeof(double)); }
+        return host_call(C.npoints, H, 6, [&](hipStream_t st, int nc) {
+            D.npoints = nc;
+            return radar_gases_launch(st, D);
+        });
+    }
+
     // in: ple, t, fcld, qi, ql, qr, qs, ri, rl, rr, rs; out: tauir, cldtmp, cldprs
     int lw_cloud_diag_dev(hipStream_t st, int ncol, int lm, double grav, double undef, double taucrit, const void *const *in,
                           void *const *out) override
@@ -3682,6 +3909,37 @@ struct MultiCtx final : geosrad_ctx {
             for (int j = 0; j < LDI_NIN; j++) S.in[j] = off(C.in[j], c0);
             for (int j = 0; j < LDO_NOUT; j++) S.out[j] = off(C.out[j], c0);
             return k->lidar_host(S);
+        });
+    }
+    int prec_scops_host(const PrecScopsCall &C) override
+    {
+        if (const int rc = prec_scops_check(C)) return rc;
+        return run_shards(C.npoints, [&](geosrad_ctx *k, int c0, int nc) {
+            PrecScopsCall S = C;
+            S.npoints = nc; S.ls = off(C.ls, c0); S.cv = off(C.cv, c0); S.frac_out = off(C.frac_out, c0); S.prec_frac = off(C.prec_frac, c0);
+            return k->prec_scops_host(S);
+        });
+    }
+    int sghydro_host(const SgHydroCall &C) override
+    {
+        if (const int rc = sghydro_check(C)) return rc;
+        return run_shards(C.npoints, [&](geosrad_ctx *k, int c0, int nc) {
+            SgHydroCall S = C;
+            S.npoints = nc; S.frac_out = off(C.frac_out, c0); S.prec_frac = off(C.prec_frac, c0);
+            for (int j = 0; j < GEOSRAD_NHYDRO; j++) S.mr[j] = off(C.mr[j], c0);
+            for (int j = 0; j < SGO_NOUT; j++) S.out[j] = off(C.out[j], c0);
+            return k->sghydro_host(S);
+        });
+    }
+    int radar_gases_host(const GasCall &C) override
+    {
+        if (const int rc = radar_gases_check(C)) return rc;
+        return run_shards(C.npoints, [&](geosrad_ctx *k, int c0, int nc) {
+            GasCall S = C;
+            S.npoints = nc;
+            for (int j = 0; j < GI_NIN; j++) S.in[j] = off(C.in[j], c0);
+            for (int j = 0; j < 2; j++) S.out[j] = C.out[j] ? (char *)C.out[j] + (size_t)c0 * sizeof(double) : nullptr;      // doubles in either kind
+            return k->radar_gases_host(S);
         });
     }
     int mcica_host(int, int, int, const void *, const void *, int, const void *, const void *, const void *, const void *, double,
@@ -4566,6 +4824,49 @@ int geosrad_cosp_lidar_dev(geosrad_ctx *c, void *stream, int npoints, int lm, in
                                 frocean, ice_type, {clcalipso, cldlayer, cfad_sr, parasolrefl, lidarpmol}};
     C.cosp.ic.cosp = true; C.cosp.ic.seed = seed; C.cosp.ic.sgfcld = sgfcld;
     return c->cosp_lidar_dev((hipStream_t)stream, C);
+}
+
+// ---- include/geosrad_radar.h -------------------------------------------------------------------------------------------------
+int geosrad_prec_scops(geosrad_ctx *c, int npoints, int nlev, int ncol, const void *ls_p_rate, const void *cv_p_rate, const void *frac_out,
+                       void *prec_frac)
+{
+    return c ? c->prec_scops_host({npoints, nlev, ncol, ls_p_rate, cv_p_rate, frac_out, prec_frac}) : GEOSRAD_EINVAL;
+}
+int geosrad_prec_scops_dev(geosrad_ctx *c, void *stream, int npoints, int nlev, int ncol, const void *ls_p_rate, const void *cv_p_rate,
+                           const void *frac_out_u8, void *prec_frac_u8)
+{
+    return c ? c->prec_scops_dev((hipStream_t)stream, {npoints, nlev, ncol, ls_p_rate, cv_p_rate, frac_out_u8, prec_frac_u8}) : GEOSRAD_EINVAL;
+}
+#define SGHYDRO_CALL(frac, prec)                                                                                                         \
+    {npoints, nlev, ncol, frac, {mr_lsliq, mr_lsice, mr_lsrain, mr_lssnow, mr_cvliq, mr_cvice, mr_cvrain, mr_cvsnow, mr_lsgrpl}, prec,   \
+        {frac_ls, frac_cv, prec_ls, prec_cv, mr_sub, mr_hydro_sg}}
+int geosrad_cosp_sghydro(geosrad_ctx *c, int npoints, int nlev, int ncol, const void *frac_out, const void *mr_lsliq, const void *mr_lsice,
+                         const void *mr_lsrain, const void *mr_lssnow, const void *mr_cvliq, const void *mr_cvice, const void *mr_cvrain,
+                         const void *mr_cvsnow, const void *mr_lsgrpl, void *prec_frac, void *frac_ls, void *frac_cv, void *prec_ls,
+                         void *prec_cv, void *mr_sub, void *mr_hydro_sg)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    const geosrad_ctx::SgHydroCall C = SGHYDRO_CALL(frac_out, prec_frac);
+    return c->sghydro_host(C);
+}
+int geosrad_cosp_sghydro_dev(geosrad_ctx *c, void *stream, int npoints, int nlev, int ncol, const void *frac_out_u8, const void *mr_lsliq,
+                             const void *mr_lsice, const void *mr_lsrain, const void *mr_lssnow, const void *mr_cvliq, const void *mr_cvice,
+                             const void *mr_cvrain, const void *mr_cvsnow, const void *mr_lsgrpl, void *prec_frac_u8, void *frac_ls,
+                             void *frac_cv, void *prec_ls, void *prec_cv, void *mr_sub, void *mr_hydro_sg)
+{
+    if (!c) return GEOSRAD_EINVAL;
+    const geosrad_ctx::SgHydroCall C = SGHYDRO_CALL(frac_out_u8, prec_frac_u8);
+    return c->sghydro_dev((hipStream_t)stream, C);
+}
+int geosrad_radar_gases(geosrad_ctx *c, int npoints, int nlev, const void *p, const void *t, const void *rh, const void *zlev, double freq,
+                        int surface_radar, void *g_vol, void *g_to_vol)
+{
+    return c ? c->radar_gases_host({npoints, nlev, surface_radar, freq, {p, t, rh, zlev}, {g_vol, g_to_vol}}) : GEOSRAD_EINVAL;
+}
+int geosrad_radar_gases_dev(geosrad_ctx *c, void *stream, int npoints, int nlev, const void *p, const void *t, const void *rh,
+                            const void *zlev, double freq, int surface_radar, void *g_vol, void *g_to_vol)
+{
+    return c ? c->radar_gases_dev((hipStream_t)stream, {npoints, nlev, surface_radar, freq, {p, t, rh, zlev}, {g_vol, g_to_vol}}) : GEOSRAD_EINVAL;
 }
 int geosrad_misr_dev(geosrad_ctx *c, void *stream, int npoints, int nlev, int ncol, const int32_t *sunlit, const void *zfull, const void *at,
                      const void *dtau_s, const void *dtau_c, const void *frac_out_u8, double missing_value, void *fq_MISR_TAU_v_CTH,

@@ -16,7 +16,7 @@
  * for each of the four particle kinds.
  * Undefined is LIDAR_UNDEF = 999.999 inside and R_UNDEF = -1.0E30 in lidarcld, cldlayer, cfad_sr and parasolrefl, as cosp_stats.F90:137-140
  * leaves them.  Cloud fractions are fractions, not percent (the scaling of cosp_simulator.F90:160-165 hangs on flags GEOS_SatsimGridComp
- * never sets).  Not built: CLCALIPSO2 and CLTLIDARRADAR, which need the radar simulator, and statistics on another vertical grid
+ * never sets).  Not built: CLCALIPSO2 and CLTLIDARRADAR, which need the radar's reflectivity (geosrad_radar.h), and statistics on another grid
  * (cosp_change_vertical_grid; GEOS passes use_vgrid = .false., GEOS_SatsimGridComp.F90:3657). */
 #ifndef GEOSRAD_LIDAR_H
 #define GEOSRAD_LIDAR_H
