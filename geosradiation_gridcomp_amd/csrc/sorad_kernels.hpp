@@ -439,10 +439,16 @@ template <typename R> struct SoL5 { R rr, tt, td, rs, ts; };
 template <typename R> GR_DEV constexpr R so_no_aerosol() { return (R)0; }
 
 // the divisions of the adding equations and of the layers' mixed optical properties (~20 per level and pass in a class-7 column): hardware
-// reciprocal (1 ulp) in the fp32 instantiation, v_rcp_f64 + Newton steps (gr_div64) in the fp64 one, instead of the correctly rounded
-// expansions (10 / 12 instructions each).  deledd keeps the reference's fp64 arithmetic as it is.
+// reciprocal (1 ulp) and one correction step of the quotient in the fp32 instantiation, v_rcp_f64 + Newton steps (gr_div64) in the fp64 one,
+// instead of the correctly rounded expansions (10 / 12 instructions each).  deledd keeps the reference's fp64 arithmetic as it is.
+// The correction step (q += (a - b q) r, two FMAs) is not optional: the bare a * rcp(b) is biased, and through the adding recurrences the
+// bias reached 2.1 (flx) to 3.9 (flcu) times the r4 - r8 spread of the oracle (tests/test_gpu_fp32_spread.py, profiles/fp32_spread.md).
 #ifndef SO_EXACT_DIV
-GR_DEV float so_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
+GR_DEV float so_div(float a, float b)
+{
+    const float r = __builtin_amdgcn_rcpf(b), q = a * r;
+    return __builtin_fmaf(__builtin_fmaf(-b, q, a), r, q);
+}
 GR_DEV double so_div(double a, double b) { return gr_div64(a, b); }
 #else
 template <typename R> GR_DEV R so_div(R a, R b) { return a / b; }
